@@ -15,7 +15,9 @@ problem are dealt over the ranks by work (strong scaling, no collective in the a
 slab of its rows, about N^2 / (2 N_gpus) doubles, the operator is DistributedSlab_LinearOperator and its matvec all-reduces
 an N-vector over RCCL.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0 (value, ms_per_step).  --full adds what
+takes runs of its own: per-kernel times and the roofline, the operator at work (matvec, CG), the CPU baseline and the other
+BASELINE.json configurations.  --dump-outputs DIR writes a seeded sample of the block the last timed step assembled (N = 1).
 """
 import argparse
 import gc
@@ -459,6 +461,107 @@ def c4_distributed_leg(args, world, rank, dev, sync):
                 matvec_ms=1e3*mv, cg_jacobi_iterations=int(its), cg_jacobi_ms=1e3*t_cg, cg_residual=float(res[-1]))
 
 
+def dump_outputs(dirname, A, budget_bytes=64 << 20):
+    """--dump-outputs: what the last timed step handed its caller, the N x N block (19 GB at the default size), as a fixed
+    sample in float64: A_diagonal, A_rows (whole rows at seeded positions, at most half the budget) and A_entries (2^20 single
+    entries at seeded positions).  The positions depend on N only, so two builds of the project compare entry for entry."""
+    import numpy as np
+    import torch
+    N = A.shape[0]
+    rng = np.random.default_rng(0)
+    rows = np.sort(rng.choice(N, size=max(1, min(32, N, budget_bytes//2//(8*N))), replace=False))
+    ij = rng.integers(0, N, size=(2, 1 << 20))
+    on_dev = lambda a: torch.from_numpy(a).to(A.device)
+    out = {'A_diagonal': torch.diagonal(A), 'A_rows': A[on_dev(rows)], 'A_entries': A[on_dev(ij[0]), on_dev(ij[1])]}
+    assert sum(8*t.numel() for t in out.values()) <= budget_bytes
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(dirname, name+'.npy'), t.cpu().numpy())
+
+
+def roofline_of_step(args, world, dev, builder, ctx, step, cnt, N, elapsed):
+    """--full: per-kernel device times and the roofline of the dominant tile kernel; returns (roofline, phases_ms)."""
+    import torch
+    phase_acc = {}
+    # a few extra (untimed) steps to average every tile kernel's duration from its own HIP events (recorded by the library
+    # on the stream the kernels run on)
+    kacc = {}
+    for _ in range(3):
+        step()
+        torch.cuda.synchronize(dev)
+        m = ctx.phase_ms()
+        for k, v in m.items():
+            phase_acc[k] = phase_acc.get(k, 0.)+v/3.
+        for k, v in ctx.kernel_ms().items():
+            kacc[k] = kacc.get(k, 0.)+v/3.
+
+    # ---- roofline of the dominant kernel: algorithmic flops / its own event-timed duration --------------------------
+    # Distant pairs of the orders packed into the tile rule table (<= 16 points) are integrated by the tile kernels: the
+    # uniform-tile kernels (tiles whose pairs are all of order 2: k_tile_uniform<3,3>; all of order 3 / 4: k_tile_uniform<3,6>) and the
+    # general one (k_tile_distant: every other tile).  The counters tell how many pairs of each order the uniform kernels
+    # took; the rest of the histogram belongs to the general kernel.
+    T = builder.tables
+    tile_orders = {q: c for q, c in cnt['orders'].items() if T.num_points(q) <= 16 and q < 18}
+    uni = cnt.get('uniformTilePairsByOrder', {})
+    mixed_orders = {q: c-uni.get(q, 0) for q, c in tile_orders.items()}
+    kernels = {'k_tile_distant': (algorithmic_flops(mixed_orders, T.num_points), 1e-3*kacc.get('tile_general', 0.)),
+               'k_tile_uniform<3,3> (order 2)': (algorithmic_flops({2: uni.get(2, 0)}, T.num_points), 1e-3*kacc.get('tile_uniform2', 0.)),
+               'k_tile_uniform<3,6> (order 3)': (algorithmic_flops({3: uni.get(3, 0)}, T.num_points), 1e-3*kacc.get('tile_uniform3', 0.)),
+               'k_tile_uniform<3,6> (order 4)': (algorithmic_flops({4: uni.get(4, 0)}, T.num_points), 1e-3*kacc.get('tile_uniform4', 0.))}
+    dominant = max(kernels, key=lambda k: kernels[k][1])
+    dom_flops, dom_s = kernels[dominant]
+    achieved = dom_flops/dom_s/1e12 if dom_s > 0 else 0.
+    both_s = sum(v[1] for v in kernels.values())
+    all_flops = sum(v[0] for v in kernels.values())
+    # HBM traffic of the dominant kernel: PMC counters cannot be read inside this process; tools/profile_round.sh runs this
+    # command under rocprofv3 --pmc (separate passes) and tools/collect_profiles.py records the kernel sources it measured.  The number is used only
+    # if it belongs to the library and the workload of this run, never a stale constant.
+    traffic, traffic_note = None, 'no PMC record (tools/profile_round.sh + tools/collect_profiles.py) for these kernel sources and this workload'
+    pmc_fn = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
+    if os.path.exists(pmc_fn) and world == 1:
+        from pynucleus_amd import _lib as _l
+        src_sha = _l.source_sha16()
+        with open(pmc_fn) as f:
+            rec = json.load(f)
+        key = 'noRef{}{}'.format(args.noRef, '' if args.sectors == 6 else '_s{}'.format(args.sectors))
+        if key in rec and rec[key].get('src_sha16') == src_sha:
+            # record keys: k_tile_distant, k_tile_uniform_3_3 (order 2), k_tile_uniform_3_6 (orders 3 and 4), k_fold_mirror
+            tkey = {'k_tile_distant': 'k_tile_distant', 'k_tile_uniform<3,3> (order 2)': 'k_tile_uniform_3_3',
+                    'k_tile_uniform<3,6> (order 3)': 'k_tile_uniform_3_6', 'k_tile_uniform<3,6> (order 4)': 'k_tile_uniform_3_6'}[dominant]
+            traffic = rec[key].get(tkey+'_hbm_bytes_per_launch')
+            traffic_note = 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command ({}), FETCH_SIZE doubled for the tile kernels'.format(rec[key].get('tag'))
+    # HBM view of the same launches: the algorithmic minimum is one write of the upper block triangle they fill
+    hbm_alg_bytes = 8.*N*N/2
+    # the hardware view next to the SURVEY 8(d) units: VALU issue utilisation = SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x kernel
+    # cycles at 2.4 GHz) from the committed PMC record of these sources (the factorised evaluator executes about a third of the
+    # reference's flop count, so `frac` can exceed what the issue slots say); whole_step_frac = all algorithmic flops of the step
+    # (every kernel evaluation and pair, SURVEY 8(d)) over the whole step time
+    valu_util, valu_note = None, traffic_note
+    if traffic is not None:
+        insts = rec[key].get(tkey+'_sq_insts_valu')
+        if insts and dom_s > 0:
+            valu_util = insts*4./(1024.*dom_s*2.4e9)
+            valu_note = 'SQ_INSTS_VALU per launch x 4 cycles / (1024 SIMDs x kernel time x 2.4 GHz), rocprofv3 --pmc pass ({})'.format(rec[key].get('tag'))
+    step_s = elapsed/args.steps
+    whole_flops = flops_from_counters(cnt, 3) if world == 1 else None
+    roofline = dict(bound='fp64_valu', kernel=dominant, achieved=achieved, peak=FP64_VECTOR_PEAK_TFLOPS, unit='TFLOP/s',
+                    frac=achieved/FP64_VECTOR_PEAK_TFLOPS,
+                    frac_note='achieved counts the flop of the reference\'s evaluation per pair (SURVEY 8(d): 759 for an order-2 P1 pair); the kernel '
+                              'forms the same local matrix from row / column sums of the kernel values in about 200 VALU instructions per pair, so frac '
+                              'can exceed 1; valu_issue_util is the executed-instruction view (at the nominal 2.4 GHz; under fp64 load the clock '
+                              'sustains about 1.7 GHz, tools/probes/valu_rate_probe.hip: 5.67 nominal cycles per v_fma_f64 of a wave)',
+                    traffic=traffic, traffic_note=traffic_note, algorithmic_flops_per_launch=dom_flops,
+                    valu_issue_util=valu_util, valu_issue_note=valu_note,
+                    whole_step_frac=(whole_flops/step_s/1e12/FP64_VECTOR_PEAK_TFLOPS) if whole_flops else None,
+                    whole_step_algorithmic_flops=whole_flops,
+                    kernel_ms=1e3*dom_s,
+                    tile_kernels={k: dict(algorithmic_flops_per_launch=v[0], kernel_ms=1e3*v[1],
+                                          achieved=v[0]/v[1]/1e12 if v[1] > 0 else 0.) for k, v in kernels.items()},
+                    tile_phase_achieved=all_flops/both_s/1e12 if both_s > 0 else 0.,
+                    hbm_algorithmic_GBs=hbm_alg_bytes/both_s/1e9 if both_s > 0 else 0., hbm_peak_GBs=HBM_PEAK_GBS)
+    return roofline, phase_acc
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -467,10 +570,18 @@ def main():
     ap.add_argument('--noRef', type=int, default=7)
     ap.add_argument('--s', type=float, default=0.5)
     ap.add_argument('--sectors', type=int, default=6, help='triangles of the initial fan (6 = the reference disc; 12 at noRef 7 gives 97 921 DoFs)')
-    ap.add_argument('--cpu-seconds', type=float, default=15., help='target CPU time of the oracle sample (rank 0, N=1 only)')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the short legs of the other BASELINE.json configurations (N=1 only)')
+    ap.add_argument('--full', action='store_true', help='beside the headline: per-kernel times and roofline, matvec and CG with the '
+                    'assembled operator, the CPU baseline and the other BASELINE.json configurations')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write a seeded sample of the block the last timed step assembled as '
+                    'DIR/<name>.npy (float64, N=1 only)')
+    ap.add_argument('--cpu-seconds', type=float, default=15., help='target CPU time of the oracle sample (--full, rank 0, N=1 only)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='--full without the short legs of the other BASELINE.json configurations')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.gpus > 1:
+        ap.error('--dump-outputs needs --gpus 1: with more ranks no process holds the whole block')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # bare command: this process becomes the launcher of its own ranks (nothing GPU-related has been imported yet)
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -544,26 +655,14 @@ def main():
     for _ in range(args.warmup):
         step()
     sync()
-    phase_acc = {}
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     sync()
     elapsed = time.perf_counter()-t0
-    # phases of the last step from HIP events recorded on the stream the kernels ran on
-    ms = ctx.phase_ms()
     cnt = ctx.counters()
-    # a few extra (untimed) steps to average every tile kernel's duration from its own HIP events (recorded by the library
-    # on the stream the kernels run on)
-    kacc = {}
-    for _ in range(3):
-        step()
-        torch.cuda.synchronize(dev)
-        m = ctx.phase_ms()
-        for k, v in m.items():
-            phase_acc[k] = phase_acc.get(k, 0.)+v/3.
-        for k, v in ctx.kernel_ms().items():
-            kacc[k] = kacc.get(k, 0.)+v/3.
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, A)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -575,80 +674,22 @@ def main():
         pairs_total = float(cnt['numAssembledCellPairs'])
     value = pairs_total*args.steps/elapsed
 
-    # ---- roofline of the dominant kernel: algorithmic flops / its own event-timed duration --------------------------
-    # Distant pairs of the orders packed into the tile rule table (<= 16 points) are integrated by the tile kernels: the
-    # uniform-tile kernels (tiles whose pairs are all of order 2: k_tile_uniform<3,3>; all of order 3 / 4: k_tile_uniform<3,6>) and the
-    # general one (k_tile_distant: every other tile).  The counters tell how many pairs of each order the uniform kernels
-    # took; the rest of the histogram belongs to the general kernel.
-    T = builder.tables
-    tile_orders = {q: c for q, c in cnt['orders'].items() if T.num_points(q) <= 16 and q < 18}
-    uni = cnt.get('uniformTilePairsByOrder', {})
-    mixed_orders = {q: c-uni.get(q, 0) for q, c in tile_orders.items()}
-    kernels = {'k_tile_distant': (algorithmic_flops(mixed_orders, T.num_points), 1e-3*kacc.get('tile_general', 0.)),
-               'k_tile_uniform<3,3> (order 2)': (algorithmic_flops({2: uni.get(2, 0)}, T.num_points), 1e-3*kacc.get('tile_uniform2', 0.)),
-               'k_tile_uniform<3,6> (order 3)': (algorithmic_flops({3: uni.get(3, 0)}, T.num_points), 1e-3*kacc.get('tile_uniform3', 0.)),
-               'k_tile_uniform<3,6> (order 4)': (algorithmic_flops({4: uni.get(4, 0)}, T.num_points), 1e-3*kacc.get('tile_uniform4', 0.))}
-    dominant = max(kernels, key=lambda k: kernels[k][1])
-    dom_flops, dom_s = kernels[dominant]
-    achieved = dom_flops/dom_s/1e12 if dom_s > 0 else 0.
-    both_s = sum(v[1] for v in kernels.values())
-    all_flops = sum(v[0] for v in kernels.values())
-    # HBM traffic of the dominant kernel: PMC counters cannot be read inside this process; tools/profile_round.sh runs this
-    # command under rocprofv3 --pmc (separate passes) and tools/collect_profiles.py records the kernel sources it measured.  The number is used only
-    # if it belongs to the library and the workload of this run, never a stale constant.
-    traffic, traffic_note = None, 'no PMC record (tools/profile_round.sh + tools/collect_profiles.py) for these kernel sources and this workload'
-    pmc_fn = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
-    if os.path.exists(pmc_fn) and world == 1:
-        from pynucleus_amd import _lib as _l
-        src_sha = _l.source_sha16()
-        with open(pmc_fn) as f:
-            rec = json.load(f)
-        key = 'noRef{}{}'.format(args.noRef, '' if args.sectors == 6 else '_s{}'.format(args.sectors))
-        if key in rec and rec[key].get('src_sha16') == src_sha:
-            # record keys: k_tile_distant, k_tile_uniform_3_3 (order 2), k_tile_uniform_3_6 (orders 3 and 4), k_fold_mirror
-            tkey = {'k_tile_distant': 'k_tile_distant', 'k_tile_uniform<3,3> (order 2)': 'k_tile_uniform_3_3',
-                    'k_tile_uniform<3,6> (order 3)': 'k_tile_uniform_3_6', 'k_tile_uniform<3,6> (order 4)': 'k_tile_uniform_3_6'}[dominant]
-            traffic = rec[key].get(tkey+'_hbm_bytes_per_launch')
-            traffic_note = 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command ({}), FETCH_SIZE doubled per MI355X_MICROARCH.md'.format(rec[key].get('tag'))
-    # HBM view of the same launches: the algorithmic minimum is one write of the upper block triangle they fill
-    hbm_alg_bytes = 8.*N*N/2
-    # the hardware view next to the SURVEY 8(d) units: VALU issue utilisation = SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x kernel
-    # cycles at 2.4 GHz) from the committed PMC record of these sources (the factorised evaluator executes about a third of the
-    # reference's flop count, so `frac` can exceed what the issue slots say); whole_step_frac = all algorithmic flops of the step
-    # (every kernel evaluation and pair) over the whole step time
-    valu_util, valu_note = None, traffic_note
-    if traffic is not None:
-        insts = rec[key].get(tkey+'_sq_insts_valu')
-        if insts and dom_s > 0:
-            valu_util = insts*4./(1024.*dom_s*2.4e9)
-            valu_note = 'SQ_INSTS_VALU per launch x 4 cycles / (1024 SIMDs x kernel time x 2.4 GHz), rocprofv3 --pmc pass ({})'.format(rec[key].get('tag'))
-    step_s = elapsed/args.steps
-    whole_flops = flops_from_counters(cnt, 3) if world == 1 else None
-    roofline = dict(bound='fp64_valu', kernel=dominant, achieved=achieved, peak=FP64_VECTOR_PEAK_TFLOPS, unit='TFLOP/s',
-                    frac=achieved/FP64_VECTOR_PEAK_TFLOPS,
-                    frac_note='achieved counts the flop of the reference\'s evaluation per pair (SURVEY 8(d): 759 for an order-2 P1 pair); the kernel '
-                              'forms the same local matrix from row / column sums of the kernel values in about 200 VALU instructions per pair, so frac '
-                              'can exceed 1; valu_issue_util is the executed-instruction view (at the nominal 2.4 GHz; under fp64 load the clock '
-                              'sustains about 1.7 GHz, tools/probes/valu_rate_probe.hip: 5.67 nominal cycles per v_fma_f64 of a wave)',
-                    traffic=traffic, traffic_note=traffic_note, algorithmic_flops_per_launch=dom_flops,
-                    valu_issue_util=valu_util, valu_issue_note=valu_note,
-                    whole_step_frac=(whole_flops/step_s/1e12/FP64_VECTOR_PEAK_TFLOPS) if whole_flops else None,
-                    whole_step_algorithmic_flops=whole_flops,
-                    kernel_ms=1e3*dom_s,
-                    tile_kernels={k: dict(algorithmic_flops_per_launch=v[0], kernel_ms=1e3*v[1],
-                                          achieved=v[0]/v[1]/1e12 if v[1] > 0 else 0.) for k, v in kernels.items()},
-                    tile_phase_achieved=all_flops/both_s/1e12 if both_s > 0 else 0.,
-                    hbm_algorithmic_GBs=hbm_alg_bytes/both_s/1e9 if both_s > 0 else 0., hbm_peak_GBs=HBM_PEAK_GBS)
-
     out = dict(metric='element-pairs/sec assembled (2D P1 fractional s=0.5, dense) + % fp64 roofline', value=value,
                unit='element-pairs/s', n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=1e3*elapsed/args.steps,
                higher_is_better=True, scaling='strong', vs_baseline=None, dtype='f64', data='synthetic',
                config=dict(workload='2D unit disc ({}uniform_disc refined {}x, {} cells), P1, {} DoFs, fractional s={}, horizon=inf, '
                            'dense getDense incl. zeroExterior; {} element pairs/step'.format('' if args.sectors == 6 else '{}-sector '.format(args.sectors), args.noRef, nc, N, args.s, int(pairs_total)),
                            noRef=args.noRef, num_dofs=N, num_cells=nc, parallelism='block rows of the upper triangle dealt over {} GPU(s), row-owned one-sided slabs'.format(world)),
-               roofline=roofline,
-               phases_ms={k: round(v, 4) for k, v in phase_acc.items()},
                kernel_evaluations_per_step=cnt['numIntegrations'] if world == 1 else None)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    out['roofline'], phase_acc = roofline_of_step(args, world, dev, builder, ctx, step, cnt, N, elapsed)
+    out['phases_ms'] = {k: round(v, 4) for k, v in phase_acc.items()}
 
     # ---- the assembled operator at work (north star: "RCCL all-reduce over xGMI for the assembled matvec"): y = A x and a
     # Jacobi-CG solve of A u = f, f = 1.  N = 1: k_gemv on the N x N block; N > 1: DistributedSlab_LinearOperator -- local slab
@@ -660,7 +701,7 @@ def main():
 
     # ---- CPU baseline: the C oracle (reference loop order) on bounded samples of the same workload -------------------
     if rank == 0 and world == 1 and not args.no_cpu:
-        out['cpu_baseline'] = cpu_baseline(args, T, N, nc, value)
+        out['cpu_baseline'] = cpu_baseline(args, builder.tables, N, nc, value)
     # ---- the other BASELINE.json configurations, each a short driver-timed leg (N = 1 only) ---------------------------
     if rank == 0 and world == 1 and not args.no_extra:
         del A
