@@ -261,6 +261,20 @@ inline DevProblem tile_problem(const pnl_context *ctx) {
     return Pt;
 }
 
+// what the mixed-tile kernel (k_tile_distant) needs beyond that: the orbit-ordered rule blocks of the orders 2 .. 4 and the orders
+// whose pairs take the structured evaluators (2D P1, rules with the orbit structure; none with the option PNL_MIXED_GENERIC)
+inline DevProblem with_mixed_rules(const pnl_context *ctx, DevProblem Pt) {
+    Pt.uni = (const double*)ctx->b_uni.p;
+    Pt.mix_struct = 0;
+    const bool generic = pnl_tune("PNL_MIXED_GENERIC") != nullptr;
+    for (int q = 0; q < 5; q++) {
+        Pt.uni_off[q] = ctx->uni_off[q] >= 0 ? ctx->uni_off[q] : 0;
+        if (q >= 2 && q <= ctx->qmax && ctx->dim == 2 && ctx->dpe == 3 && ctx->uni_off[q] >= 0 && ctx->uni_struct[q] && !generic)
+            Pt.mix_struct |= 1 << q;
+    }
+    return Pt;
+}
+
 
 inline void kt_begin(pnl_context *ctx, int slot) { (void)hipEventRecord(ctx->kev[slot][0], ctx->stream); }
 inline void kt_end(pnl_context *ctx, int slot) { (void)hipEventRecord(ctx->kev[slot][1], ctx->stream); ctx->kev_set[slot] = true; }

@@ -83,6 +83,11 @@ struct DevProblem {
     // symmetric contributions are written once, at (min, max), the operator is A' + A'^T - diag(A')
     const int *rowmap, *colmap;
     int onesided, pad3;
+    // mixed tiles (k_tile_distant, 2D P1): rule blocks of the uniform tiles (pnl_context::b_uni, points in orbit order) and the
+    // orders 2 .. 4 whose rule has the orbit structure (bit q; 0 with PNL_MIXED_GENERIC): their pairs take the structured evaluators
+    const double *uni = nullptr;
+    int uni_off[5] = {0, 0, 0, 0, 0};
+    int mix_struct = 0;
 };
 
 // row of the dense output that global DoF I is stored in (identity without a row slab); -1: not stored by this rank

@@ -733,7 +733,7 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
     SOk.nU = ctx->nU;                                       // rows of the LDS sub-block (also without the block-slot storage)
     kt_begin(ctx, PNL_K_TILE_GENERAL);
     if (grid > 0)
-        hipLaunchKernelGGL(kfun, dim3(grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->tile_off, A,
+        hipLaunchKernelGGL(kfun, dim3(grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)), (const int2*)ctx->b_tiles.p+ctx->tile_off, A,
                            (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), cell_begin, cell_end, acc_stride, (int4*)ctx->b_wl.p,
                            wlc, ctx->wl_cap_each, ctx->ablate | (ctx->symflush ? 256 : 0), ntiles, ClusterTiles{},
                            (unsigned*)ctx->b_tilectr.p, SOk);
@@ -1321,7 +1321,7 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
         if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] cluster tiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", pl->ntiles,
                                            pl->chunk_stride, lds, per_cu);
         const int grid = pnl_grid_cap(std::min(pl->ntiles, 256*std::max(per_cu, 1)));
-        hipLaunchKernelGGL(kfun, dim3(grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, ctx->P, (const int2*)nullptr, (double*)nullptr, 0ll,
+        hipLaunchKernelGGL(kfun, dim3(grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, ctx->P), (const int2*)nullptr, (double*)nullptr, 0ll,
                            (double*)nullptr, 0, ctx->nc, acc_stride, (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, ctx->wl_cap, 0,
                            pl->ntiles, CT, (unsigned*)ctx->b_tilectr.p, SlotOut{});
         HIPCHK(ctx, hipGetLastError());
@@ -1930,7 +1930,7 @@ const char *const k_product_options[] = {"PNL_WL_FRAC", "PNL_FH_NOTILES", "PNL_N
                                          "PNL_NO_OVERLAP", "PNL_NO_FORK",
                                          // tests: at most this many workgroups of a persistent tile kernel (every workgroup then walks
                                          // many tiles at test sizes: the pipelined tile loops against the oracle)
-                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC"};
+                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_MIXED_GENERIC"};
 }  // namespace
 
 const char *pnl_tune(const char *name) {

@@ -218,6 +218,140 @@ __device__ __forceinline__ void eval_distant_lds(const DevProblem &P, const doub
     }
 }
 
+// Structured evaluators of the mixed tiles (2D P1; pnl_context::uni_struct): the rule block of the uniform tiles (layout bary[n][3],
+// w[n], w phi[n][3], w phi_a phi_b[6][n]; points in orbit order) read through the scalar cache once per pair.  In an orbit o of three points of
+// equal weight w_o, w_o phi_b(x_(o,p)) = A_o + B_o delta_bp, and w phi_a phi_b at its points is K0_o + K1_o (delta_ap + delta_bp)
+// + K2_o delta_ap delta_bp.  With g_ij = gamma(x_i, y_j), r_i = sum_j w_j g_ij and c_j = sum_i w_i g_ij:
+//   G[a][b] = sum_i (A_o(i) + B_o(i) delta_(a,p(i))) u_b(i),   u_b(i) = sum_j g_ij (A_o(j) + B_o(j) delta_(b,p(j)))
+//   S1[ab]  = sum_i (K0 + K1 (delta_ap + delta_bp) + K2 delta_ap delta_bp)_o(i) r_i, S2 the same with c_j
+// -- the algebra of k_tile_uniform<3, 3 | 6, KT, true> (pnl_tile2.h), here for one pair per lane with the factors S1 / S2 of
+// PairAcc.  Three points (one orbit): K0 = A^2 / w, K1 = A B / w, K2 = B^2 / w, i.e. G = B^2 g_ab + A B (s_a + c_b) + A^2 S.
+template <int KT>
+__device__ __forceinline__ void eval_struct3(const DevKernel &kk, pnl_const_f64_ptr rule, const double *av, const double *bv,
+                                             PairAcc<2, 3> &R, const double *__restrict__ lpow) {
+    constexpr int R_WPH = 12;                            // bary[3][3], w[3], w phi[3][3]
+    double x[3][2], y[3][2];
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            double sx = 0., sy = 0.;
+#pragma unroll
+            for (int k = 0; k < 3; k++) { sx = __builtin_fma(rule[3*p+k], av[2*k+d], sx); sy = __builtin_fma(rule[3*p+k], bv[2*k+d], sy); }
+            x[p][d] = sx; y[p][d] = sy;
+        }
+    double g[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            double d2 = 0.;
+#pragma unroll
+            for (int d = 0; d < 2; d++) { const double t = x[a][d]-y[b][d]; d2 = __builtin_fma(t, t, d2); }
+            g[a][b] = kern_eval<KT>(kk, d2, lpow);
+        }
+    double sr[3], sc[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) { sr[a] = (g[a][0]+g[a][1])+g[a][2]; sc[a] = (g[0][a]+g[1][a])+g[2][a]; }
+    const double S = (sr[0]+sr[1])+sr[2];
+    const double A = rule[R_WPH+1], B = rule[R_WPH]-rule[R_WPH+1];
+    const double k2 = B*B, k1 = A*B, T = (A*A)*S;
+    double ra[3], rc[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) { ra[a] = __builtin_fma(k1, sr[a], T); rc[a] = k1*sc[a]; }
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) R.G[a][b] = __builtin_fma(k2, g[a][b], ra[a]+rc[b]);
+    // r_i = w s_i, c_j = w sc_j: the 1 / w of K0..K2 cancels
+    int e = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = a; b < 3; b++) {
+            R.S1[e] = __builtin_fma(k1, sr[a]+sr[b], a == b ? __builtin_fma(k2, sr[a], T) : T);
+            R.S2[e] = __builtin_fma(k1, sc[a]+sc[b], a == b ? __builtin_fma(k2, sc[a], T) : T);
+            e++;
+        }
+}
+
+// six points in two orbits (o = 0: points 0 .. 2, o = 1: points 3 .. 5 of the rule block).  The columns run in orbit order (their
+// points and constants once per pair); per row of the rule: six kernel values, the orbit sums s_0, s_1 and from them r and u_b (14
+// instead of 24 instructions).  The rows need no structure: their constants come from the tile's LDS copy tab (packed point order,
+// layout bary[3], w, phi[3]; broadcast reads) as in eval_distant_fixed, and the row loop stays rolled.
+template <int KT>
+__device__ __forceinline__ void eval_struct6(const DevKernel &kk, pnl_const_f64_ptr rule, const double *__restrict__ tab, const double *av,
+                                             const double *bv, PairAcc<2, 3> &R, const double *__restrict__ lpow) {
+    constexpr int NP = 6, ST = 7, R_W = 3*NP, R_WPH = R_W+NP, R_PP = R_WPH+3*NP;
+    double y[NP][2], c[NP];
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+        c[j] = 0.;
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            double s = 0.;
+#pragma unroll
+            for (int k = 0; k < 3; k++) s = __builtin_fma(rule[3*j+k], bv[2*k+d], s);
+            y[j][d] = s;
+        }
+    }
+    // column orbits: weights and A_o, B_o
+    const double w0 = rule[R_W], w1 = rule[R_W+3];
+    const double A0 = rule[R_WPH+1], B0 = rule[R_WPH]-A0, A1 = rule[R_WPH+3*3+1], B1 = rule[R_WPH+3*3]-A1;
+#pragma unroll 1
+    for (int i = 0; i < NP; i++) {
+        double x[2];
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            double s = 0.;
+#pragma unroll
+            for (int k = 0; k < 3; k++) s = __builtin_fma(tab[i*ST+k], av[2*k+d], s);
+            x[d] = s;
+        }
+        const double wi = tab[i*ST+3];
+        double g[NP];
+#pragma unroll
+        for (int j = 0; j < NP; j++) {
+            double d2 = 0.;
+#pragma unroll
+            for (int d = 0; d < 2; d++) { const double t = x[d]-y[j][d]; d2 = __builtin_fma(t, t, d2); }
+            g[j] = kern_eval<KT>(kk, d2, lpow);
+            c[j] = __builtin_fma(wi, g[j], c[j]);
+        }
+        const double s0 = (g[0]+g[1])+g[2], s1 = (g[3]+g[4])+g[5];
+        const double r = __builtin_fma(w0, s0, w1*s1);
+        const double base = __builtin_fma(A0, s0, A1*s1);
+        double u[3];
+#pragma unroll
+        for (int b = 0; b < 3; b++) u[b] = __builtin_fma(B0, g[b], __builtin_fma(B1, g[3+b], base));
+        int e = 0;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const double pa = wi*tab[i*ST+4+a];
+#pragma unroll
+            for (int b = 0; b < 3; b++) R.G[a][b] = __builtin_fma(pa, u[b], R.G[a][b]);
+            const double pr = pa*r;
+#pragma unroll
+            for (int b = a; b < 3; b++) { R.S1[e] = __builtin_fma(pr, tab[i*ST+4+b], R.S1[e]); e++; }
+        }
+    }
+    // S2 from the column sums; per orbit of the columns w phi_a phi_b = K0 + K1 (delta_ap + delta_bp) + K2 delta_ap delta_bp
+    const double K00 = rule[R_PP+NP+2], K10 = rule[R_PP+NP]-K00, K20 = rule[R_PP]-(K00+2.*K10);
+    const double K01 = rule[R_PP+NP+5], K11 = rule[R_PP+NP+3]-K01, K21 = rule[R_PP+3]-(K01+2.*K11);
+    const double T2 = __builtin_fma(K00, (c[0]+c[1])+c[2], K01*((c[3]+c[4])+c[5]));
+    double Q2[3], D2[3];
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        Q2[p] = __builtin_fma(K10, c[p], K11*c[3+p]);
+        D2[p] = __builtin_fma(K20, c[p], K21*c[3+p]);
+    }
+    int e = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = a; b < 3; b++) { R.S2[e] = (a == b ? T2+D2[a] : T2)+(Q2[a]+Q2[b]); e++; }
+}
+
 // eval_distant_blocked: pnl_common.h
 // the evaluator of a work-list kernel: the branch-free power where it applies
 template <int DIM, int DPE, int KT, int CM>
@@ -885,6 +1019,16 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         PairAcc<DIM, DPE> R;
         R.clear();
         const int nq = __builtin_amdgcn_readfirstlane(s_ttn[q]), to = __builtin_amdgcn_readfirstlane(s_tto[q]);
+        // orders with the orbit structure (lists A, B and the other 6-point order of list C): the structured evaluators
+        if constexpr (DIM == 2 && DPE == 3 && !FH) {
+            if (q <= 4 && ((P.mix_struct >> q) & 1) && (nq == 3 || nq == 6)) {
+                const pnl_const_f64_ptr rule = (pnl_const_f64_ptr)(unsigned long long)(P.uni+P.uni_off[q]);
+                if (nq == 6) eval_struct6<KTE>(P.k, rule, s_tt+to*(4+DPE), av, bv, R, lpow);
+                else eval_struct3<KTE>(P.k, rule, av, bv, R, lpow);
+                if (act) accumulate(R, i, j);
+                continue;
+            }
+        }
         if (nq == NB) eval_distant_fixed<DIM, DPE, KTE, NB>(P, s_tt+to*(4+DPE), P.tt_wphi+to*DPE, av, bv, R, lpow);
         else if (nq == NA) eval_distant_fixed<DIM, DPE, KTE, NA>(P, s_tt+to*(4+DPE), P.tt_wphi+to*DPE, av, bv, R, lpow);
         else eval_distant_lds<DIM, DPE, KTE>(P, s_tt+to*(4+DPE), 4+DPE, nq, av, bv, R, lpow);
