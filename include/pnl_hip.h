@@ -108,6 +108,22 @@ enum pnl_counter {
  * name and falls back to the environment: the A/B switches named in DESIGN.md live there. */
 int pnl_set_option(const char *name, const char *value);
 
+/* Test hook (tests/test_device_math.py): the device functions of the kernel values and of the quadrature order, evaluated on
+ * the current device by the production code, one thread per input.  in / out are host arrays.
+ *   PNL_SELFTEST_LOG, _EXP, _EXP_RANGED   out[i] = pnl_log / pnl_exp / pnl_exp_ranged (in[i])
+ *   PNL_SELFTEST_KERNEL   out[i] = kern_scale<KT>(k) kern_eval<KT, BND>(k, d2 = in[i], power tables in LDS) for the pnl_kernel
+ *                         *param of dimension dim; boundary != 0: k is the folded boundary kernel of the boundary tiles and
+ *                         BND = true.  path: PNL_SELFTEST_DISPATCH (+ 1: INSIDE) the KT that kern_dispatch<KT0, INSIDE> picks, KT0 = 1
+ *                         for a fast kernel, else 0; any other value is the KT itself (0: exp(e ln d2) without tables, 1, 2, 3,
+ *                         13, 14, 15, 17); the kernel must suit that path (fast for 1, 2 and >= 10)
+ *   PNL_SELFTEST_SCALING  out[i] = pw_scaling<dim>(W, s = in[i], boundary), W from the pnl_order_function *param
+ *   PNL_SELFTEST_QORDER   in[4 i ..] = h1, h2, d2, H0 of a cell pair; out[3 i ..] = quad_order_exact, quad_order_try,
+ *                         quad_order_fast for the pnl_order_formula *param, ln h and |ln(h / H0)| staged like the tile kernels */
+enum { PNL_SELFTEST_LOG = 0, PNL_SELFTEST_EXP = 1, PNL_SELFTEST_EXP_RANGED = 2, PNL_SELFTEST_KERNEL = 3, PNL_SELFTEST_SCALING = 4,
+       PNL_SELFTEST_QORDER = 5 };
+#define PNL_SELFTEST_DISPATCH 100
+int pnl_selftest(int op, int path, int dim, int boundary, const void *param, int n, const double *in, double *out);
+
 /* ---- lifetime ---------------------------------------------------------------- */
 int pnl_create(int device_id, pnl_context **ctx);
 void pnl_destroy(pnl_context *ctx);

@@ -31,7 +31,7 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_inv_diagonal', 'pnl_set_classes', 'pnl_select_class', 'pnl_upload_sparsity', 'pnl_upload_sparsity_device', 'pnl_assemble_pairs_masked', 'pnl_assemble_boundary_masked', 'pnl_assemble_clusters_tiled', 'pnl_h2_setup', 'pnl_h2_matvec', 'pnl_h2_upward', 'pnl_h2_interact', 'pnl_h2_downward', 'pnl_h2_sizes', 'pnl_spmv',
            'pnl_assemble_pairs_in_horizon', 'pnl_assemble_pairs_in_horizon_range', 'pnl_set_nonsymmetric', 'pnl_set_order_function', 'pnl_upload_pointwise_rules', 'pnl_assemble_dense_pointwise',
            'pnl_assemble_pairs_masked_pointwise', 'pnl_assemble_boundary_masked_pointwise',
-           'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step']
+           'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest']
 
 
 def source_sha16():
@@ -119,6 +119,7 @@ def load():
     L.pnl_upload_mesh.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, dbl]
     L.pnl_upload_dofmap.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     L.pnl_set_kernel.argtypes = [vp, i32, C.POINTER(pnl_kernel)]
+    L.pnl_selftest.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp]
     L.pnl_set_order_formula.argtypes = [vp, i32, C.POINTER(pnl_order_formula)]
     L.pnl_upload_distant_rules.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.pnl_upload_singular_rule.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, dbl]
@@ -212,6 +213,25 @@ def set_option(name, value=None):
     rc = load().pnl_set_option(name.encode(), None if value is None else str(value).encode())
     if rc:
         raise PnlError('pnl_set_option({!r}) failed: {} (a product build accepts only the options listed in include/pnl_hip.h)'.format(name, rc))
+
+
+SELFTEST_LOG, SELFTEST_EXP, SELFTEST_EXP_RANGED, SELFTEST_KERNEL, SELFTEST_SCALING, SELFTEST_QORDER = range(6)
+SELFTEST_DISPATCH = 100
+
+
+def selftest(op, x, path=0, dim=1, boundary=False, param=None):
+    """pnl_selftest (include/pnl_hip.h): the production device function `op` on the current device, one thread per input.
+    x: [n] inputs (SELFTEST_QORDER: [n, 4] rows h1, h2, d2, H0 -> [n, 3] orders exact, try, fast); param: the pnl_kernel,
+    pnl_order_function or pnl_order_formula the op needs"""
+    L = load()
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    n = x.shape[0]
+    out = np.empty((n, 3) if op == SELFTEST_QORDER else n)
+    rc = L.pnl_selftest(int(op), int(path), int(dim), int(bool(boundary)), None if param is None else C.addressof(param), n,
+                        x.ctypes.data, out.ctypes.data)
+    if rc != PNL_OK:
+        raise PnlError('pnl_selftest(op={}, path={}) failed: {}'.format(op, path, rc))
+    return out
 
 
 def _hp(a, dtype):

@@ -89,9 +89,12 @@ __device__ __forceinline__ double pnl_log(double x) {
     return __builtin_fma(kd, 6.93147180369123816490e-01, __builtin_fma(kd, 1.90821492927058770002e-10, PNL_LOG_TAB[j][1]+p));
 }
 
-// exp y, |y| < 700: y = n ln 2 / 64 + r, |r| <= ln 2 / 128, exp y = 2^(n >> 6) 2^((n & 63)/64) exp r, exp r to r^5 (next 3e-17);
-// n = rint(y 64 / ln 2) from the low word of y 64 / ln 2 + 1.5 2^52, the power of two added to the exponent field (the result
-// is a normal number: kernel values, |y| < 700)
+// exp y for y in [-708, 709], relative error <= 1e-15 (tests/test_device_math.py): y = n ln 2 / 64 + r, |r| <= ln 2 / 128,
+// exp y = 2^(n >> 6) 2^((n & 63)/64) exp r, exp r to r^5 (next 3e-17); n = rint(y 64 / ln 2) from the low word of
+// y 64 / ln 2 + 1.5 2^52, the power of two added to the exponent field without a range check: outside that interval the result is
+// garbage (y = -720 gives -6.6e303).  Its callers are the fractional kernels exp(e ln d2) with -2 < e < 0 (general exponent, order
+// per quadrature point), inside for 1e-150 < d2 < 1e150 (|e ln d2| < 60 on any realistic mesh); the integrable kernels, whose
+// argument has no lower bound, take pnl_exp_ranged.
 __device__ __forceinline__ double pnl_exp(double y) {
     const double big = __builtin_fma(y, PNL_64_LN2, 6755399441055744.0);
     const int ni = __double2loint(big);
@@ -107,6 +110,10 @@ __device__ __forceinline__ double pnl_exp(double y) {
     const double v = p*PNL_EXP_TAB[ni & 63];
     return __hiloint2double(__double2hiint(v)+((ni >> 6) << 20), __double2loint(v));
 }
+// exp y for y <= 709 (the Gaussian and exponential kernels: y = -d2 / (2 variance^d) or -rate |x-y| <= 0, far below -708 for the far
+// pairs of a small variance or a large rate: variance 0.05 on the unit disc gives y = -800): 0 below -708 and for NaN.  The flushed
+// values are below 3.4e-308, i.e. kernel values below 1e-300 of the kernel's scale; one compare and one select more than pnl_exp.
+__device__ __forceinline__ double pnl_exp_ranged(double y) { return y >= -708. ? pnl_exp(y) : 0.; }
 
 // General power through tables in LDS (the tile kernels of a general exponent): x = 2^k m, m in [1, 2), j = top seven fraction
 // bits of m, u = m T[j] - 1 with T[j] = fl(1 / c_j) (one FMA, |u| <= 2^-8),
@@ -251,15 +258,15 @@ __device__ __forceinline__ double kern_eval(const DevKernel &k, double d2, const
         if (k.ktype == 0) return ltab ? pnl_pow_tab(d2, k, ltab) : k.scale*pnl_exp(k.exponent*pnl_log(d2));
         if (k.ktype == 1) return k.scale;
         if (k.ktype == 2) return k.scale/sqrt(d2);
-        if (k.ktype == 3) return k.scale*pnl_exp(k.exponent*d2);              // Gaussian: exponent = -1 / (2 variance^d) or -9 / horizon^2
-        if (k.ktype == 4 || !BND) return k.scale*pnl_exp(k.exponent*sqrt(d2));       // exponential: exponent = -rate
+        if (k.ktype == 3) return k.scale*pnl_exp_ranged(k.exponent*d2);       // Gaussian: exponent = -1 / (2 variance^d) or -9 / horizon^2
+        if (k.ktype == 4 || !BND) return k.scale*pnl_exp_ranged(k.exponent*sqrt(d2));       // exponential: exponent = -rate
         // Gauss-theorem twins of the integrable kernels on the full space (kernelsCy.pyx:418-477; gammainc(a, x) there is the
         // unnormalised upper incomplete Gamma function, :39-40): 5 Gaussian 1D, 6 exponential; 7 / 8 the 2D forms with the
         // 1 / |x-y| of the normal factor folded in (DevProblem::bkn)
         if (k.ktype == 5) return k.scale*sqrt(3.14159265358979323846/(-k.exponent))*pnl_erfc(sqrt(-k.exponent*d2));
-        if (k.ktype == 6) return 2.*k.scale*pnl_exp(k.exponent*sqrt(d2))/(-k.exponent);
-        if (k.ktype == 7) return k.scale*pnl_exp(k.exponent*d2)/(-k.exponent*d2);
-        return 2.*k.scale*pnl_exp(k.exponent*sqrt(d2))/(-k.exponent*sqrt(d2));
+        if (k.ktype == 6) return 2.*k.scale*pnl_exp_ranged(k.exponent*sqrt(d2))/(-k.exponent);
+        if (k.ktype == 7) return k.scale*pnl_exp_ranged(k.exponent*d2)/(-k.exponent*d2);
+        return 2.*k.scale*pnl_exp_ranged(k.exponent*sqrt(d2))/(-k.exponent*sqrt(d2));
     }
 }
 

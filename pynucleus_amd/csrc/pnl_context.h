@@ -218,6 +218,32 @@ inline DevKernel to_dev(const pnl_kernel &k, int dim) {
     return d;
 }
 
+// the boundary kernel as the boundary tiles evaluate it (DevProblem::bkn): in 2D the 1/|x-y| of the normal factor n.(y-x)/|y-x|
+// folded into the exponent of a fractional kernel, the folded 2D forms 7 / 8 of the Gauss-theorem twins (kern_eval, pnl_common.h)
+inline DevKernel to_dev_bkn(pnl_kernel kn, int dim) {
+    if (dim == 2 && kn.ktype == PNL_FRACTIONAL) kn.exponent -= 0.5;
+    DevKernel d = to_dev(kn, dim);
+    if (dim == 2 && kn.ktype != PNL_FRACTIONAL) d.fast = 0;
+    if (dim == 2 && kn.ktype == PNL_GAUSSIAN_BOUNDARY) d.ktype = 7;
+    if (dim == 2 && kn.ktype == PNL_EXPONENTIAL_BOUNDARY) d.ktype = 8;
+    return d;
+}
+
+// values of the pnl_pow_tab tables of k (PNL_POW_TAB_DOUBLES doubles, scale folded in; pnl_hip.hip); false where the kernel
+// has none (not fractional, or fast without also_fast, or the option PNL_NO_POWTAB)
+bool pow_table_values(const DevKernel &k, bool also_fast, std::vector<double> &tab);
+
+// the order function's part of PwDev (the rest is per mesh: pnl_set_order_function); false: a bad Chebyshev series of the scaling
+inline bool pw_set_function(PwDev &W, const pnl_order_function &f) {
+    std::memset(&W, 0, sizeof(W));
+    W.type = f.type; W.normalized = f.normalized;
+    for (int i = 0; i < 6; i++) W.p[i] = f.p[i];
+    if (f.scal_n < 0 || f.scal_n > 32 || (f.scal_n > 0 && !(f.scal_half > 0.))) return false;
+    W.scal_n = f.scal_n; W.scal_mid = f.scal_mid; W.scal_inv_half = f.scal_n > 0 ? 1./f.scal_half : 0.;
+    for (int i = 0; i < 32; i++) W.scal_cheb[i] = i < f.scal_n ? f.scal_cheb[i] : 0.;
+    return true;
+}
+
 inline DevFormula to_dev(const pnl_order_formula &f) {
     DevFormula d;
     d.c0 = f.c0; d.a = f.a; d.b = f.b; d.e = f.e; d.den0 = f.den0; d.clip = f.clip_num; d.pad = 0;

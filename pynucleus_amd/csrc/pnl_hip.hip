@@ -467,15 +467,16 @@ int finalize(pnl_context *ctx) {
     return PNL_OK;
 }
 
+}  // namespace
+
 // Tables of pnl_pow_tab for x^exponent * scale (long double on the host, rounded once):  x = 2^k m, m in [1, 2), j = top seven
 // fraction bits of m, c_j = 1 / fl(1 / (1 + (j + 1/2) / 128)), u = m fl(1/c_j) - 1 (one FMA, |u| <= 2^-8):
 //   x^e = 2^(e k) c_j^e (1 + u)^e.
 // also_fast: tables for an exponent -qm/4 as well -- a launch over the tiles of SEVERAL order classes runs the KT == 0 kernels for
 // all of them, and a class without tables falls into the general branch there (exp(e ln x) behind the per-lane horizon test)
-static const double *pow_table(pnl_context *ctx, const DevKernel &k, bool also_fast = false) {
-    if (k.ktype != PNL_FRACTIONAL || (k.fast && !also_fast) || pnl_tune("PNL_NO_POWTAB")) return nullptr;
-    for (auto *t : ctx->powtabs) if (t->exponent == k.exponent && t->scale == k.scale) return (const double*)t->buf.p;
-    std::vector<double> tab(PNL_POW_TAB_DOUBLES);
+bool pow_table_values(const DevKernel &k, bool also_fast, std::vector<double> &tab) {
+    if (k.ktype != PNL_FRACTIONAL || (k.fast && !also_fast) || pnl_tune("PNL_NO_POWTAB")) return false;
+    tab.assign(PNL_POW_TAB_DOUBLES, 0.);
     for (int j = 0; j < 128; j++) {
         const double invc = (double)(1.L/(1.L+((long double)j+0.5L)/128.L));
         const long double c = 1.L/(long double)invc;
@@ -483,6 +484,15 @@ static const double *pow_table(pnl_context *ctx, const DevKernel &k, bool also_f
         tab[128+j] = (double)((long double)k.scale*powl(c, (long double)k.exponent));
         tab[256+j] = (double)exp2l((long double)k.exponent*(long double)(j-96));
     }
+    return true;
+}
+namespace {
+
+static const double *pow_table(pnl_context *ctx, const DevKernel &k, bool also_fast = false) {
+    if (k.ktype != PNL_FRACTIONAL || (k.fast && !also_fast) || pnl_tune("PNL_NO_POWTAB")) return nullptr;
+    for (auto *t : ctx->powtabs) if (t->exponent == k.exponent && t->scale == k.scale) return (const double*)t->buf.p;
+    std::vector<double> tab;
+    if (!pow_table_values(k, also_fast, tab)) return nullptr;
     auto *t = new pnl_context::PowTab;
     t->exponent = k.exponent; t->scale = k.scale;
     if (upload(ctx, t->buf, tab.data(), tab.size()) != PNL_OK) { delete t; return nullptr; }
@@ -494,15 +504,7 @@ void refresh_tables(pnl_context *ctx) {
     DevProblem &P = ctx->P;
     P.k = to_dev(ctx->C().kern[0], ctx->dim);
     P.bk = to_dev(ctx->C().kern[1], ctx->dim);
-    {
-        // n.(y-x)/|y-x| * Gamma_b(|x-y|^2): fold the normalisation into the exponent (fractional kernels only)
-        pnl_kernel kn = ctx->C().kern[1];
-        if (ctx->dim == 2 && kn.ktype == PNL_FRACTIONAL) kn.exponent -= 0.5;
-        P.bkn = to_dev(kn, ctx->dim);
-        if (ctx->dim == 2 && kn.ktype != PNL_FRACTIONAL) P.bkn.fast = 0;
-        if (ctx->dim == 2 && kn.ktype == PNL_GAUSSIAN_BOUNDARY) P.bkn.ktype = 7;        // kern_eval (pnl_common.h): folded 2D forms
-        if (ctx->dim == 2 && kn.ktype == PNL_EXPONENTIAL_BOUNDARY) P.bkn.ktype = 8;
-    }
+    P.bkn = to_dev_bkn(ctx->C().kern[1], ctx->dim);     // n.(y-x)/|y-x| * Gamma_b(|x-y|^2), the normalisation folded in
     P.qo = to_dev(ctx->C().form[0]);
     P.bqo = to_dev(ctx->C().form[1]);
     P.qmax = ctx->qmax;
@@ -3218,12 +3220,7 @@ int pnl_set_order_function(pnl_context *ctx, const pnl_order_function *f, const 
     if (f->type < 1 || f->type > 5) return fail(ctx, PNL_ERR_UNSUPPORTED, "order function type %d is not implemented", f->type);
     if (ctx->have_dofs && !(ctx->dpe == ctx->dim+1 || (ctx->dim == 2 && ctx->dpe == 6) || (ctx->dim == 1 && ctx->dpe == 3)))
         return fail(ctx, PNL_ERR_UNSUPPORTED, "pointwise variable orders: P1 and P2 elements");
-    std::memset(&ctx->pw, 0, sizeof(ctx->pw));
-    ctx->pw.type = f->type; ctx->pw.normalized = f->normalized;
-    for (int i = 0; i < 6; i++) ctx->pw.p[i] = f->p[i];
-    if (f->scal_n < 0 || f->scal_n > 32 || (f->scal_n > 0 && !(f->scal_half > 0.))) return fail(ctx, PNL_ERR_INVALID, "bad Chebyshev series of the scaling");
-    ctx->pw.scal_n = f->scal_n; ctx->pw.scal_mid = f->scal_mid; ctx->pw.scal_inv_half = f->scal_n > 0 ? 1./f->scal_half : 0.;
-    for (int i = 0; i < 32; i++) ctx->pw.scal_cheb[i] = i < f->scal_n ? f->scal_cheb[i] : 0.;
+    if (!pw_set_function(ctx->pw, *f)) return fail(ctx, PNL_ERR_INVALID, "bad Chebyshev series of the scaling");
     ctx->pw.c0 = c0; ctx->pw.bc0 = bc0; ctx->pw.sfac = sing_fac; ctx->pw.bfac = bsing_fac;
     ctx->pw_cell_smax.assign(cell_smax, cell_smax+ctx->nc);
     ctx->pw_facet_smax.clear();
