@@ -534,6 +534,21 @@ int pnl_theta_step(pnl_mg *mg, const double *S_dev, int64_t ldS, const int32_t *
 /* 1/diag(A) into dinv_dev (jacobi_solver.setup, solvers.pyx:233-237) */
 int pnl_inv_diagonal(pnl_context *ctx, const double *A_dev, int64_t ldA, int n, double *dinv_dev);
 
+/* ---- direct solver for the dense symmetric positive definite operators (csrc/pnl_chol.hip): what lu_solver.setup / solve
+ *      (base/PyNucleus_base/solvers.pyx:80-186: dense copy, getrf, getrs) is for `--matrixFormat dense --solver lu`.  The operators
+ *      of the symmetric kernels are positive definite, so the factor is Cholesky; there is no LU with pivoting. ----------------
+ * replaces lu_solver.setup (solvers.pyx:80-186): A = L L^T in place on the lower triangle of the row-major n x n block A_dev
+ * (leading dimension ldA >= n).  Reads A[i][j] for j <= i only and leaves L there, L[i][i] > 0; nothing above the diagonal and
+ * nothing in the padding columns n .. ldA - 1 is read or written.  *info = 0 on success; *info = k > 0 if the leading minor of
+ * order k is not positive definite (pivot k is not > 0, NaN included): the call still returns PNL_OK, the lower triangle is then
+ * unspecified and everything else untouched.  PNL_ERR_INVALID for n < 0, ldA < n or a null pointer with n > 0; n = 0 is a no-op.
+ * Runs on the context's stream and synchronises it to return info (the pivot check costs no synchronisation per panel). */
+int pnl_potrf(pnl_context *ctx, double *A_dev, int64_t ldA, int n, int *info);
+/* replaces lu_solver.solve (solvers.pyx:80-186): L y = b, then L^T x = y, in place on the nrhs >= 1 right-hand sides
+ * B_dev[r * ldb .. r * ldb + n), ldb >= n, with the factor pnl_potrf left in the lower triangle of L_dev (only that triangle is
+ * read).  Asynchronous on the context's stream. */
+int pnl_potrs(pnl_context *ctx, const double *L_dev, int64_t ldL, int n, double *B_dev, int64_t ldb, int nrhs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,8 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_inv_diagonal', 'pnl_set_classes', 'pnl_select_class', 'pnl_upload_sparsity', 'pnl_upload_sparsity_device', 'pnl_assemble_pairs_masked', 'pnl_assemble_boundary_masked', 'pnl_assemble_clusters_tiled', 'pnl_h2_setup', 'pnl_h2_matvec', 'pnl_h2_upward', 'pnl_h2_interact', 'pnl_h2_downward', 'pnl_h2_sizes', 'pnl_spmv',
            'pnl_assemble_pairs_in_horizon', 'pnl_assemble_pairs_in_horizon_range', 'pnl_set_nonsymmetric', 'pnl_set_order_function', 'pnl_upload_pointwise_rules', 'pnl_assemble_dense_pointwise',
            'pnl_assemble_pairs_masked_pointwise', 'pnl_assemble_boundary_masked_pointwise',
-           'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest']
+           'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest',
+           'pnl_potrf', 'pnl_potrs']
 
 
 def source_sha16():
@@ -176,6 +177,8 @@ def load():
     L.pnl_mg_solve.argtypes = [vp, vp, vp, dbl, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_double), i32]
     L.pnl_mg_cg.argtypes = [vp, vp, i64, vp, vp, dbl, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_double), i32]
     L.pnl_theta_step.argtypes = [vp, vp, i64, vp, vp, vp, dbl, dbl, vp, vp, dbl, i32, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.pnl_potrf.argtypes = [vp, vp, i64, i32, C.POINTER(C.c_int)]
+    L.pnl_potrs.argtypes = [vp, vp, i64, i32, vp, i64, i32]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
     L.pnl_upload_sparsity_device.argtypes = [vp, i32, vp, vp]
     L.pnl_set_classes.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -613,6 +616,18 @@ class Context:
                                          C.c_void_p(M_data_ptr), float(dt), float(theta), C.c_void_p(forcing_ptr) if forcing_ptr else None,
                                          C.c_void_p(u_ptr), float(tol), int(maxiter), C.byref(it), C.byref(res)))
         return it.value, res.value
+
+    # -- direct solver (pnl_chol.hip) --------------------------------------------------------------
+    def potrf(self, A_ptr, ldA, n):
+        """Cholesky factor in place on the lower triangle; returns info (0, or the order of the first minor that is not positive
+        definite)"""
+        info = C.c_int(0)
+        self.check(self.L.pnl_potrf(self.h, C.c_void_p(A_ptr) if A_ptr else None, int(ldA), int(n), C.byref(info)))
+        return info.value
+
+    def potrs(self, L_ptr, ldL, n, B_ptr, ldb, nrhs):
+        self.check(self.L.pnl_potrs(self.h, C.c_void_p(L_ptr) if L_ptr else None, int(ldL), int(n), C.c_void_p(B_ptr) if B_ptr else None,
+                                    int(ldb), int(nrhs)))
 
     def inv_diagonal(self, A_ptr, ldA, n, out_ptr):
         self.check(self.L.pnl_inv_diagonal(self.h, C.c_void_p(A_ptr), int(ldA), int(n), C.c_void_p(out_ptr)))

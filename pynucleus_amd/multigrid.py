@@ -456,22 +456,40 @@ class CrankNicolson:
     """Theta method for M u_t + S u = g(t) on the finest level of a hierarchy with mass matrices (timestepping.py:64-112):
     (M/dt + theta S) u_{k+1} = (M/dt) u_k - (1 - theta) S u_k + (1 - theta) g(t_k) + theta g(t_{k+1}).
     The system is solved by multigrid-preconditioned CG on the transient hierarchy alpha M + beta A
-    (buildTransientSolver, discretizedProblems.py:751-768) inside pnl_theta_step."""
+    (buildTransientSolver, discretizedProblems.py:751-768) inside pnl_theta_step (solver='cg-mg', the default), or directly
+    (solver='chol'): M/dt + theta S of the finest level is factored once (solvers.chol) and every step is the right-hand side
+    (pnl_csr_matvec, pnl_gemv_axpby) and two triangular sweeps (pnl_potrs); ``iterations`` then records 0 per step."""
 
-    def __init__(self, hierarchy, dt, theta=0.5, tol=1e-8, maxiter=100, smoother=('jacobi', {'omega': 2.0/3.0})):
+    def __init__(self, hierarchy, dt, theta=0.5, tol=1e-8, maxiter=100, smoother=('jacobi', {'omega': 2.0/3.0}), solver='cg-mg'):
         assert 0. <= theta <= 1. and dt > 0.
+        if solver not in ('cg-mg', 'chol'):
+            raise NotImplementedError('solver {!r}: cg-mg and chol are built'.format(solver))
         levels = hierarchy.getLevelList() if hasattr(hierarchy, 'getLevelList') else list(hierarchy)
         self.dt, self.theta, self.tol, self.maxiter = float(dt), float(theta), tol, maxiter
+        self.solverType = solver
         self.S = levels[-1]['A']
+        self.iterations = []
+        if solver == 'chol':
+            from .linear_operators import Dense_LinearOperator
+            if not isinstance(self.S, Dense_LinearOperator) or not self.S.symmetric:
+                raise NotImplementedError('solver=\'chol\' needs a symmetric dense operator on the finest level; got {!r}'.format(self.S))
+            levels = levels[-1:]                               # the direct solver needs the finest level alone
         self.device = self.S.A.device
         self.M = _DevCSR(levels[-1]['M'], self.device)
         self.transient = buildTransientHierarchy(levels, 1./self.dt, self.theta)
-        self.solver = multigrid(self.transient, smoother=smoother)
-        if not getattr(self.solver, '_native', False):
-            # pnl_theta_step drives the library's own V cycle: dense levels and the Jacobi smoother
-            raise NotImplementedError('time stepping needs the library multigrid (dense levels, Jacobi smoother); '
-                                      'got smoother={!r} / a level that is not dense'.format(smoother))
-        self.iterations = []
+        if solver == 'chol':
+            # M/dt + theta S formed in HBM and factored once, in its own storage (lu_solver, solvers.pyx:80-186)
+            from .solvers import chol
+            T = self.transient[-1]['A']
+            T.symmetric = True
+            self.ctx = self.S.ctx
+            self.solver = self.factor = chol(T, overwrite=True)
+        else:
+            self.solver = multigrid(self.transient, smoother=smoother)
+            if not getattr(self.solver, '_native', False):
+                # pnl_theta_step drives the library's own V cycle: dense levels and the Jacobi smoother
+                raise NotImplementedError('time stepping needs the library multigrid (dense levels, Jacobi smoother); '
+                                          'got smoother={!r} / a level that is not dense'.format(smoother))
 
     def setRHS(self, g_t, g_tdt):
         """forcing of one step from the load vectors at t and t + dt (setRHS, timestepping.py:76-91)"""
@@ -480,6 +498,8 @@ class CrankNicolson:
     def step(self, t, u, forcing):
         """advance u (a device vector, overwritten) from t to t + dt; returns t + dt"""
         import torch
+        if self.solverType == 'chol':
+            return self._step_chol(t, u, forcing)
         mg = self.solver
         f = mg._vec(forcing)
         assert isinstance(u, torch.Tensor) and u.device == self.device and u.dtype == torch.float64 and u.is_contiguous()
@@ -487,6 +507,26 @@ class CrankNicolson:
         its, res = mg.ctx.theta_step(mg._mg, self.S.A.data_ptr(), self.S.A.stride(0), self.M.indptr.data_ptr(), self.M.indices.data_ptr(),
                                      self.M.data.data_ptr(), self.dt, self.theta, f.data_ptr(), u.data_ptr(), self.tol, self.maxiter)
         self.iterations.append(its)
+        return t+self.dt
+
+    def _step_chol(self, t, u, forcing):
+        """rhs = forcing + (M/dt) u - (1 - theta) S u as in pnl_theta_step, then the two triangular sweeps"""
+        import torch
+        assert isinstance(u, torch.Tensor) and u.device == self.device and u.dtype == torch.float64 and u.is_contiguous()
+        if isinstance(forcing, torch.Tensor):
+            rhs = forcing.to(device=self.device, dtype=torch.float64).contiguous().clone()
+        else:
+            rhs = torch.from_numpy(np.ascontiguousarray(np.asarray(forcing, dtype=np.float64))).to(self.device)
+        ctx, n = self.ctx, self.S.num_rows
+        ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        ctx.csr_matvec(n, self.M.indptr.data_ptr(), self.M.indices.data_ptr(), self.M.data.data_ptr(), u.data_ptr(), 1./self.dt, 1., rhs.data_ptr())
+        if self.theta < 1.:
+            ctx.gemv_axpby(self.S.A.data_ptr(), self.S.A.stride(0), n, n, u.data_ptr(), -(1.-self.theta), 1., rhs.data_ptr(), rhs.data_ptr())
+        Ld = self.factor._L
+        ctx.potrs(Ld.data_ptr(), Ld.stride(0) if n > 1 else Ld.shape[1], n, rhs.data_ptr(), n, 1)
+        ctx.synchronize()
+        u.copy_(rhs)
+        self.iterations.append(0)
         return t+self.dt
 
 
@@ -502,7 +542,8 @@ def determineTimeSteps(h, finalTime, timeStepperType='Crank-Nicolson'):
     return finalTime/n, n
 
 
-def solveFractionalHeat(hierarchy, initial, load, finalTime=1.0, timeStepperType='Crank-Nicolson', theta=0.5, tol=1e-8, maxiter=100):
+def solveFractionalHeat(hierarchy, initial, load, finalTime=1.0, timeStepperType='Crank-Nicolson', theta=0.5, tol=1e-8, maxiter=100,
+                        solver='cg-mg'):
     """discretizedTransientProblem.solve (discretizedProblems.py:889-905): u_t + (-Laplace)^s u = f on the finest level,
     u(0) = interpolant of ``initial``; ``load(t)`` returns the load vector int f(t) phi_i.  Returns (times, [u_k] on the host,
     stepper)."""
@@ -510,8 +551,8 @@ def solveFractionalHeat(hierarchy, initial, load, finalTime=1.0, timeStepperType
     L = hierarchy.finest if hasattr(hierarchy, 'finest') else hierarchy[-1]
     dm = L['DoFMap']
     dt, nt = determineTimeSteps(dm.mesh.h, finalTime, timeStepperType)
-    stepper = (CrankNicolson(hierarchy, dt, theta=theta, tol=tol, maxiter=maxiter) if timeStepperType == 'Crank-Nicolson'
-               else ImplicitEuler(hierarchy, dt, tol=tol, maxiter=maxiter))
+    stepper = (CrankNicolson(hierarchy, dt, theta=theta, tol=tol, maxiter=maxiter, solver=solver) if timeStepperType == 'Crank-Nicolson'
+               else ImplicitEuler(hierarchy, dt, tol=tol, maxiter=maxiter, solver=solver))
     times = np.linspace(0., finalTime, nt+1)
     u0 = np.asarray(dm.interpolate(initial), dtype=np.float64)
     u = torch.from_numpy(u0.copy()).to(stepper.device)

@@ -7,7 +7,9 @@ x, r, (refresh), Br, beta, p.  ``jacobi`` = the reference's jacobi_solver as a p
 The dense operator additionally has this loop as one library call (pnl_cg_jacobi, Dense_LinearOperator.solve_cg_jacobi).
 ``gmres`` follows gmres_solver.solve (solvers.pyx:504-659; the drivers' gmres-jacobi / gmres-mg for non-symmetric orders):
 left (default) or right preconditioner, modified Gram-Schmidt, Givens rotations, the rotated right-hand side as residual
-estimate, restarts; the Krylov basis stays in HBM, the small Hessenberg problem lives on the host."""
+estimate, restarts; the Krylov basis stays in HBM, the small Hessenberg problem lives on the host.
+``chol`` / ``lu`` are the direct solver of the symmetric dense operators (lu_solver, solvers.pyx:80-186): the Cholesky factor is
+computed once in HBM (pnl_potrf), every solve is two triangular sweeps (pnl_potrs)."""
 import numpy as np
 
 
@@ -211,3 +213,86 @@ def bicgstab(A, b, x0=None, tol=1e-8, maxiter=50, preconditioner=None):
     if isinstance(b, torch.Tensor):
         return x, its, residuals
     return x.cpu().numpy(), its, residuals
+
+
+class CholeskyFactor:
+    """A = L L^T of a symmetric positive definite dense operator, L in the lower triangle of a device block (the strict upper
+    triangle holds whatever the operator had there and is never read).  ``solve(b)`` = lu_solver.solve (solvers.pyx:80-186);
+    calling the object applies A^-1 to a device vector, so it can be the ``preconditioner=`` of cg / gmres / bicgstab."""
+
+    def __init__(self, L_dev, ctx):
+        self._L = L_dev
+        self.ctx = ctx
+        self.device = L_dev.device
+        self.num_rows = self.num_columns = int(L_dev.shape[0])
+        self.shape = (self.num_rows, self.num_columns)
+
+    @property
+    def L(self):
+        """the factor as a lower-triangular numpy array (a copy; tests)"""
+        self.ctx.synchronize()
+        return np.tril(self._L.cpu().numpy())
+
+    def _solve_dev(self, X):
+        """in place on the rows of the contiguous device block X [nrhs, n]"""
+        import torch
+        torch.cuda.current_stream(self.device).synchronize()
+        self.ctx.potrs(self._L.data_ptr(), self._L.stride(0) if self.num_rows > 1 else self._L.shape[1], self.num_rows, X.data_ptr(),
+                       X.stride(0) if X.shape[0] > 1 else max(X.shape[1], 1), X.shape[0])
+        self.ctx.synchronize()
+        return X
+
+    def solve(self, b):
+        """x with A x = b for a vector, or row by row for a 2-D array of right-hand sides; torch in, torch out, else numpy"""
+        import torch
+        X = _dev_vector(b, self.device)
+        if X.ndim not in (1, 2) or X.shape[-1] != self.num_rows:
+            raise AssertionError('right-hand side of shape {} for an operator with {} rows'.format(tuple(X.shape), self.num_rows))
+        shape = tuple(X.shape)
+        X = X.reshape(-1, self.num_rows).contiguous().clone()
+        self._solve_dev(X)
+        X = X.reshape(shape)
+        return X if isinstance(b, torch.Tensor) else X.cpu().numpy()
+
+    def __call__(self, r):
+        return self.solve(r)
+
+    def __repr__(self):
+        return '<Cholesky factor of a {}x{} dense operator on {}>'.format(self.num_rows, self.num_columns, self.device)
+
+
+def chol(A, overwrite=False):
+    """Cholesky factorisation of a symmetric dense operator on its device (pnl_potrf).  Without ``overwrite`` a device copy of the
+    block is factored; with it the operator's own storage becomes the factor (its lower triangle; the operator is invalidated and
+    must not be applied any more).  Raises numpy.linalg.LinAlgError if a leading minor is not positive definite."""
+    import torch
+    from .linear_operators import Dense_LinearOperator
+    if not isinstance(A, Dense_LinearOperator) or not A.symmetric:
+        raise NotImplementedError('chol: a symmetric Dense_LinearOperator is needed (direct solves of H2, sparse, distributed or '
+                                  'non-symmetric operators are not built); got {!r}'.format(A))
+    A.ctx.synchronize()
+    torch.cuda.current_stream(A.A.device).synchronize()
+    if overwrite:
+        Ld = A.A
+    else:
+        try:
+            Ld = A.A.clone(memory_format=torch.contiguous_format)
+        except torch.cuda.OutOfMemoryError as e:
+            raise MemoryError('chol: no room in HBM for a copy of the {} x {} operator ({:.1f} GB); '
+                              'chol(A, overwrite=True) factors it in place'.format(A.num_rows, A.num_columns,
+                                                                                   8e-9*A.num_rows*A.A.stride(0))) from e
+        torch.cuda.current_stream(A.A.device).synchronize()
+    n = A.num_rows
+    info = A.ctx.potrf(Ld.data_ptr(), Ld.stride(0) if n > 1 else Ld.shape[1], n)
+    if overwrite:
+        A.invalidate()
+    if info > 0:
+        raise np.linalg.LinAlgError('chol: the leading minor of order {} is not positive definite'.format(info))
+    return CholeskyFactor(Ld, A.ctx)
+
+
+def lu(A):
+    """the reference's name (lu_solver): for a symmetric dense operator the Cholesky factor"""
+    if not getattr(A, 'symmetric', False):
+        raise NotImplementedError('LU with pivoting')
+    return chol(A)
