@@ -536,7 +536,7 @@ int pnl_inv_diagonal(pnl_context *ctx, const double *A_dev, int64_t ldA, int n, 
 
 /* ---- direct solver for the dense symmetric positive definite operators (csrc/pnl_chol.hip): what lu_solver.setup / solve
  *      (base/PyNucleus_base/solvers.pyx:80-186: dense copy, getrf, getrs) is for `--matrixFormat dense --solver lu`.  The operators
- *      of the symmetric kernels are positive definite, so the factor is Cholesky; there is no LU with pivoting. ----------------
+ *      of the symmetric kernels are positive definite, so the factor is Cholesky; pnl_getrf / pnl_getrs below are the LU. -------
  * replaces lu_solver.setup (solvers.pyx:80-186): A = L L^T in place on the lower triangle of the row-major n x n block A_dev
  * (leading dimension ldA >= n).  Reads A[i][j] for j <= i only and leaves L there, L[i][i] > 0; nothing above the diagonal and
  * nothing in the padding columns n .. ldA - 1 is read or written.  *info = 0 on success; *info = k > 0 if the leading minor of
@@ -548,6 +548,23 @@ int pnl_potrf(pnl_context *ctx, double *A_dev, int64_t ldA, int n, int *info);
  * B_dev[r * ldb .. r * ldb + n), ldb >= n, with the factor pnl_potrf left in the lower triangle of L_dev (only that triangle is
  * read).  Asynchronous on the context's stream. */
 int pnl_potrs(pnl_context *ctx, const double *L_dev, int64_t ldL, int n, double *B_dev, int64_t ldb, int nrhs);
+
+/* ---- direct solver for the dense operators that are not symmetric (csrc/pnl_lu.hip): lu_solver.setup / solve as they stand, getrf
+ *      and getrs, for the orders evaluated per quadrature point. ------------------------------------------------------------------
+ * replaces lu_solver.setup: P A = L U with partial pivoting in place on the row-major n x n block A_dev (leading dimension
+ * ldA >= n).  The strict lower triangle receives L (unit diagonal, not stored, every |l_ik| <= 1), the upper triangle with the
+ * diagonal U.  piv_dev[k], k < n, is 0-based with k <= piv_dev[k] < n: LAPACK's swap sequence (at step k the rows k and piv_dev[k] of
+ * the whole matrix were exchanged).  The pivot of column k is the entry of largest magnitude among the rows k .. n - 1 as they stand
+ * at that step, the lowest row among equal magnitudes; the search is a deterministic reduction, so the same input gives the same
+ * bits and the same piv_dev.  *info = 0, or the 1-based index of the first column whose pivot p does not satisfy |p| > 0 (NaN
+ * included): the call still returns PNL_OK and the block is then unspecified.  The padding columns n .. ldA - 1 are neither read
+ * nor written.  PNL_ERR_INVALID for n < 0, ldA < n or a null pointer with n > 0; n = 0 is a no-op.  Runs on the context's stream
+ * and synchronises it to return info. */
+int pnl_getrf(pnl_context *ctx, double *A_dev, int64_t ldA, int n, int32_t *piv_dev, int *info);
+/* replaces lu_solver.solve: the swaps applied to b, L y = P b (unit diagonal, no division), U x = y, in place on the nrhs >= 1
+ * right-hand sides B_dev[r * ldb .. r * ldb + n), ldb >= n, with the factors and the swap sequence pnl_getrf left.  A block of
+ * right-hand sides gives the bits of the one-by-one solves.  Asynchronous on the context's stream. */
+int pnl_getrs(pnl_context *ctx, const double *LU_dev, int64_t ldLU, int n, const int32_t *piv_dev, double *B_dev, int64_t ldb, int nrhs);
 
 #ifdef __cplusplus
 }

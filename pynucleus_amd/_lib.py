@@ -32,7 +32,7 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_assemble_pairs_in_horizon', 'pnl_assemble_pairs_in_horizon_range', 'pnl_set_nonsymmetric', 'pnl_set_order_function', 'pnl_upload_pointwise_rules', 'pnl_assemble_dense_pointwise',
            'pnl_assemble_pairs_masked_pointwise', 'pnl_assemble_boundary_masked_pointwise',
            'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest',
-           'pnl_potrf', 'pnl_potrs']
+           'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs']
 
 
 def source_sha16():
@@ -179,6 +179,8 @@ def load():
     L.pnl_theta_step.argtypes = [vp, vp, i64, vp, vp, vp, dbl, dbl, vp, vp, dbl, i32, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.pnl_potrf.argtypes = [vp, vp, i64, i32, C.POINTER(C.c_int)]
     L.pnl_potrs.argtypes = [vp, vp, i64, i32, vp, i64, i32]
+    L.pnl_getrf.argtypes = [vp, vp, i64, i32, vp, C.POINTER(C.c_int)]
+    L.pnl_getrs.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
     L.pnl_upload_sparsity_device.argtypes = [vp, i32, vp, vp]
     L.pnl_set_classes.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -628,6 +630,19 @@ class Context:
     def potrs(self, L_ptr, ldL, n, B_ptr, ldb, nrhs):
         self.check(self.L.pnl_potrs(self.h, C.c_void_p(L_ptr) if L_ptr else None, int(ldL), int(n), C.c_void_p(B_ptr) if B_ptr else None,
                                     int(ldb), int(nrhs)))
+
+    # -- direct solver with pivoting (pnl_lu.hip) ---------------------------------------------------
+    def getrf(self, A_ptr, ldA, n, piv_ptr):
+        """P A = L U in place, the swap sequence (int32, 0-based) into piv_ptr; returns info (0, or the 1-based column of the first
+        pivot that is zero or NaN)"""
+        info = C.c_int(0)
+        self.check(self.L.pnl_getrf(self.h, C.c_void_p(A_ptr) if A_ptr else None, int(ldA), int(n), C.c_void_p(piv_ptr) if piv_ptr else None,
+                                    C.byref(info)))
+        return info.value
+
+    def getrs(self, LU_ptr, ldLU, n, piv_ptr, B_ptr, ldb, nrhs):
+        self.check(self.L.pnl_getrs(self.h, C.c_void_p(LU_ptr) if LU_ptr else None, int(ldLU), int(n), C.c_void_p(piv_ptr) if piv_ptr else None,
+                                    C.c_void_p(B_ptr) if B_ptr else None, int(ldb), int(nrhs)))
 
     def inv_diagonal(self, A_ptr, ldA, n, out_ptr):
         self.check(self.L.pnl_inv_diagonal(self.h, C.c_void_p(A_ptr), int(ldA), int(n), C.c_void_p(out_ptr)))

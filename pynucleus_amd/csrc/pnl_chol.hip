@@ -3,7 +3,7 @@
 //
 // Reference: lu_solver.setup / solve (base/PyNucleus_base/solvers.pyx:80-186: the operator to a dense array, LAPACK getrf, then
 // getrs per right-hand side), the solver behind `--matrixFormat dense --solver lu`.  The operators of the symmetric kernels are
-// positive definite, so the factor here is Cholesky; LU with pivoting for the non-symmetric orders is not built.
+// positive definite, so the factor here is Cholesky; LU with pivoting for the non-symmetric orders is pnl_lu.hip.
 //
 // Storage: row-major A[n][ld], ld >= n, fp64, 64-bit offsets.  Only A[i][j] with j <= i < n is read or written, nothing above the
 // diagonal and nothing in the padding columns.

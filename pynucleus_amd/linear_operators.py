@@ -28,7 +28,7 @@ class Dense_LinearOperator:
         # a symmetric operator is applied from its upper triangle alone (4 N^2 bytes per product instead of 8 N^2); set by the builder
         # for symmetric kernels only -- the block itself always holds the full matrix, like the reference's
         self.symmetric = bool(symmetric) and self.num_rows == self.num_columns
-        self._chol = None              # Cholesky factor of solve_direct (a second n^2 block in HBM), dropped by invalidate()
+        self._chol = None              # Cholesky / LU factor of solve_direct (a second n^2 block in HBM), dropped by invalidate()
 
     # reference API -------------------------------------------------------
     @property
@@ -100,15 +100,16 @@ class Dense_LinearOperator:
         return xd.cpu().numpy(), its, res
 
     def solve_direct(self, b):
-        """x with A x = b through the Cholesky factor (solvers.chol) of a device copy of the block, computed on the first call and
-        kept until invalidate() / refresh() or until the context assembles again (Context.assembly_epoch, as for ``data``)"""
+        """x with A x = b through the Cholesky factor (solvers.chol; a symmetric operator) or the pivoted LU factors (solvers.plu; any
+        other square one) of a device copy of the block, computed on the first call and kept until invalidate() / refresh() or until
+        the context assembles again (Context.assembly_epoch, as for ``data``)"""
         epoch = getattr(self.ctx, 'assembly_epoch', 0)
         if self._chol is not None and self._chol_epoch != epoch:
             self._chol = None
         if self._chol is None:
             self._chol_epoch = epoch
-            from .solvers import chol
-            self._chol = chol(self)
+            from .solvers import chol, plu
+            self._chol = chol(self) if self.symmetric else plu(self)
         return self._chol.solve(b)
 
     # operator files: the reference's layout (DenseLinearOperator_{SCALAR}.pxi:86-94) on any h5py-like group (create_dataset,

@@ -458,12 +458,13 @@ class CrankNicolson:
     The system is solved by multigrid-preconditioned CG on the transient hierarchy alpha M + beta A
     (buildTransientSolver, discretizedProblems.py:751-768) inside pnl_theta_step (solver='cg-mg', the default), or directly
     (solver='chol'): M/dt + theta S of the finest level is factored once (solvers.chol) and every step is the right-hand side
-    (pnl_csr_matvec, pnl_gemv_axpby) and two triangular sweeps (pnl_potrs); ``iterations`` then records 0 per step."""
+    (pnl_csr_matvec, pnl_gemv_axpby) and two triangular sweeps (pnl_potrs); ``iterations`` then records 0 per step.
+    solver='lu' is the same with the pivoted factors (solvers.plu, pnl_getrs) for any dense finest level, symmetric or not."""
 
     def __init__(self, hierarchy, dt, theta=0.5, tol=1e-8, maxiter=100, smoother=('jacobi', {'omega': 2.0/3.0}), solver='cg-mg'):
         assert 0. <= theta <= 1. and dt > 0.
-        if solver not in ('cg-mg', 'chol'):
-            raise NotImplementedError('solver {!r}: cg-mg and chol are built'.format(solver))
+        if solver not in ('cg-mg', 'chol', 'lu'):
+            raise NotImplementedError('solver {!r}: cg-mg, chol and lu are built'.format(solver))
         levels = hierarchy.getLevelList() if hasattr(hierarchy, 'getLevelList') else list(hierarchy)
         self.dt, self.theta, self.tol, self.maxiter = float(dt), float(theta), tol, maxiter
         self.solverType = solver
@@ -474,6 +475,11 @@ class CrankNicolson:
             if not isinstance(self.S, Dense_LinearOperator) or not self.S.symmetric:
                 raise NotImplementedError('solver=\'chol\' needs a symmetric dense operator on the finest level; got {!r}'.format(self.S))
             levels = levels[-1:]                               # the direct solver needs the finest level alone
+        elif solver == 'lu':
+            from .linear_operators import Dense_LinearOperator
+            if not isinstance(self.S, Dense_LinearOperator) or self.S.num_rows != self.S.num_columns:
+                raise NotImplementedError('solver=\'lu\' needs a dense operator on the finest level; got {!r}'.format(self.S))
+            levels = levels[-1:]
         self.device = self.S.A.device
         self.M = _DevCSR(levels[-1]['M'], self.device)
         self.transient = buildTransientHierarchy(levels, 1./self.dt, self.theta)
@@ -484,6 +490,10 @@ class CrankNicolson:
             T.symmetric = True
             self.ctx = self.S.ctx
             self.solver = self.factor = chol(T, overwrite=True)
+        elif solver == 'lu':
+            from .solvers import plu
+            self.ctx = self.S.ctx
+            self.solver = self.factor = plu(self.transient[-1]['A'], overwrite=True)
         else:
             self.solver = multigrid(self.transient, smoother=smoother)
             if not getattr(self.solver, '_native', False):
@@ -498,7 +508,7 @@ class CrankNicolson:
     def step(self, t, u, forcing):
         """advance u (a device vector, overwritten) from t to t + dt; returns t + dt"""
         import torch
-        if self.solverType == 'chol':
+        if self.solverType in ('chol', 'lu'):
             return self._step_chol(t, u, forcing)
         mg = self.solver
         f = mg._vec(forcing)
@@ -510,7 +520,7 @@ class CrankNicolson:
         return t+self.dt
 
     def _step_chol(self, t, u, forcing):
-        """rhs = forcing + (M/dt) u - (1 - theta) S u as in pnl_theta_step, then the two triangular sweeps"""
+        """rhs = forcing + (M/dt) u - (1 - theta) S u as in pnl_theta_step, then the two triangular sweeps (after the swaps for 'lu')"""
         import torch
         assert isinstance(u, torch.Tensor) and u.device == self.device and u.dtype == torch.float64 and u.is_contiguous()
         if isinstance(forcing, torch.Tensor):
@@ -522,8 +532,12 @@ class CrankNicolson:
         ctx.csr_matvec(n, self.M.indptr.data_ptr(), self.M.indices.data_ptr(), self.M.data.data_ptr(), u.data_ptr(), 1./self.dt, 1., rhs.data_ptr())
         if self.theta < 1.:
             ctx.gemv_axpby(self.S.A.data_ptr(), self.S.A.stride(0), n, n, u.data_ptr(), -(1.-self.theta), 1., rhs.data_ptr(), rhs.data_ptr())
-        Ld = self.factor._L
-        ctx.potrs(Ld.data_ptr(), Ld.stride(0) if n > 1 else Ld.shape[1], n, rhs.data_ptr(), n, 1)
+        if self.solverType == 'lu':
+            Ld = self.factor._LU
+            ctx.getrs(Ld.data_ptr(), Ld.stride(0) if n > 1 else Ld.shape[1], n, self.factor._piv.data_ptr(), rhs.data_ptr(), n, 1)
+        else:
+            Ld = self.factor._L
+            ctx.potrs(Ld.data_ptr(), Ld.stride(0) if n > 1 else Ld.shape[1], n, rhs.data_ptr(), n, 1)
         ctx.synchronize()
         u.copy_(rhs)
         self.iterations.append(0)

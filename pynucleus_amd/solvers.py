@@ -9,7 +9,8 @@ The dense operator additionally has this loop as one library call (pnl_cg_jacobi
 left (default) or right preconditioner, modified Gram-Schmidt, Givens rotations, the rotated right-hand side as residual
 estimate, restarts; the Krylov basis stays in HBM, the small Hessenberg problem lives on the host.
 ``chol`` / ``lu`` are the direct solver of the symmetric dense operators (lu_solver, solvers.pyx:80-186): the Cholesky factor is
-computed once in HBM (pnl_potrf), every solve is two triangular sweeps (pnl_potrs)."""
+computed once in HBM (pnl_potrf), every solve is two triangular sweeps (pnl_potrs).  ``plu`` is the same solver for any square dense
+operator, symmetric or not: P A = L U with partial pivoting (pnl_getrf), every solve the swaps and two sweeps (pnl_getrs)."""
 import numpy as np
 
 
@@ -291,8 +292,112 @@ def chol(A, overwrite=False):
     return CholeskyFactor(Ld, A.ctx)
 
 
+class LUFactor:
+    """P A = L U of a square dense operator: L (unit diagonal, not stored) below the diagonal of a device block, U on and above it,
+    and the swap sequence (int32, LAPACK's ipiv 0-based) on the device.  ``solve(b)`` = lu_solver.solve (solvers.pyx:80-186);
+    calling the object applies A^-1 to a device vector, so it can be the ``preconditioner=`` of cg / gmres / bicgstab."""
+
+    def __init__(self, LU_dev, piv_dev, ctx):
+        self._LU = LU_dev
+        self._piv = piv_dev
+        self.ctx = ctx
+        self.device = LU_dev.device
+        self.num_rows = self.num_columns = int(LU_dev.shape[0])
+        self.shape = (self.num_rows, self.num_columns)
+
+    def _host(self):
+        self.ctx.synchronize()
+        return self._LU.cpu().numpy()
+
+    @property
+    def L(self):
+        """the unit lower triangular factor as a numpy array (a copy; tests)"""
+        return np.tril(self._host(), -1)+np.eye(self.num_rows)
+
+    @property
+    def U(self):
+        """the upper triangular factor as a numpy array (a copy; tests)"""
+        return np.triu(self._host())
+
+    @property
+    def piv(self):
+        """the swap sequence: at step k the rows k and piv[k] were exchanged (a copy; tests)"""
+        self.ctx.synchronize()
+        return self._piv.cpu().numpy().copy()
+
+    @property
+    def perm(self):
+        """the row order with A[perm] = L U"""
+        perm = np.arange(self.num_rows)
+        for k, p in enumerate(self.piv):
+            perm[k], perm[p] = perm[p], perm[k]
+        return perm
+
+    def _ld(self):
+        return self._LU.stride(0) if self.num_rows > 1 else self._LU.shape[1]
+
+    def _solve_dev(self, X):
+        """in place on the rows of the contiguous device block X [nrhs, n]"""
+        import torch
+        torch.cuda.current_stream(self.device).synchronize()
+        self.ctx.getrs(self._LU.data_ptr(), self._ld(), self.num_rows, self._piv.data_ptr(), X.data_ptr(),
+                       X.stride(0) if X.shape[0] > 1 else max(X.shape[1], 1), X.shape[0])
+        self.ctx.synchronize()
+        return X
+
+    def solve(self, b):
+        """x with A x = b for a vector, or row by row for a 2-D array of right-hand sides; torch in, torch out, else numpy"""
+        import torch
+        X = _dev_vector(b, self.device)
+        if X.ndim not in (1, 2) or X.shape[-1] != self.num_rows:
+            raise AssertionError('right-hand side of shape {} for an operator with {} rows'.format(tuple(X.shape), self.num_rows))
+        shape = tuple(X.shape)
+        X = X.reshape(-1, self.num_rows).contiguous().clone()
+        self._solve_dev(X)
+        X = X.reshape(shape)
+        return X if isinstance(b, torch.Tensor) else X.cpu().numpy()
+
+    def __call__(self, r):
+        return self.solve(r)
+
+    def __repr__(self):
+        return '<LU factors of a {}x{} dense operator on {}>'.format(self.num_rows, self.num_columns, self.device)
+
+
+def plu(A, overwrite=False):
+    """LU factorisation with partial pivoting of a square dense operator, symmetric or not, on its device (pnl_getrf).  Without
+    ``overwrite`` a device copy of the block is factored; with it the operator's own storage becomes the factors (the operator is
+    invalidated and must not be applied any more).  Raises numpy.linalg.LinAlgError if a pivot is zero."""
+    import torch
+    from .linear_operators import Dense_LinearOperator
+    if not isinstance(A, Dense_LinearOperator) or A.num_rows != A.num_columns:
+        raise NotImplementedError('plu: a square Dense_LinearOperator on one GPU is needed (direct solves of H2, sparse or distributed '
+                                  'operators are not built); got {!r}'.format(A))
+    A.ctx.synchronize()
+    torch.cuda.current_stream(A.A.device).synchronize()
+    if overwrite:
+        Ld = A.A
+    else:
+        try:
+            Ld = A.A.clone(memory_format=torch.contiguous_format)
+        except torch.cuda.OutOfMemoryError as e:
+            raise MemoryError('plu: no room in HBM for a copy of the {} x {} operator ({:.1f} GB); '
+                              'plu(A, overwrite=True) factors it in place'.format(A.num_rows, A.num_columns,
+                                                                                  8e-9*A.num_rows*A.A.stride(0))) from e
+    n = A.num_rows
+    piv = torch.empty(max(n, 1), dtype=torch.int32, device=A.A.device)
+    torch.cuda.current_stream(A.A.device).synchronize()
+    info = A.ctx.getrf(Ld.data_ptr(), Ld.stride(0) if n > 1 else Ld.shape[1], n, piv.data_ptr())
+    if overwrite:
+        A.invalidate()
+    if info > 0:
+        raise np.linalg.LinAlgError('plu: the pivot of column {} is zero, the operator is singular'.format(info))
+    return LUFactor(Ld, piv[:n], A.ctx)
+
+
 def lu(A):
-    """the reference's name (lu_solver): for a symmetric dense operator the Cholesky factor"""
+    """the reference's name (lu_solver): for a symmetric dense operator the Cholesky factor.  ``plu`` is the pivoted factorisation,
+    for symmetric and non-symmetric operators alike."""
     if not getattr(A, 'symmetric', False):
         raise NotImplementedError('LU with pivoting')
     return chol(A)
