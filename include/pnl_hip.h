@@ -534,7 +534,7 @@ int pnl_theta_step(pnl_mg *mg, const double *S_dev, int64_t ldS, const int32_t *
 /* 1/diag(A) into dinv_dev (jacobi_solver.setup, solvers.pyx:233-237) */
 int pnl_inv_diagonal(pnl_context *ctx, const double *A_dev, int64_t ldA, int n, double *dinv_dev);
 
-/* ---- direct solver for the dense symmetric positive definite operators (csrc/pnl_chol.hip): what lu_solver.setup / solve
+/* ---- direct solver for the dense symmetric positive definite operators (csrc/pnl_direct.hip): what lu_solver.setup / solve
  *      (base/PyNucleus_base/solvers.pyx:80-186: dense copy, getrf, getrs) is for `--matrixFormat dense --solver lu`.  The operators
  *      of the symmetric kernels are positive definite, so the factor is Cholesky; pnl_getrf / pnl_getrs below are the LU. -------
  * replaces lu_solver.setup (solvers.pyx:80-186): A = L L^T in place on the lower triangle of the row-major n x n block A_dev
@@ -549,7 +549,7 @@ int pnl_potrf(pnl_context *ctx, double *A_dev, int64_t ldA, int n, int *info);
  * read).  Asynchronous on the context's stream. */
 int pnl_potrs(pnl_context *ctx, const double *L_dev, int64_t ldL, int n, double *B_dev, int64_t ldb, int nrhs);
 
-/* ---- direct solver for the dense operators that are not symmetric (csrc/pnl_lu.hip): lu_solver.setup / solve as they stand, getrf
+/* ---- direct solver for the dense operators that are not symmetric (csrc/pnl_direct.hip): lu_solver.setup / solve as they stand, getrf
  *      and getrs, for the orders evaluated per quadrature point. ------------------------------------------------------------------
  * replaces lu_solver.setup: P A = L U with partial pivoting in place on the row-major n x n block A_dev (leading dimension
  * ldA >= n).  The strict lower triangle receives L (unit diagonal, not stored, every |l_ik| <= 1), the upper triangle with the

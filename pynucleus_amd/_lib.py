@@ -619,7 +619,7 @@ class Context:
                                          C.c_void_p(u_ptr), float(tol), int(maxiter), C.byref(it), C.byref(res)))
         return it.value, res.value
 
-    # -- direct solver (pnl_chol.hip) --------------------------------------------------------------
+    # -- direct solver (pnl_direct.hip) ------------------------------------------------------------
     def potrf(self, A_ptr, ldA, n):
         """Cholesky factor in place on the lower triangle; returns info (0, or the order of the first minor that is not positive
         definite)"""
@@ -631,7 +631,7 @@ class Context:
         self.check(self.L.pnl_potrs(self.h, C.c_void_p(L_ptr) if L_ptr else None, int(ldL), int(n), C.c_void_p(B_ptr) if B_ptr else None,
                                     int(ldb), int(nrhs)))
 
-    # -- direct solver with pivoting (pnl_lu.hip) ---------------------------------------------------
+    # -- direct solver with pivoting (pnl_direct.hip) -----------------------------------------------
     def getrf(self, A_ptr, ldA, n, piv_ptr):
         """P A = L U in place, the swap sequence (int32, 0-based) into piv_ptr; returns info (0, or the 1-based column of the first
         pivot that is zero or NaN)"""

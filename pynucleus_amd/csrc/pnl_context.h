@@ -85,8 +85,8 @@ struct pnl_context {
     long long slot_total = 0;         // doubles
     // row slab of a rank (pnl_set_row_slab, pnl_slab.hip)
     DevBuf b_rowmap, b_rowdof, b_colmap, b_coldof;
-    DevBuf b_cholinfo;                // pnl_potrf (pnl_chol.hip): the word that takes the first pivot that is not positive
-    DevBuf b_luwork, b_lutmp;         // pnl_getrf (pnl_lu.hip): info word, ticket, pivot rows, partial maxima; pnl_getrs: the permuted right-hand sides
+    DevBuf b_cholinfo;                // pnl_potrf (pnl_direct.hip): the word that takes the first pivot that is not positive
+    DevBuf b_luwork, b_lutmp;         // pnl_getrf (pnl_direct.hip): info word, ticket, pivot rows, partial maxima; pnl_getrs: the permuted right-hand sides
     std::vector<int32_t> slab_rowdofs, slab_coldofs;
     int slab_rows = 0, slab_cols = 0;
     bool slot_full_list = false;      // the current tile list is the whole upper block triangle (pnl_assemble_dense)

@@ -216,30 +216,22 @@ def bicgstab(A, b, x0=None, tol=1e-8, maxiter=50, preconditioner=None):
     return x.cpu().numpy(), its, residuals
 
 
-class CholeskyFactor:
-    """A = L L^T of a symmetric positive definite dense operator, L in the lower triangle of a device block (the strict upper
-    triangle holds whatever the operator had there and is never read).  ``solve(b)`` = lu_solver.solve (solvers.pyx:80-186);
-    calling the object applies A^-1 to a device vector, so it can be the ``preconditioner=`` of cg / gmres / bicgstab."""
+class _DenseFactor:
+    """What the factors of a square dense operator share: the shape, the device and ``solve``.  A subclass keeps the device block
+    [n, ld] under its own name and supplies ``_trs(B_ptr, ldb, nrhs)``, the library's triangular solves in place on a device block
+    of right-hand sides."""
 
-    def __init__(self, L_dev, ctx):
-        self._L = L_dev
+    def __init__(self, F_dev, ctx):
         self.ctx = ctx
-        self.device = L_dev.device
-        self.num_rows = self.num_columns = int(L_dev.shape[0])
+        self.device = F_dev.device
+        self.num_rows = self.num_columns = int(F_dev.shape[0])
         self.shape = (self.num_rows, self.num_columns)
-
-    @property
-    def L(self):
-        """the factor as a lower-triangular numpy array (a copy; tests)"""
-        self.ctx.synchronize()
-        return np.tril(self._L.cpu().numpy())
 
     def _solve_dev(self, X):
         """in place on the rows of the contiguous device block X [nrhs, n]"""
         import torch
         torch.cuda.current_stream(self.device).synchronize()
-        self.ctx.potrs(self._L.data_ptr(), self._L.stride(0) if self.num_rows > 1 else self._L.shape[1], self.num_rows, X.data_ptr(),
-                       X.stride(0) if X.shape[0] > 1 else max(X.shape[1], 1), X.shape[0])
+        self._trs(X.data_ptr(), X.stride(0) if X.shape[0] > 1 else max(X.shape[1], 1), X.shape[0])
         self.ctx.synchronize()
         return X
 
@@ -258,6 +250,52 @@ class CholeskyFactor:
     def __call__(self, r):
         return self.solve(r)
 
+
+def _ld(F):
+    """row stride of the square device block F as the library wants it"""
+    return F.stride(0) if F.shape[0] > 1 else F.shape[1]
+
+
+def _factor_block(A, overwrite, name, accepts, needs):
+    """The device block that ``chol`` / ``plu`` (``name``) factor in place: the operator's own storage with ``overwrite``, else a
+    contiguous copy; both quiescent.  ``accepts(A)`` says whether A is a dense operator this factorisation takes, ``needs`` is the
+    text of the error if not."""
+    import torch
+    from .linear_operators import Dense_LinearOperator
+    if not isinstance(A, Dense_LinearOperator) or not accepts(A):
+        raise NotImplementedError('{}: {}; got {!r}'.format(name, needs, A))
+    A.ctx.synchronize()
+    torch.cuda.current_stream(A.A.device).synchronize()
+    if overwrite:
+        return A.A
+    try:
+        F = A.A.clone(memory_format=torch.contiguous_format)
+    except torch.cuda.OutOfMemoryError as e:
+        raise MemoryError('{0}: no room in HBM for a copy of the {1} x {2} operator ({3:.1f} GB); '
+                          '{0}(A, overwrite=True) factors it in place'.format(name, A.num_rows, A.num_columns,
+                                                                              8e-9*A.num_rows*A.A.stride(0))) from e
+    torch.cuda.current_stream(A.A.device).synchronize()
+    return F
+
+
+class CholeskyFactor(_DenseFactor):
+    """A = L L^T of a symmetric positive definite dense operator, L in the lower triangle of a device block (the strict upper
+    triangle holds whatever the operator had there and is never read).  ``solve(b)`` = lu_solver.solve (solvers.pyx:80-186);
+    calling the object applies A^-1 to a device vector, so it can be the ``preconditioner=`` of cg / gmres / bicgstab."""
+
+    def __init__(self, L_dev, ctx):
+        super().__init__(L_dev, ctx)
+        self._L = L_dev
+
+    @property
+    def L(self):
+        """the factor as a lower-triangular numpy array (a copy; tests)"""
+        self.ctx.synchronize()
+        return np.tril(self._L.cpu().numpy())
+
+    def _trs(self, B, ldb, nrhs):
+        self.ctx.potrs(self._L.data_ptr(), _ld(self._L), self.num_rows, B, ldb, nrhs)
+
     def __repr__(self):
         return '<Cholesky factor of a {}x{} dense operator on {}>'.format(self.num_rows, self.num_columns, self.device)
 
@@ -266,25 +304,10 @@ def chol(A, overwrite=False):
     """Cholesky factorisation of a symmetric dense operator on its device (pnl_potrf).  Without ``overwrite`` a device copy of the
     block is factored; with it the operator's own storage becomes the factor (its lower triangle; the operator is invalidated and
     must not be applied any more).  Raises numpy.linalg.LinAlgError if a leading minor is not positive definite."""
-    import torch
-    from .linear_operators import Dense_LinearOperator
-    if not isinstance(A, Dense_LinearOperator) or not A.symmetric:
-        raise NotImplementedError('chol: a symmetric Dense_LinearOperator is needed (direct solves of H2, sparse, distributed or '
-                                  'non-symmetric operators are not built); got {!r}'.format(A))
-    A.ctx.synchronize()
-    torch.cuda.current_stream(A.A.device).synchronize()
-    if overwrite:
-        Ld = A.A
-    else:
-        try:
-            Ld = A.A.clone(memory_format=torch.contiguous_format)
-        except torch.cuda.OutOfMemoryError as e:
-            raise MemoryError('chol: no room in HBM for a copy of the {} x {} operator ({:.1f} GB); '
-                              'chol(A, overwrite=True) factors it in place'.format(A.num_rows, A.num_columns,
-                                                                                   8e-9*A.num_rows*A.A.stride(0))) from e
-        torch.cuda.current_stream(A.A.device).synchronize()
-    n = A.num_rows
-    info = A.ctx.potrf(Ld.data_ptr(), Ld.stride(0) if n > 1 else Ld.shape[1], n)
+    Ld = _factor_block(A, overwrite, 'chol', lambda A: A.symmetric,
+                       'a symmetric Dense_LinearOperator is needed (direct solves of H2, sparse, distributed or '
+                       'non-symmetric operators are not built)')
+    info = A.ctx.potrf(Ld.data_ptr(), _ld(Ld), A.num_rows)
     if overwrite:
         A.invalidate()
     if info > 0:
@@ -292,18 +315,15 @@ def chol(A, overwrite=False):
     return CholeskyFactor(Ld, A.ctx)
 
 
-class LUFactor:
+class LUFactor(_DenseFactor):
     """P A = L U of a square dense operator: L (unit diagonal, not stored) below the diagonal of a device block, U on and above it,
     and the swap sequence (int32, LAPACK's ipiv 0-based) on the device.  ``solve(b)`` = lu_solver.solve (solvers.pyx:80-186);
     calling the object applies A^-1 to a device vector, so it can be the ``preconditioner=`` of cg / gmres / bicgstab."""
 
     def __init__(self, LU_dev, piv_dev, ctx):
+        super().__init__(LU_dev, ctx)
         self._LU = LU_dev
         self._piv = piv_dev
-        self.ctx = ctx
-        self.device = LU_dev.device
-        self.num_rows = self.num_columns = int(LU_dev.shape[0])
-        self.shape = (self.num_rows, self.num_columns)
 
     def _host(self):
         self.ctx.synchronize()
@@ -333,32 +353,8 @@ class LUFactor:
             perm[k], perm[p] = perm[p], perm[k]
         return perm
 
-    def _ld(self):
-        return self._LU.stride(0) if self.num_rows > 1 else self._LU.shape[1]
-
-    def _solve_dev(self, X):
-        """in place on the rows of the contiguous device block X [nrhs, n]"""
-        import torch
-        torch.cuda.current_stream(self.device).synchronize()
-        self.ctx.getrs(self._LU.data_ptr(), self._ld(), self.num_rows, self._piv.data_ptr(), X.data_ptr(),
-                       X.stride(0) if X.shape[0] > 1 else max(X.shape[1], 1), X.shape[0])
-        self.ctx.synchronize()
-        return X
-
-    def solve(self, b):
-        """x with A x = b for a vector, or row by row for a 2-D array of right-hand sides; torch in, torch out, else numpy"""
-        import torch
-        X = _dev_vector(b, self.device)
-        if X.ndim not in (1, 2) or X.shape[-1] != self.num_rows:
-            raise AssertionError('right-hand side of shape {} for an operator with {} rows'.format(tuple(X.shape), self.num_rows))
-        shape = tuple(X.shape)
-        X = X.reshape(-1, self.num_rows).contiguous().clone()
-        self._solve_dev(X)
-        X = X.reshape(shape)
-        return X if isinstance(b, torch.Tensor) else X.cpu().numpy()
-
-    def __call__(self, r):
-        return self.solve(r)
+    def _trs(self, B, ldb, nrhs):
+        self.ctx.getrs(self._LU.data_ptr(), _ld(self._LU), self.num_rows, self._piv.data_ptr(), B, ldb, nrhs)
 
     def __repr__(self):
         return '<LU factors of a {}x{} dense operator on {}>'.format(self.num_rows, self.num_columns, self.device)
@@ -369,25 +365,12 @@ def plu(A, overwrite=False):
     ``overwrite`` a device copy of the block is factored; with it the operator's own storage becomes the factors (the operator is
     invalidated and must not be applied any more).  Raises numpy.linalg.LinAlgError if a pivot is zero."""
     import torch
-    from .linear_operators import Dense_LinearOperator
-    if not isinstance(A, Dense_LinearOperator) or A.num_rows != A.num_columns:
-        raise NotImplementedError('plu: a square Dense_LinearOperator on one GPU is needed (direct solves of H2, sparse or distributed '
-                                  'operators are not built); got {!r}'.format(A))
-    A.ctx.synchronize()
-    torch.cuda.current_stream(A.A.device).synchronize()
-    if overwrite:
-        Ld = A.A
-    else:
-        try:
-            Ld = A.A.clone(memory_format=torch.contiguous_format)
-        except torch.cuda.OutOfMemoryError as e:
-            raise MemoryError('plu: no room in HBM for a copy of the {} x {} operator ({:.1f} GB); '
-                              'plu(A, overwrite=True) factors it in place'.format(A.num_rows, A.num_columns,
-                                                                                  8e-9*A.num_rows*A.A.stride(0))) from e
+    Ld = _factor_block(A, overwrite, 'plu', lambda A: A.num_rows == A.num_columns,
+                       'a square Dense_LinearOperator on one GPU is needed (direct solves of H2, sparse or distributed '
+                       'operators are not built)')
     n = A.num_rows
-    piv = torch.empty(max(n, 1), dtype=torch.int32, device=A.A.device)
-    torch.cuda.current_stream(A.A.device).synchronize()
-    info = A.ctx.getrf(Ld.data_ptr(), Ld.stride(0) if n > 1 else Ld.shape[1], n, piv.data_ptr())
+    piv = torch.empty(max(n, 1), dtype=torch.int32, device=Ld.device)
+    info = A.ctx.getrf(Ld.data_ptr(), _ld(Ld), n, piv.data_ptr())
     if overwrite:
         A.invalidate()
     if info > 0:

@@ -1,9 +1,9 @@
-"""The direct solver (pnl_potrf, pnl_potrs; csrc/pnl_chol.hip) through the C ABI on SYNTHETIC matrices built in numpy, in the manner of
+"""The direct solver (pnl_potrf, pnl_potrs; csrc/pnl_direct.hip) through the C ABI on SYNTHETIC matrices built in numpy, in the manner of
 tests/test_apply_kernels.py: no assembled operator, a bare context.
 
-Kernels and their constants (csrc/pnl_chol.hip): k_chol_diag / k_chol_panel work on panels of NB = 64 columns, OB = 256 columns make a
-block, k_chol_update works in T x T = 64 x 64 workgroup tiles (once per panel inside the block, once per block on the rest);
-k_chol_trsv_diag<false / true>, k_chol_fwd_sweep, k_chol_bwd_sweep walk block columns of NB.
+Kernels and their constants (csrc/pnl_direct.hip): k_chol_diag / k_chol_panel work on panels of NB = 64 columns, OB = 256 columns make
+a block, k_direct_update<true> works in T x T = 64 x 64 workgroup tiles (once per panel inside the block, once per block on the rest);
+k_direct_trsv_diag (L y = b, then L^T x = y), k_direct_sweep, k_chol_bwd_sweep walk block columns of NB.
 
 (E) exact.  L0 integer lower triangular, off-diagonal entries in [-3, 3] with about half of them zero, diagonal in {1, 2, 4};
     A = L0 L0^T.  Every partial sum of the factorisation of entry (i, j), in any order and with or without FMA, MFMA accumulation
@@ -27,7 +27,7 @@ import pytest
 
 gpu = pytest.mark.gpu
 
-NB, OB, T = 64, 256, 64                       # CH_NB, CH_OB, CH_T of csrc/pnl_chol.hip
+NB, OB, T = 64, 256, 64                       # NB, OB, T of csrc/pnl_direct.hip
 U = 2.**-53
 LD = np.longdouble
 LD_OK = np.finfo(np.longdouble).nmant >= 63

@@ -1,9 +1,10 @@
-"""The pivoted direct solver (pnl_getrf, pnl_getrs; csrc/pnl_lu.hip) through the C ABI on SYNTHETIC matrices built in numpy, in the manner
-of tests/test_cholesky.py: no assembled operator, a bare context.
+"""The pivoted direct solver (pnl_getrf, pnl_getrs; csrc/pnl_direct.hip) through the C ABI on SYNTHETIC matrices built in numpy, in the
+manner of tests/test_cholesky.py: no assembled operator, a bare context.
 
-Kernels and their constants (csrc/pnl_lu.hip): k_lu_step works on panels of NB = 64 columns, RB = 64 rows per workgroup; OB = 256 columns
-make a block; k_lu_update works in T x T = 64 x 64 tiles and stages KC = 32 columns of k per step; k_lu_swap / k_lu_u12 take 256 columns
-per workgroup; k_lu_gather, k_lu_trsv_diag<false / true>, k_lu_sweep walk block columns of NB.
+Kernels and their constants (csrc/pnl_direct.hip): k_lu_step works on panels of NB = 64 columns, RB = 64 rows per workgroup; OB = 256
+columns make a block; k_direct_update<false> works in T x T = 64 x 64 tiles and stages KC = 32 columns of k per step; k_lu_swap /
+k_lu_u12 take 256 columns per workgroup; k_lu_gather, k_direct_trsv_diag (L y = P b, then U x = y), k_direct_sweep walk block columns
+of NB.
 
 (E) exact.  L0 unit lower triangular, off-diagonal entries in {0, +-1/4, +-1/2} with about half of them zero; U0 upper triangular,
     off-diagonal entries 4 {-3 .. 3} with about half of them zero, diagonal in +-{4, 8, 16}; A = (L0 U0) with its rows scattered by a
@@ -29,7 +30,7 @@ from test_cholesky import gamma, LD, LD_OK, POISON, _hp, _hp_dot, _context, _dev
 
 gpu = pytest.mark.gpu
 
-NB, OB, T, KC, RB = 64, 256, 64, 32, 64         # LU_NB, LU_OB, LU_T, LU_KC, LU_RB of csrc/pnl_lu.hip
+NB, OB, T, KC, RB = 64, 256, 64, 32, 64         # NB, OB, T, KC, RB of csrc/pnl_direct.hip
 FULL_ROWS_MAX = 513
 LARGE = 2081                                    # 8 blocks and a narrow last panel
 SIZES = tuple(sorted({1, 2, 3, 15, 16, 17, LARGE, 4*NB+1, 2*OB+1} | {v for w in (NB, OB, T, KC, RB) for v in (w-1, w, w+1, 2*w-1, 2*w+1)}))
