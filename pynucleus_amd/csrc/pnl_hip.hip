@@ -5,6 +5,7 @@
 // pnl_kernels.h on one HIP stream.  No Python or torch types cross this boundary.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -18,6 +19,7 @@
 
 #include <thread>
 #include "pnl_context.h"
+#include "pnl_launch.h"
 
 // vertex order of the cells for the tile kernels (see finalize): search on host threads, tables on first use
 struct TileOrderJob {
@@ -532,6 +534,27 @@ void refresh_tables(pnl_context *ctx) {
 }
 
 
+// the per-cell diagonal blocks D (packed upper triangles, cells of P) into the dense matrix / into the sparse data
+template <int DPE>
+void scatter_diag(pnl_context *ctx, const DevProblem &P, const double *D, double *A, int64_t ldA) {
+    const long long nt = (long long)ctx->nc*DPE*DPE;
+    hipLaunchKernelGGL((k_scatter_diag<DPE>), dim3((unsigned)((nt+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0, ctx->stream, P, D,
+                       A, (long long)ldA);
+}
+template <int DPE>
+void scatter_diag_sparse(pnl_context *ctx, const double *D, const SparseOut &S) {
+    const long long n = (long long)ctx->nc*(DPE*(DPE+1)/2);
+    hipLaunchKernelGGL((k_scatter_diag_sparse<DPE>), dim3((unsigned)((n+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0, ctx->stream,
+                       ctx->P, D, ctx->nc, S);
+}
+
+// end of an assembly path that skips its later phases: their events, so that the phase timers read zero
+int finish_events(pnl_context *ctx, int from) {
+    for (int e = from; e < 8; e++) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
+    ctx->ev_valid = true; ctx->tiles_launched = true;
+    return PNL_OK;
+}
+
 template <int DIM, int DPE, int KT>
 int launch_pure(pnl_context *ctx, double *A, int64_t ldA, const SlotOut &SO) {
     if (ctx->n_pure == 0) return PNL_OK;
@@ -540,18 +563,16 @@ int launch_pure(pnl_context *ctx, double *A, int64_t ldA, const SlotOut &SO) {
     const size_t lds = sizeof(double)*(64*NP*DIM+64+2*64*ND+NP*(4+DPE)+(KT == 0 ? PNL_POW_TAB_DOUBLES : 0))+sizeof(int)*(64*DPE+64)
                        +sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
     auto kfun = k_tile_pure<DIM, DPE, KT>;
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int per_cu = 2;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kfun, PNL_NTHREADS, lds);
+    const PersistentGrid g = persistent_grid(ctx, kfun, PNL_NTHREADS, lds, ctx->n_pure, 2);
+    if (g.rc) return g.rc;
     if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] uniform tiles=%d of %d, lds=%zu bytes, occupancy API: %d blocks/CU\n", ctx->n_pure,
-                                       ctx->n_pure+ctx->n_mixed, lds, per_cu);
-    const int grid = pnl_grid_cap(std::min(ctx->n_pure, 256*std::max(per_cu, 1)));
+                                       ctx->n_pure+ctx->n_mixed, lds, g.per_cu);
     int pure_abl = 0;
 #ifdef PNL_DEBUG_ABLATE
     pure_abl = pnl_tune("PNL_PURE_ABL") ? atoi(pnl_tune("PNL_PURE_ABL")) : 0;
 #endif
     kt_begin(ctx, PNL_K_TILE_UNIFORM2);
-    hipLaunchKernelGGL(kfun, dim3(grid), dim3(PNL_NTHREADS), lds, ctx->stream, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->tile_off+ctx->n_mixed,
+    hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->tile_off+ctx->n_mixed,
                        ctx->n_pure, A, (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), acc_stride, 2,
                        (ctx->symflush ? 1 : 0) | pure_abl, SO);
     kt_end(ctx, PNL_K_TILE_UNIFORM2);
@@ -629,7 +650,29 @@ static size_t wl_lane_lds(F fun, int dpe, int kt) {
     return b;
 }
 
-// counting sort of a work-list region by order, then the sorted evaluation (k_worklist_lane / k_worklist_sorted);
+// sorted evaluation of a work list: the orders with at most PNL_WL_LANE_MAXPTS points one pair per lane (k_worklist_lane, if
+// `lane`), the others 16 lanes per pair with the rule in LDS (k_worklist_sorted; bins nmin .. last_bin).  kb_option / kb_default:
+// KB of LDS for the rule copy; rules with more points are read from global memory.  18 KB are 8 workgroups per CU
+// (60 KB / 2 workgroups per CU was 0.6 ms slower at 98,304 cells in the dense path and 4 ms at C4 in the cluster path)
+template <int DIM, int DPE, int KT, bool SPARSE>
+int worklist_eval(pnl_context *ctx, const char *kb_option, int kb_default, const int4 *sorted, const WlBins &B, double *A, int64_t ldA,
+                  double *D, const SparseOut &S, const ClusterTiles &CT, int last_bin, int nmin, bool lane, int lane_flags) {
+    const int wl_kb = pnl_tune(kb_option) ? std::max(4, atoi(pnl_tune(kb_option))) : kb_default;
+    const int tab_max = wl_tab_max<DPE>(wl_kb);
+    const int wl_grid = 256*std::max(1, std::min(8, 150/(wl_kb+(KT == 0 ? 3 : 0))));      // KT == 0: + 3 KB of power tables
+    const size_t lds = wl_sorted_lds<DPE>(tab_max);
+    auto wfun = k_worklist_sorted<DIM, DPE, KT, SPARSE>;
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)wfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lane)
+        hipLaunchKernelGGL((k_worklist_lane<DIM, DPE, KT, SPARSE>), dim3(256*4), dim3(PNL_NTHREADS), wl_lane_lds(k_worklist_lane<DIM, DPE, KT, SPARSE>, DPE, KT), ctx->stream, ctx->P,
+                           sorted, (const unsigned*)B.offs, A, (long long)ldA, D, S, lane_flags, CT);
+    hipLaunchKernelGGL(wfun, dim3(wl_grid), dim3(PNL_NTHREADS), lds, ctx->stream, ctx->P, sorted, (const unsigned*)B.offs,
+                       (const unsigned*)B.coff, A, (long long)ldA, D, tab_max, S, last_bin, nmin, CT);
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+
+// counting sort of a work-list region by order, then the sorted evaluation;
 // region: which copy of the sort buffers to use (passes that may run concurrently need their own)
 template <int DIM, int DPE, int KT>
 int run_worklist(pnl_context *ctx, const int4 *wl, const unsigned *wlc, unsigned cap, double *A, int64_t ldA, bool sym, int region = 0,
@@ -637,36 +680,16 @@ int run_worklist(pnl_context *ctx, const int4 *wl, const unsigned *wlc, unsigned
     int rc;
     if ((rc = ensure(ctx, ctx->b_wlsorted, (size_t)cap*nregions*sizeof(int4)))) return rc;
     if ((rc = ensure(ctx, ctx->b_wlaux, sizeof(unsigned)*(4*(PNL_WL_BINS+1))*nregions))) return rc;
-    unsigned *hist = (unsigned*)ctx->b_wlaux.p+(size_t)region*4*(PNL_WL_BINS+1), *offs = hist+(PNL_WL_BINS+1), *coff = offs+(PNL_WL_BINS+1),
-             *cursor = coff+(PNL_WL_BINS+1);
-    int4 *wlsorted = (int4*)ctx->b_wlsorted.p+(size_t)region*cap;
-    HIPCHK(ctx, hipMemsetAsync(hist, 0, sizeof(unsigned)*(PNL_WL_BINS+1), ctx->stream));
-    hipLaunchKernelGGL(k_wl_hist, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, wlc, cap, hist);
-    hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(64), 0, ctx->stream, (const unsigned*)hist, offs, coff, cursor);
-    hipLaunchKernelGGL(k_wl_scatter, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, wlc, cap, (const unsigned*)offs, cursor,
-                       wlsorted);
-    const int st = 4+DPE;
-    // LDS copy of the rule: 18 KB (8 workgroups per CU; rules with more points are read from global memory; 60 KB / 2 workgroups per CU was 0.6 ms slower at 98,304 cells)
-    const int wl_kb = pnl_tune("PNL_WL_LDS_KB") ? std::max(4, atoi(pnl_tune("PNL_WL_LDS_KB"))) : 18;
-    const int tab_max = wl_tab_max<DPE>(wl_kb);
-    const int wl_grid = 256*std::max(1, std::min(8, 150/(wl_kb+(KT == 0 ? 3 : 0))));      // KT == 0: + 3 KB of power tables
-    const size_t lds = wl_sorted_lds<DPE>(tab_max);
-    auto wfun = k_worklist_sorted<DIM, DPE, KT, false>;
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)wfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nmin = ctx->wl_lane ? PNL_WL_LANE_MAXPTS+1 : 0;
+    const int4 *wlsorted = (const int4*)ctx->b_wlsorted.p+(size_t)region*cap;
+    WlBins B;
+    if ((rc = wl_sort(ctx, wl, wlc, cap, (unsigned*)ctx->b_wlaux.p+(size_t)region*4*(PNL_WL_BINS+1), (int4*)wlsorted, B))) return rc;
     int dbg = 0;
 #ifdef PNL_DEBUG_ABLATE
     dbg = pnl_tune("PNL_WL_DBG") ? atoi(pnl_tune("PNL_WL_DBG")) : 0;
 #endif
-    if (ctx->wl_lane)
-        hipLaunchKernelGGL((k_worklist_lane<DIM, DPE, KT, false>), dim3(256*4), dim3(PNL_NTHREADS), wl_lane_lds(k_worklist_lane<DIM, DPE, KT, false>, DPE, KT), ctx->stream, ctx->P,
-                           (const int4*)wlsorted, (const unsigned*)offs, A, (long long)ldA, (double*)ctx->b_D.p, SparseOut{},
-                           dbg | (sym ? 8 : 0), ClusterTiles{});
-    hipLaunchKernelGGL(wfun, dim3(wl_grid), dim3(PNL_NTHREADS), lds, ctx->stream, ctx->P, (const int4*)wlsorted,
-                       (const unsigned*)offs, (const unsigned*)coff, A, (long long)ldA, (double*)ctx->b_D.p, tab_max,
-                       SparseOut{}, PNL_WL_BINS-1, nmin | (sym ? 1 << 16 : 0), ClusterTiles{});
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
+    const int nmin = ctx->wl_lane ? PNL_WL_LANE_MAXPTS+1 : 0;
+    return worklist_eval<DIM, DPE, KT, false>(ctx, "PNL_WL_LDS_KB", 18, wlsorted, B, A, ldA, (double*)ctx->b_D.p, SparseOut{}, ClusterTiles{},
+                                              PNL_WL_BINS-1, nmin | (sym ? 1 << 16 : 0), ctx->wl_lane, dbg | (sym ? 8 : 0));
 }
 
 // work list for the orders that are integrated one pair per wave: `regions` regions of equal capacity, sized generously;
@@ -714,11 +737,6 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
     const int ntiles = ctx->n_mixed;
     const int acc_stride = acc_stride_of(ctx->nU, S::fixed_bytes);
     const size_t lds = S::fixed_bytes+sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
-    if (pnl_tune("PNL_VERBOSE")) {
-        int nblk = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void*)k_tile_distant<DIM, DPE, TILE, KT, false>, tile_threads(DPE, KT), lds);
-        fprintf(stderr, "[pnl] tiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", ntiles, ctx->nU, lds, nblk);
-    }
     if (lds > 160*1024)
         return fail(ctx, PNL_ERR_UNSUPPORTED, "a block of %d cells touches %d DoFs: LDS sub-block of %zu bytes exceeds 160 KiB "
                     "(cells must be numbered with spatial locality)", TILE, ctx->nU, lds);
@@ -726,16 +744,15 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
     unsigned *wlc = (unsigned*)ctx->b_wlcount.p+wl_slot;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
     auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false>;
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int per_cu = 2;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kfun, tile_threads(DPE, KT), lds);
     const int grid_mult = pnl_tune("PNL_GRID_MULT") ? atoi(pnl_tune("PNL_GRID_MULT")) : 1;
-    const int grid = pnl_grid_cap(std::min(ntiles, 256*std::max(per_cu, 1)*std::max(grid_mult, 1)));
+    const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT), lds, ntiles, 2, grid_mult);
+    if (g.rc) return g.rc;
+    if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] tiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", ntiles, ctx->nU, lds, g.per_cu);
     SlotOut SOk = SO;
     SOk.nU = ctx->nU;                                       // rows of the LDS sub-block (also without the block-slot storage)
     kt_begin(ctx, PNL_K_TILE_GENERAL);
-    if (grid > 0)
-        hipLaunchKernelGGL(kfun, dim3(grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)), (const int2*)ctx->b_tiles.p+ctx->tile_off, A,
+    if (g.grid > 0)
+        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)), (const int2*)ctx->b_tiles.p+ctx->tile_off, A,
                            (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), cell_begin, cell_end, acc_stride, (int4*)ctx->b_wl.p,
                            wlc, ctx->wl_cap_each, ctx->ablate | (ctx->symflush ? 256 : 0), ntiles, ClusterTiles{},
                            (unsigned*)ctx->b_tilectr.p, SOk);
@@ -752,26 +769,26 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
     return run_worklist<DIM, DPE, KT>(ctx, (const int4*)ctx->b_wl.p, wlc, ctx->wl_cap_each, A, ldA, ctx->symflush || SO.A2 != nullptr);
 }
 
-template <int DIM, int DPE, int SLOT, int KT>
-int launch_singular_slot(pnl_context *ctx, int np, double *A, int64_t ldA, int cell_begin, int cell_end) {
-    constexpr int NV = DIM+1;
-    const int2 *pairs = (const int2*)(ctx->orient ? ctx->C().b_spairs1[SLOT].p : ctx->C().b_spairs[SLOT].p);
+// touching pairs (k_singular_pairs): the rule of the slot staged in LDS if it needs at most 150 KB, else read from global memory;
+// at most 256 * min(workgroups per CU, 4) workgroups, fewer if `want` (the site's own count) is smaller; INT_MAX selects that
+// fixed grid (the sparse path, whose pairs are counted on the device)
+template <int DIM, int DPE, int SLOT, int KT, bool SPARSE>
+int launch_singular_pairs(pnl_context *ctx, int want, const int2 *pairs, int np, double *A, int64_t ldA, int cell_begin, int cell_end,
+                          const SparseOut &S, const int4 *sorted, const unsigned *offs, const ClusterTiles &CT) {
     const int M = ctx->P.sM[SLOT], rows = ctx->P.sRows[SLOT];
-    const size_t lds = sizeof(double)*(size_t)(2*NV+1+rows)*M;
-    const int waves_per_block = PNL_SING_THREADS/64;
-    if (lds <= 150*1024) {
-        auto kfun = k_singular_pairs<DIM, DPE, SLOT, KT, true, false>;
+    const size_t lds = sizeof(double)*(size_t)(2*(DIM+1)+1+rows)*M;
+    const bool stage = lds <= 150*1024;
+    const int per_cu = stage ? std::max(1, (int)((160*1024)/std::max<size_t>(lds, 1))) : 4;
+    const int grid = std::min(want, 256*std::min(per_cu, 4));
+    auto launch = [&](auto kfun, size_t bytes) {
+        hipLaunchKernelGGL(kfun, dim3(grid), dim3(PNL_SING_THREADS), bytes, ctx->stream, ctx->P, pairs, np, A, (long long)ldA, cell_begin,
+                           cell_end, S, sorted, offs, CT);
+    };
+    if (stage) {
+        auto kfun = k_singular_pairs<DIM, DPE, SLOT, KT, true, SPARSE>;
         HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int per_cu = std::max(1, (int)((160*1024)/std::max<size_t>(lds, 1)));
-        const int grid = std::min((np+waves_per_block-1)/waves_per_block, 256*std::min(per_cu, 4));
-        hipLaunchKernelGGL(kfun, dim3(grid), dim3(PNL_SING_THREADS), lds, ctx->stream, ctx->P, pairs, np, A, (long long)ldA,
-                           cell_begin, cell_end, SparseOut{}, (const int4*)nullptr, (const unsigned*)nullptr, ClusterTiles{});
-    } else {
-        const int grid = std::min((np+waves_per_block-1)/waves_per_block, 256*4);
-        hipLaunchKernelGGL((k_singular_pairs<DIM, DPE, SLOT, KT, false, false>), dim3(grid), dim3(PNL_SING_THREADS), 0, ctx->stream,
-                           ctx->P, pairs, np, A, (long long)ldA, cell_begin, cell_end, SparseOut{}, (const int4*)nullptr,
-                           (const unsigned*)nullptr, ClusterTiles{});
-    }
+        launch(kfun, lds);
+    } else launch(k_singular_pairs<DIM, DPE, SLOT, KT, false, SPARSE>, 0);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
@@ -782,10 +799,13 @@ int launch_singular(pnl_context *ctx, double *A, int64_t ldA, int cell_begin, in
         const int np = ctx->orient ? ctx->C().n_spairs1[s] : ctx->C().n_spairs[s];
         if (!np) continue;
         if (!ctx->C().have_sing[0][s]) return fail(ctx, PNL_ERR_STATE, "singular rule for %d common vertices not uploaded", s+1);
-        int rc;
-        if (s == 0) rc = launch_singular_slot<DIM, DPE, 0, KT>(ctx, np, A, ldA, cell_begin, cell_end);
-        else if (s == 1) rc = launch_singular_slot<DIM, DPE, 1, KT>(ctx, np, A, ldA, cell_begin, cell_end);
-        else rc = launch_singular_slot<DIM, DPE, (DIM == 2 ? 2 : 1), KT>(ctx, np, A, ldA, cell_begin, cell_end);
+        const int wpb = PNL_SING_THREADS/64;
+        int rc = with_slot<DIM>(s, [&](auto slot) {
+            constexpr int SLOT = decltype(slot)::value;
+            const int2 *pairs = (const int2*)(ctx->orient ? ctx->C().b_spairs1[SLOT].p : ctx->C().b_spairs[SLOT].p);
+            return launch_singular_pairs<DIM, DPE, SLOT, KT, false>(ctx, (np+wpb-1)/wpb, pairs, np, A, ldA, cell_begin, cell_end, SparseOut{},
+                                                                    nullptr, nullptr, ClusterTiles{});
+        });
         if (rc) return rc;
     }
     return PNL_OK;
@@ -846,24 +866,18 @@ int launch_boundary(pnl_context *ctx, int cell_begin, int cell_end, int what = 3
                 }
             }
         }
-        if (tiled) {}
-        else if (fast)
-            hipLaunchKernelGGL((k_boundary_distant<DIM, DPE, 1>), dim3(gx, chunks), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
+        // one dispatch per kernel: both instantiations of a kernel are named together, in the order the code object has them
+        if (!tiled) with_kt(fast, [&](auto kt) {
+            hipLaunchKernelGGL((k_boundary_distant<DIM, DPE, decltype(kt)::value>), dim3(gx, chunks), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
                                (double*)ctx->b_D.p, cell_begin, cell_end, per, bkcls, bfcls, defer, dcells, dfacets, dslots, dcount, cap, dcls);
-        else
-            hipLaunchKernelGGL((k_boundary_distant<DIM, DPE, 0>), dim3(gx, chunks), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
-                               (double*)ctx->b_D.p, cell_begin, cell_end, per, bkcls, bfcls, defer, dcells, dfacets, dslots, dcount, cap, dcls);
-        if (use_list) {
-            const double *verts = (const double*)ctx->b_vertices.p;
-            if (fast)
-                hipLaunchKernelGGL((k_boundary_items<DIM, DPE, 1>), dim3(256*4), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts,
-                                   (const int*)dcells, (const int*)dfacets, (const unsigned*)dslots, (int)cap, 1., SparseOut{},
-                                   (double*)ctx->b_D.p, (const unsigned*)dcount, bkcls ? (const int*)dcls : nullptr, bkcls, bfcls);
-            else
-                hipLaunchKernelGGL((k_boundary_items<DIM, DPE, 0>), dim3(256*4), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts,
-                                   (const int*)dcells, (const int*)dfacets, (const unsigned*)dslots, (int)cap, 1., SparseOut{},
-                                   (double*)ctx->b_D.p, (const unsigned*)dcount, bkcls ? (const int*)dcls : nullptr, bkcls, bfcls);
-        }
+            return PNL_OK;
+        });
+        if (use_list) with_kt(fast, [&](auto kt) {
+            hipLaunchKernelGGL((k_boundary_items<DIM, DPE, decltype(kt)::value>), dim3(256*4), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
+                               (const double*)ctx->b_vertices.p, (const int*)dcells, (const int*)dfacets, (const unsigned*)dslots, (int)cap, 1.,
+                               SparseOut{}, (double*)ctx->b_D.p, (const unsigned*)dcount, bkcls ? (const int*)dcls : nullptr, bkcls, bfcls);
+            return PNL_OK;
+        });
         HIPCHK(ctx, hipGetLastError());
     }
     if (what & 2)
@@ -873,11 +887,13 @@ int launch_boundary(pnl_context *ctx, int cell_begin, int cell_end, int what = 3
         if (!ctx->C().have_sing[1][s]) return fail(ctx, PNL_ERR_STATE, "boundary singular rule for %d common vertices not uploaded", s+1);
         const int grid = (np+3)/4;
         const int2 *pairs = (const int2*)ctx->C().b_bpairs[s].p;
-        const bool fast = ctx->P.bkn.fast;
-        if (s == 0 && fast) hipLaunchKernelGGL((k_boundary_singular<DIM, DPE, 0, 1>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, pairs, np, (double*)ctx->b_D.p, cell_begin, cell_end);
-        else if (s == 0) hipLaunchKernelGGL((k_boundary_singular<DIM, DPE, 0, 0>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, pairs, np, (double*)ctx->b_D.p, cell_begin, cell_end);
-        else if (fast) hipLaunchKernelGGL((k_boundary_singular<DIM, DPE, (DIM == 2 ? 1 : 0), 1>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, pairs, np, (double*)ctx->b_D.p, cell_begin, cell_end);
-        else hipLaunchKernelGGL((k_boundary_singular<DIM, DPE, (DIM == 2 ? 1 : 0), 0>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, pairs, np, (double*)ctx->b_D.p, cell_begin, cell_end);
+        auto launch = [&](auto kfun) {
+            hipLaunchKernelGGL(kfun, dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, pairs, np, (double*)ctx->b_D.p, cell_begin, cell_end);
+            return PNL_OK;
+        };
+        const bool fast = ctx->P.bkn.fast != 0;
+        if (s == 0) with_kt(fast, [&](auto kt) { return launch(k_boundary_singular<DIM, DPE, 0, decltype(kt)::value>); });
+        else with_kt(fast, [&](auto kt) { return launch(k_boundary_singular<DIM, DPE, (DIM == 2 ? 1 : 0), decltype(kt)::value>); });
         HIPCHK(ctx, hipGetLastError());
     }
     return PNL_OK;
@@ -960,8 +976,9 @@ int launch_tiles_single(pnl_context *ctx, double *A, int64_t ldA, int cell_begin
             fork.use(k);
             const int4 *wl = (const int4*)ctx->b_wl.p+(size_t)k*ctx->wl_cap_each;
             const unsigned *wlc = (const unsigned*)ctx->b_wlcount.p+k;
-            rc = ctx->P.k.fast ? run_worklist<DIM, DPE, 1>(ctx, wl, wlc, ctx->wl_cap_each, A, ldA, sym, k, ncls)
-                               : run_worklist<DIM, DPE, 0>(ctx, wl, wlc, ctx->wl_cap_each, A, ldA, sym, k, ncls);
+            rc = with_kt(ctx->P.k.fast, [&](auto kt) {
+                return run_worklist<DIM, DPE, decltype(kt)::value>(ctx, wl, wlc, ctx->wl_cap_each, A, ldA, sym, k, ncls);
+            });
             if (rc) { ctx->cur = 0; return rc; }
         }
     }
@@ -1097,8 +1114,7 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
             const int tb0 = ctx->tile_cell_filter ? cell_begin : 0, tb1 = ctx->tile_cell_filter ? cell_end : ctx->nc;
             // s = 1/2 in 2D (exponent -6/4) has its own instantiation: branch-free evaluations
             if (ctx->P.k.fast && ctx->P.k.qm == 6 && DPE == 3 && !pnl_tune("PNL_NO_KT2")) rc = launch_tiles<DIM, DPE, TILE, (DPE == 3 ? 2 : 1)>(ctx, ko, A, ldA, tb0, tb1, SO);
-            else rc = ctx->P.k.fast ? launch_tiles<DIM, DPE, TILE, 1>(ctx, ko, A, ldA, tb0, tb1, SO)
-                                    : launch_tiles<DIM, DPE, TILE, 0>(ctx, ko, A, ldA, tb0, tb1, SO);
+            else rc = with_kt(ctx->P.k.fast, [&](auto kt) { return launch_tiles<DIM, DPE, TILE, decltype(kt)::value>(ctx, ko, A, ldA, tb0, tb1, SO); });
             if (rc) { ctx->cur = 0; ctx->orient = 0; return rc; }
         }
         }
@@ -1138,8 +1154,7 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
             ctx->cur = ko/norient; ctx->orient = ko%norient;
             refresh_tables(ctx);
             fork.use(ko);
-            rc = ctx->P.k.fast ? launch_singular<DIM, DPE, 1>(ctx, A, ldA, cell_begin, cell_end)
-                               : launch_singular<DIM, DPE, 0>(ctx, A, ldA, cell_begin, cell_end);
+            rc = with_kt(ctx->P.k.fast, [&](auto kt) { return launch_singular<DIM, DPE, decltype(kt)::value>(ctx, A, ldA, cell_begin, cell_end); });
             if (rc) { ctx->cur = 0; ctx->orient = 0; return rc; }
         }
     }
@@ -1161,12 +1176,8 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
     if (bnd_side) HIPCHK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join[1], 0));
     HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     if (ctx->slab_rows == 0) {
-        const long long nt = (long long)ctx->nc*DPE*DPE;
-        hipLaunchKernelGGL((k_scatter_diag<DPE>), dim3((unsigned)((nt+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0,
-                           ctx->stream, ctx->P, (const double*)ctx->b_D.p, A, (long long)ldA);
-        if (ctx->have_tile_order)
-            hipLaunchKernelGGL((k_scatter_diag<DPE>), dim3((unsigned)((nt+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0,
-                               ctx->stream, tile_problem(ctx), (const double*)ctx->b_Dt.p, A, (long long)ldA);
+        scatter_diag<DPE>(ctx, ctx->P, (const double*)ctx->b_D.p, A, ldA);
+        if (ctx->have_tile_order) scatter_diag<DPE>(ctx, tile_problem(ctx), (const double*)ctx->b_Dt.p, A, ldA);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
@@ -1175,26 +1186,6 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
 }
 
 // ---- masked pair assembly into CSR / SSS (assembleClusters) --------------------------------------------------------
-template <int DIM, int DPE, int SLOT, int KT>
-int launch_singular_sparse(pnl_context *ctx, const SparseOut &S, const int4 *sorted, const unsigned *offs) {
-    constexpr int NV = DIM+1;
-    if (!ctx->C().have_sing[0][SLOT]) return PNL_OK;     // checked against the histogram by the caller
-    const int M = ctx->P.sM[SLOT], rows = ctx->P.sRows[SLOT];
-    const size_t lds = sizeof(double)*(size_t)(2*NV+1+rows)*M;
-    if (lds <= 150*1024) {
-        auto kfun = k_singular_pairs<DIM, DPE, SLOT, KT, true, true>;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int per_cu = std::max(1, (int)((160*1024)/std::max<size_t>(lds, 1)));
-        hipLaunchKernelGGL(kfun, dim3(256*std::min(per_cu, 4)), dim3(PNL_SING_THREADS), lds, ctx->stream, ctx->P, (const int2*)nullptr, 0,
-                           (double*)nullptr, 0ll, 0, 0, S, sorted, offs, ClusterTiles{});
-    } else {
-        hipLaunchKernelGGL((k_singular_pairs<DIM, DPE, SLOT, KT, false, true>), dim3(256*4), dim3(PNL_SING_THREADS), 0, ctx->stream,
-                           ctx->P, (const int2*)nullptr, 0, (double*)nullptr, 0ll, 0, 0, S, sorted, offs, ClusterTiles{});
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
-}
-
 // classify == false: the work list b_mp_wl[0..np) has been filled on the device (k_fh_pairs)
 template <int DIM, int DPE, int KT>
 int pairs_masked_impl(pnl_context *ctx, int np, const SparseOut &S, bool classify = true, bool first = true, bool keepD = false) {
@@ -1202,61 +1193,46 @@ int pairs_masked_impl(pnl_context *ctx, int np, const SparseOut &S, bool classif
     if ((rc = ensure(ctx, ctx->b_mp_wl, (size_t)np*sizeof(int4)))) return rc;
     if ((rc = ensure(ctx, ctx->b_mp_sorted, (size_t)np*sizeof(int4)))) return rc;
     if ((rc = ensure(ctx, ctx->b_mp_aux, sizeof(unsigned)*(4*(PNL_WL_BINS+1)+1)))) return rc;
-    unsigned *hist = (unsigned*)ctx->b_mp_aux.p, *offs = hist+(PNL_WL_BINS+1), *coff = offs+(PNL_WL_BINS+1), *cursor = coff+(PNL_WL_BINS+1),
-             *count = cursor+(PNL_WL_BINS+1);
+    unsigned *count = (unsigned*)ctx->b_mp_aux.p+4*(PNL_WL_BINS+1);      // behind the four bin arrays of wl_sort
     int4 *wl = (int4*)ctx->b_mp_wl.p, *sorted = (int4*)ctx->b_mp_sorted.p;
     const unsigned unp = (unsigned)np;
-    HIPCHK(ctx, hipMemsetAsync(hist, 0, sizeof(unsigned)*(PNL_WL_BINS+1), ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(count, &unp, sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // unp lives on this stack frame
     if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     if (classify)
         hipLaunchKernelGGL((k_mp_classify<DIM, DPE>), dim3((np+PNL_NTHREADS-1)/PNL_NTHREADS), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
                            S.pairs, np, wl);
-    hipLaunchKernelGGL(k_wl_hist, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, (const int4*)wl, (const unsigned*)count, unp, hist);
-    hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(64), 0, ctx->stream, (const unsigned*)hist, offs, coff, cursor);
-    hipLaunchKernelGGL(k_wl_scatter, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, (const int4*)wl, (const unsigned*)count, unp,
-                       (const unsigned*)offs, cursor, sorted);
-    hipLaunchKernelGGL(k_mp_stats, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, ctx->P, (const unsigned*)hist);
+    WlBins B;
+    if ((rc = wl_sort(ctx, wl, count, unp, (unsigned*)ctx->b_mp_aux.p, sorted, B))) return rc;
+    hipLaunchKernelGGL(k_mp_stats, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, ctx->P, (const unsigned*)B.hist);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     {
-        const int st = 4+DPE;
-        // LDS copy of the rule: see run_worklist (PNL_WL_MP_KB: A/B switch of the sparse path)
-        const int wl_kb = pnl_tune("PNL_WL_MP_KB") ? std::max(4, atoi(pnl_tune("PNL_WL_MP_KB"))) : 60;
-        const int tab_max = wl_tab_max<DPE>(wl_kb);
-        const int wl_grid = 256*std::max(1, std::min(8, 150/(wl_kb+(KT == 0 ? 3 : 0))));
-        const size_t lds = wl_sorted_lds<DPE>(tab_max);
-        auto wfun = k_worklist_sorted<DIM, DPE, KT, true>;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)wfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int nmin = ctx->wl_lane ? PNL_WL_LANE_MAXPTS+1 : 0;
         // no masks (getSparse): diagonal blocks through the per-cell buffer, one scatter per cell at the end
         constexpr int ND = DPE*(DPE+1)/2;
         double *Dbuf = S.masks ? nullptr : (double*)ctx->b_D.p;
         if (Dbuf && !keepD) HIPCHK(ctx, hipMemsetAsync(Dbuf, 0, sizeof(double)*(size_t)ctx->ncp*ND, ctx->stream));      // keepD: the tiles of a finite horizon have been there
-        if (ctx->wl_lane)
-            hipLaunchKernelGGL((k_worklist_lane<DIM, DPE, KT, true>), dim3(256*4), dim3(PNL_NTHREADS), wl_lane_lds(k_worklist_lane<DIM, DPE, KT, true>, DPE, KT), ctx->stream, ctx->P,
-                               (const int4*)sorted, (const unsigned*)offs, (double*)nullptr, 0ll, Dbuf, S, 0, ClusterTiles{});
-        hipLaunchKernelGGL(wfun, dim3(wl_grid), dim3(PNL_NTHREADS), lds, ctx->stream, ctx->P, (const int4*)sorted, (const unsigned*)offs,
-                           (const unsigned*)coff, (double*)nullptr, 0ll, Dbuf, tab_max, S, PNL_MAXQ, nmin, ClusterTiles{});
-        if (Dbuf) {
-            const long long n = (long long)ctx->nc*ND;
-            hipLaunchKernelGGL((k_scatter_diag_sparse<DPE>), dim3((unsigned)((n+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0,
-                               ctx->stream, ctx->P, (const double*)Dbuf, ctx->nc, S);
-        }
+        // 60 KB of rule copy and the bins up to PNL_MAXQ: differences from the dense path that are kept, not decided
+        const int nmin = ctx->wl_lane ? PNL_WL_LANE_MAXPTS+1 : 0;
+        if ((rc = worklist_eval<DIM, DPE, KT, true>(ctx, "PNL_WL_MP_KB", 60, sorted, B, nullptr, 0, Dbuf, S, ClusterTiles{}, PNL_MAXQ, nmin,
+                                                    ctx->wl_lane, 0))) return rc;
+        if (Dbuf) scatter_diag_sparse<DPE>(ctx, Dbuf, S);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     // touching pairs: bins 121 (common vertex), 122 (common edge / identical in 1D), 123 (identical in 2D)
     unsigned hh[PNL_WL_BINS+1];
-    HIPCHK(ctx, hipMemcpyAsync(hh, hist, sizeof(hh), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(hh, B.hist, sizeof(hh), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (int s = 0; s < DIM+1; s++)
         if (hh[121+s] && !ctx->C().have_sing[0][s]) return fail(ctx, PNL_ERR_STATE, "singular rule for %d common vertices not uploaded", s+1);
-    if (hh[121] && (rc = launch_singular_sparse<DIM, DPE, 0, KT>(ctx, S, sorted, offs))) return rc;
-    if (hh[122] && (rc = launch_singular_sparse<DIM, DPE, 1, KT>(ctx, S, sorted, offs))) return rc;
-    if (DIM == 2 && hh[123] && (rc = launch_singular_sparse<DIM, DPE, (DIM == 2 ? 2 : 1), KT>(ctx, S, sorted, offs))) return rc;
+    for (int s = 0; s < DIM+1; s++)
+        if (hh[121+s] && (rc = with_slot<DIM>(s, [&](auto slot) {
+                // the pairs come from the sorted list: the fixed grid of the sparse path, whatever their number
+                return launch_singular_pairs<DIM, DPE, decltype(slot)::value, KT, true>(ctx, INT_MAX, nullptr, 0, nullptr, 0, 0, 0, S, sorted, B.offs,
+                                                                                        ClusterTiles{});
+            }))) return rc;
     HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
@@ -1270,13 +1246,12 @@ int boundary_masked_impl(pnl_context *ctx, int ni, double fac, const SparseOut &
     const int grid = std::min((ni+3)/4, 256*8);
     const int *cells = (const int*)ctx->b_bi_cells.p, *facets = (const int*)ctx->b_bi_facets.p;
     const unsigned *masks = (const unsigned*)ctx->b_bi_masks.p;
-    const double *verts = (const double*)ctx->b_vertices.p;
-    if (ctx->P.bkn.fast)
-        hipLaunchKernelGGL((k_boundary_items<DIM, DPE, 1>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, cells, facets,
-                           masks, ni, fac, S, (double*)nullptr, (const unsigned*)nullptr, (const int*)nullptr, (const DevKernel*)nullptr, (const DevFormula*)nullptr);
-    else
-        hipLaunchKernelGGL((k_boundary_items<DIM, DPE, 0>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, cells, facets,
-                           masks, ni, fac, S, (double*)nullptr, (const unsigned*)nullptr, (const int*)nullptr, (const DevKernel*)nullptr, (const DevFormula*)nullptr);
+    with_kt(ctx->P.bkn.fast, [&](auto kt) {
+        hipLaunchKernelGGL((k_boundary_items<DIM, DPE, decltype(kt)::value>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
+                           (const double*)ctx->b_vertices.p, cells, facets, masks, ni, fac, S, (double*)nullptr, (const unsigned*)nullptr,
+                           (const int*)nullptr, (const DevKernel*)nullptr, (const DevFormula*)nullptr);
+        return PNL_OK;
+    });
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
@@ -1317,13 +1292,11 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
     }
     if (pl->ntiles > 0) {
         auto kfun = k_tile_distant<DIM, DPE, TILE, KT, true>;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 2;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kfun, tile_threads(DPE, KT), lds);
+        const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT), lds, pl->ntiles, 2);
+        if (g.rc) return g.rc;
         if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] cluster tiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", pl->ntiles,
-                                           pl->chunk_stride, lds, per_cu);
-        const int grid = pnl_grid_cap(std::min(pl->ntiles, 256*std::max(per_cu, 1)));
-        hipLaunchKernelGGL(kfun, dim3(grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, ctx->P), (const int2*)nullptr, (double*)nullptr, 0ll,
+                                           pl->chunk_stride, lds, g.per_cu);
+        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, ctx->P), (const int2*)nullptr, (double*)nullptr, 0ll,
                            (double*)nullptr, 0, ctx->nc, acc_stride, (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, ctx->wl_cap, 0,
                            pl->ntiles, CT, (unsigned*)ctx->b_tilectr.p, SlotOut{});
         HIPCHK(ctx, hipGetLastError());
@@ -1343,28 +1316,12 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
     {
         if ((rc = ensure(ctx, ctx->b_wlsorted, (size_t)ctx->wl_cap*sizeof(int4)))) return rc;
         if ((rc = ensure(ctx, ctx->b_wlaux, sizeof(unsigned)*(4*(PNL_WL_BINS+1))))) return rc;
-        unsigned *hist = (unsigned*)ctx->b_wlaux.p, *offs = hist+(PNL_WL_BINS+1), *coff = offs+(PNL_WL_BINS+1), *cursor = coff+(PNL_WL_BINS+1);
-        HIPCHK(ctx, hipMemsetAsync(hist, 0, sizeof(unsigned)*(PNL_WL_BINS+1), ctx->stream));
-        const int4 *wl = (const int4*)ctx->b_wl.p;
-        const unsigned *wlc = (const unsigned*)ctx->b_wlcount.p;
-        hipLaunchKernelGGL(k_wl_hist, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, wlc, ctx->wl_cap, hist);
-        hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(64), 0, ctx->stream, (const unsigned*)hist, offs, coff, cursor);
-        hipLaunchKernelGGL(k_wl_scatter, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, wlc, ctx->wl_cap, (const unsigned*)offs, cursor,
-                           (int4*)ctx->b_wlsorted.p);
-        const int st = 4+DPE;
-        // LDS copy of the rule: see run_worklist (PNL_WL_CL_KB: A/B switch of the cluster path)
-        const int wl_kb = pnl_tune("PNL_WL_CL_KB") ? std::max(4, atoi(pnl_tune("PNL_WL_CL_KB"))) : 18;      // 60 KB / two workgroups per CU: + 4 ms at C4
-        const int tab_max = wl_tab_max<DPE>(wl_kb);
-        const size_t wlds = wl_sorted_lds<DPE>(tab_max);
-        const int wl_grid = 256*std::max(1, std::min(8, 150/(wl_kb+(KT == 0 ? 3 : 0))));
-        auto wfun = k_worklist_sorted<DIM, DPE, KT, false>;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)wfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        hipLaunchKernelGGL((k_worklist_lane<DIM, DPE, KT, false>), dim3(256*4), dim3(PNL_NTHREADS), wl_lane_lds(k_worklist_lane<DIM, DPE, KT, false>, DPE, KT), ctx->stream, ctx->P,
-                           (const int4*)ctx->b_wlsorted.p, (const unsigned*)offs, (double*)nullptr, 0ll, (double*)nullptr, SparseOut{}, 0, CT);
-        hipLaunchKernelGGL(wfun, dim3(wl_grid), dim3(PNL_NTHREADS), wlds, ctx->stream, ctx->P, (const int4*)ctx->b_wlsorted.p,
-                           (const unsigned*)offs, (const unsigned*)coff, (double*)nullptr, 0ll, (double*)nullptr, tab_max, SparseOut{},
-                           PNL_WL_BINS-1, PNL_WL_LANE_MAXPTS+1, CT);
-        HIPCHK(ctx, hipGetLastError());
+        WlBins B;
+        if ((rc = wl_sort(ctx, (const int4*)ctx->b_wl.p, (const unsigned*)ctx->b_wlcount.p, ctx->wl_cap, (unsigned*)ctx->b_wlaux.p,
+                          (int4*)ctx->b_wlsorted.p, B))) return rc;
+        // the lane kernel whatever the option PNL_WL_LANE says, and with it nmin: a difference from the other two paths that is kept, not decided
+        if ((rc = worklist_eval<DIM, DPE, KT, false>(ctx, "PNL_WL_CL_KB", 18, (const int4*)ctx->b_wlsorted.p, B, nullptr, 0, nullptr, SparseOut{},
+                                                     CT, PNL_WL_BINS-1, PNL_WL_LANE_MAXPTS+1, true, 0))) return rc;
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
@@ -1376,27 +1333,11 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
         if (!ctx->C().have_sing[0][s]) return fail(ctx, PNL_ERR_STATE, "singular rule for %d common vertices not uploaded", s+1);
         ClusterTiles C2 = CT;
         C2.sing_pair = sing_pair_dev[s];
-        const int M = ctx->P.sM[s], rows = ctx->P.sRows[s];
-        const size_t slds = sizeof(double)*(size_t)(2*(DIM+1)+1+rows)*M;
         const int wpb = PNL_SING_THREADS/64;
-        const bool stage = slds <= 150*1024;
-        const int per_cu = stage ? std::max(1, (int)((160*1024)/std::max<size_t>(slds, 1))) : 4;
-        const int grid = std::min((np+wpb-1)/wpb, 256*std::min(per_cu, 4));
-#define PNL_LAUNCH_SING(SLOT)                                                                                                          \
-        if (stage) {                                                                                                                   \
-            auto kf = k_singular_pairs<DIM, DPE, SLOT, KT, true, false>;                                                               \
-            HIPCHK(ctx, hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));                 \
-            hipLaunchKernelGGL(kf, dim3(grid), dim3(PNL_SING_THREADS), slds, ctx->stream, ctx->P, sing_dev[s], np, (double*)nullptr, 0ll, \
-                               0, ctx->nc, SparseOut{}, (const int4*)nullptr, (const unsigned*)nullptr, C2);                          \
-        } else                                                                                                                         \
-            hipLaunchKernelGGL((k_singular_pairs<DIM, DPE, SLOT, KT, false, false>), dim3(grid), dim3(PNL_SING_THREADS), 0, ctx->stream, \
-                               ctx->P, sing_dev[s], np, (double*)nullptr, 0ll, 0, ctx->nc, SparseOut{}, (const int4*)nullptr,          \
-                               (const unsigned*)nullptr, C2);
-        if (s == 0) { PNL_LAUNCH_SING(0) }
-        else if (s == 1) { PNL_LAUNCH_SING(1) }
-        else { PNL_LAUNCH_SING((DIM == 2 ? 2 : 1)) }
-#undef PNL_LAUNCH_SING
-        HIPCHK(ctx, hipGetLastError());
+        if ((rc = with_slot<DIM>(s, [&](auto slot) {
+                return launch_singular_pairs<DIM, DPE, decltype(slot)::value, KT, false>(ctx, (np+wpb-1)/wpb, sing_dev[s], np, nullptr, 0, 0, ctx->nc,
+                                                                                         SparseOut{}, nullptr, nullptr, C2);
+            }))) return rc;
     }
     if (overlap) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
@@ -1423,34 +1364,28 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
             dcount = (unsigned*)((int*)(dslots+cap)+cap);
             HIPCHK(ctx, hipMemsetAsync(dcount, 0, sizeof(unsigned), ctx->stream));
         }
-        if (ctx->P.bkn.fast)
-            hipLaunchKernelGGL((k_cluster_boundary<DIM, DPE, 1>), grid, dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, d_cell, d_pair,
-                               pl->num_dslots, pair_foff, fvid, fgeo, pl->nfacets, CT.D, per, defer, dcells, dfacets, dslots, dcount, cap);
-        else
-            hipLaunchKernelGGL((k_cluster_boundary<DIM, DPE, 0>), grid, dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, d_cell, d_pair,
-                               pl->num_dslots, pair_foff, fvid, fgeo, pl->nfacets, CT.D, per, defer, dcells, dfacets, dslots, dcount, cap);
+        // items of k_boundary_items, one per wave: the deferred pairs (count on the device) and the touching (cell, facet) pairs
+        auto items = [&](auto kt, int g, const int *cells, const int *facets, const unsigned *slots, int n, const unsigned *count) {
+            hipLaunchKernelGGL((k_boundary_items<DIM, DPE, decltype(kt)::value>), dim3(g), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, cells,
+                               facets, slots, n, 1., SparseOut{}, CT.D, count, (const int*)nullptr, (const DevKernel*)nullptr, (const DevFormula*)nullptr);
+        };
+        with_kt(ctx->P.bkn.fast, [&](auto kt) {
+            hipLaunchKernelGGL((k_cluster_boundary<DIM, DPE, decltype(kt)::value>), grid, dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, d_cell,
+                               d_pair, pl->num_dslots, pair_foff, fvid, fgeo, pl->nfacets, CT.D, per, defer, dcells, dfacets, dslots, dcount, cap);
+            return PNL_OK;
+        });
         HIPCHK(ctx, hipGetLastError());
         if (cap) {
-            if (ctx->P.bkn.fast)
-                hipLaunchKernelGGL((k_boundary_items<DIM, DPE, 1>), dim3(256*8), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts,
-                                   (const int*)dcells, (const int*)dfacets, (const unsigned*)dslots, (int)cap, 1., SparseOut{}, CT.D,
-                                   (const unsigned*)dcount, (const int*)nullptr, (const DevKernel*)nullptr, (const DevFormula*)nullptr);
-            else
-                hipLaunchKernelGGL((k_boundary_items<DIM, DPE, 0>), dim3(256*8), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts,
-                                   (const int*)dcells, (const int*)dfacets, (const unsigned*)dslots, (int)cap, 1., SparseOut{}, CT.D,
-                                   (const unsigned*)dcount, (const int*)nullptr, (const DevKernel*)nullptr, (const DevFormula*)nullptr);
+            with_kt(ctx->P.bkn.fast, [&](auto kt) { items(kt, 256*8, dcells, dfacets, dslots, (int)cap, dcount); return PNL_OK; });
             HIPCHK(ctx, hipGetLastError());
         }
         if (pl->n_btouch > 0) {
             for (int s = 0; s < DIM; s++)
                 if (!ctx->C().have_sing[1][s]) return fail(ctx, PNL_ERR_STATE, "boundary singular rule for %d common vertices not uploaded", s+1);
-            const int g2 = std::min((pl->n_btouch+3)/4, 256*8);
-            if (ctx->P.bkn.fast)
-                hipLaunchKernelGGL((k_boundary_items<DIM, DPE, 1>), dim3(g2), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, bt_cell,
-                                   bt_facet, bt_slot, pl->n_btouch, 1., SparseOut{}, CT.D, (const unsigned*)nullptr, (const int*)nullptr, (const DevKernel*)nullptr, (const DevFormula*)nullptr);
-            else
-                hipLaunchKernelGGL((k_boundary_items<DIM, DPE, 0>), dim3(g2), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, bt_cell,
-                                   bt_facet, bt_slot, pl->n_btouch, 1., SparseOut{}, CT.D, (const unsigned*)nullptr, (const int*)nullptr, (const DevKernel*)nullptr, (const DevFormula*)nullptr);
+            with_kt(ctx->P.bkn.fast, [&](auto kt) {
+                items(kt, std::min((pl->n_btouch+3)/4, 256*8), bt_cell, bt_facet, bt_slot, pl->n_btouch, nullptr);
+                return PNL_OK;
+            });
             HIPCHK(ctx, hipGetLastError());
         }
     }
@@ -1713,11 +1648,9 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
         const size_t lds = sizeof(double)*(64*NP*DIM+2*64*NP+64+2*64*ND)+sizeof(int)*(64*DPE+64)
                            +2*sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
         auto tfun = k_pw_tile<DIM>;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)tfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)tfun, PNL_NTHREADS, lds);
-        const int grid = pnl_grid_cap(std::min((int)uniform.size(), 256*std::max(per_cu, 1)));
-        hipLaunchKernelGGL(tfun, dim3(grid), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int2*)ctx->b_tiles.p+mixed.size(),
+        const PersistentGrid g = persistent_grid(ctx, tfun, PNL_NTHREADS, lds, (int)uniform.size(), 1);
+        if (g.rc) return g.rc;
+        hipLaunchKernelGGL(tfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int2*)ctx->b_tiles.p+mixed.size(),
                            (int)uniform.size(), A, (long long)ldA, (double*)ctx->b_D.p, acc_stride);
         HIPCHK(ctx, hipGetLastError());
         ctx->pure_launched = true;
@@ -1731,13 +1664,11 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
                            +sizeof(int)*(3*PNL_PW_NBUCK+2*64*DPE)+2*sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
         if (lds > 160*1024) return fail(ctx, PNL_ERR_UNSUPPORTED, "a block of 64 cells touches %d DoFs: LDS sub-blocks of %zu bytes exceed 160 KiB", ctx->nU, lds);
         auto mfun = k_pw_mixed<DIM>;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)mfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)mfun, PNL_NTHREADS, lds);
-        const int grid = pnl_grid_cap(std::min((int)mixed.size(), 256*std::max(per_cu, 1)));
+        const PersistentGrid g = persistent_grid(ctx, mfun, PNL_NTHREADS, lds, (int)mixed.size(), 1);
+        if (g.rc) return g.rc;
         if ((rc = ensure(ctx, ctx->b_tilectr, sizeof(unsigned)))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
-        hipLaunchKernelGGL(mfun, dim3(grid), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int2*)ctx->b_tiles.p, (int)mixed.size(), A,
+        hipLaunchKernelGGL(mfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int2*)ctx->b_tiles.p, (int)mixed.size(), A,
                            (long long)ldA, (double*)ctx->b_D.p, acc_stride, (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, ctx->wl_cap,
                            cell_begin, cell_end, (unsigned*)ctx->b_tilectr.p);
     }
@@ -1747,15 +1678,10 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     {
-        unsigned *hist = (unsigned*)ctx->b_wlaux.p, *offs = hist+(PNL_WL_BINS+1), *coff = offs+(PNL_WL_BINS+1), *cursor = coff+(PNL_WL_BINS+1);
-        HIPCHK(ctx, hipMemsetAsync(hist, 0, sizeof(unsigned)*(PNL_WL_BINS+1), ctx->stream));
-        const int4 *wl = (const int4*)ctx->b_wl.p;
-        const unsigned *wlc = (const unsigned*)ctx->b_wlcount.p;
-        hipLaunchKernelGGL(k_wl_hist, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, wlc, ctx->wl_cap, hist);
-        hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(64), 0, ctx->stream, (const unsigned*)hist, offs, coff, cursor);
-        hipLaunchKernelGGL(k_wl_scatter, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, wlc, ctx->wl_cap, (const unsigned*)offs, cursor,
-                           (int4*)ctx->b_wlsorted.p);
-        hipLaunchKernelGGL(k_pw_stats, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, P, (const unsigned*)hist);
+        WlBins B;
+        if ((rc = wl_sort(ctx, (const int4*)ctx->b_wl.p, (const unsigned*)ctx->b_wlcount.p, ctx->wl_cap, (unsigned*)ctx->b_wlaux.p,
+                          (int4*)ctx->b_wlsorted.p, B))) return rc;
+        hipLaunchKernelGGL(k_pw_stats, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, P, (const unsigned*)B.hist);
         // LDS: rule table + order / scaling of the second cell's points for the 16 pairs of a chunk
         const int tab_max = 256;
         const size_t lds = sizeof(double)*((size_t)tab_max*ST+(size_t)(PNL_NTHREADS/16)*tab_max*2);
@@ -1764,9 +1690,9 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
         const bool lane_kernel = P1 && !pnl_tune("PNL_PW_NOLANE");      // (with the in-tile evaluation only the rules of more than 16 points arrive here)
         if constexpr (P1el) if (lane_kernel)
             hipLaunchKernelGGL((k_pw_lane<DIM>), dim3(256*2), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, (const int4*)ctx->b_wlsorted.p,
-                               (const unsigned*)offs, A, (long long)ldA, (double*)ctx->b_D.p);
+                               (const unsigned*)B.offs, A, (long long)ldA, (double*)ctx->b_D.p);
         hipLaunchKernelGGL(kfun, dim3(256*4), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int4*)ctx->b_wlsorted.p,
-                           (const unsigned*)offs, A, (long long)ldA, (double*)ctx->b_D.p, tab_max, lane_kernel ? PNL_PW_LANE_MAXPTS+1 : 0, PwNear{});
+                           (const unsigned*)B.offs, A, (long long)ldA, (double*)ctx->b_D.p, tab_max, lane_kernel ? PNL_PW_LANE_MAXPTS+1 : 0, PwNear{});
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
@@ -1797,12 +1723,8 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    {
-        const long long nt = (long long)ctx->nc*DPE*DPE;
-        hipLaunchKernelGGL((k_scatter_diag<DPE>), dim3((unsigned)((nt+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0,
-                           ctx->stream, P, (const double*)ctx->b_D.p, A, (long long)ldA);
-        HIPCHK(ctx, hipGetLastError());
-    }
+    scatter_diag<DPE>(ctx, P, (const double*)ctx->b_D.p, A, ldA);
+    HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
     ctx->ev_valid = true;
     return PNL_OK;
@@ -1859,9 +1781,8 @@ int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
         if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
         if (use_tiles) {
             auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false, true>;
-            HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            int per_cu = 2;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kfun, tile_threads(DPE, KT, true), lds);
+            const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT, true), lds, nt, 2);
+            if (g.rc) return g.rc;
             if ((rc = ensure(ctx, ctx->b_tilectr, sizeof(unsigned)))) return rc;
             HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
             HIPCHK(ctx, hipMemsetAsync(ctx->b_D.p, 0, sizeof(double)*(size_t)ctx->ncp*ND, ctx->stream));
@@ -1870,8 +1791,7 @@ int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
             CT.wl_ds = (int2*)ctx->b_mp_pairs.p;                   // the pairs of the far-list entries
             SlotOut SOk{};
             SOk.nU = ctx->nU;                                      // rows of the LDS sub-block
-            const int grid = pnl_grid_cap(std::min(nt, 256*std::max(per_cu, 1)));
-            hipLaunchKernelGGL(kfun, dim3(grid), dim3(tile_threads(DPE, KT, true)), lds, ctx->stream, ctx->P, (const int2*)ctx->b_tiles.p+t0,
+            hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT, true)), lds, ctx->stream, ctx->P, (const int2*)ctx->b_tiles.p+t0,
                                (double*)nullptr, 0ll, (double*)ctx->b_D.p, std::max(cell_begin, 0), std::min(cell_end, ctx->nc), acc_stride, (int4*)ctx->b_mp_wl.p,
                                (unsigned*)ctx->b_wlcount.p, (unsigned)cap, 0, nt, CT, (unsigned*)ctx->b_tilectr.p, SOk);
         } else
@@ -1897,19 +1817,13 @@ int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
         if (np && (rc = pairs_masked_impl<DIM, DPE, KT>(ctx, (int)np, S, false, false, use_tiles))) return rc;
         if (!np && use_tiles) {
             // no far entries in this chunk: the diagonal blocks of its tiles still have to reach the matrix
-            const long long n = (long long)ctx->nc*ND;
-            hipLaunchKernelGGL((k_scatter_diag_sparse<DPE>), dim3((unsigned)((n+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0,
-                               ctx->stream, ctx->P, (const double*)ctx->b_D.p, ctx->nc, S);
-            for (int e = 1; e < 8; e++) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
-            ctx->ev_valid = true; ctx->tiles_launched = true;
+            scatter_diag_sparse<DPE>(ctx, (const double*)ctx->b_D.p, S);
+            if ((rc = finish_events(ctx, 1))) return rc;
         }
         first = false;
     }
     ctx->visited_pairs = total;
-    if (total == 0) {
-        for (int e = 1; e < 8; e++) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
-        ctx->ev_valid = true; ctx->tiles_launched = true;
-    }
+    if (total == 0 && (rc = finish_events(ctx, 1))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));     // pnl_get_counters reads it as the dense work-list fill
     return PNL_OK;
 }
@@ -2755,14 +2669,13 @@ int pnl_assemble_pairs_masked(pnl_context *ctx, int np, const int32_t *pairs, co
         const int k = ko/norient;
         ctx->orient = ko%norient;
         if (ctx->nlab > 0) { ctx->cur = k; refresh_tables(ctx); }
-        const int kt = ctx->P.k.fast ? 1 : 0;
-        const bool first = ko == 0;
+        const bool fast = ctx->P.k.fast != 0, first = ko == 0;
         if (ctx->dim == 2 && ctx->dpe == 3)
-            rc = kt ? pairs_masked_impl<2, 3, 1>(ctx, np, S, true, first) : pairs_masked_impl<2, 3, 0>(ctx, np, S, true, first);
+            rc = with_kt(fast, [&](auto kt) { return pairs_masked_impl<2, 3, decltype(kt)::value>(ctx, np, S, true, first); });
         else if (ctx->dim == 2 && ctx->dpe == 6)
-            rc = kt ? pairs_masked_impl<2, 6, 1>(ctx, np, S, true, first) : pairs_masked_impl<2, 6, 0>(ctx, np, S, true, first);
+            rc = with_kt(fast, [&](auto kt) { return pairs_masked_impl<2, 6, decltype(kt)::value>(ctx, np, S, true, first); });
         else if (ctx->dim == 2 && ctx->dpe == 1)
-            rc = kt ? pairs_masked_impl<2, 1, 1>(ctx, np, S, true, first) : pairs_masked_impl<2, 1, 0>(ctx, np, S, true, first);
+            rc = with_kt(fast, [&](auto kt) { return pairs_masked_impl<2, 1, decltype(kt)::value>(ctx, np, S, true, first); });
         else if (ctx->dim == 1 && ctx->dpe == 2) rc = pairs_masked_impl<1, 2, 0>(ctx, np, S, true, first);
         else if (ctx->dim == 1 && ctx->dpe == 1) rc = pairs_masked_impl<1, 1, 0>(ctx, np, S, true, first);
         else if (ctx->dim == 1 && ctx->dpe == 3) rc = pairs_masked_impl<1, 3, 0>(ctx, np, S, true, first);
@@ -2793,10 +2706,10 @@ int pnl_assemble_pairs_in_horizon_range(pnl_context *ctx, double *data, double *
     SparseOut S;
     if ((rc = sparse_ready(ctx, data, diag, S))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
-    const int kt = ctx->P.k.fast ? 1 : 0;
-    if (ctx->dim == 2 && ctx->dpe == 3) return kt ? horizon_impl<2, 3, 1>(ctx, S, cell_begin, cell_end) : horizon_impl<2, 3, 0>(ctx, S, cell_begin, cell_end);
-    if (ctx->dim == 2 && ctx->dpe == 6) return kt ? horizon_impl<2, 6, 1>(ctx, S, cell_begin, cell_end) : horizon_impl<2, 6, 0>(ctx, S, cell_begin, cell_end);
-    if (ctx->dim == 2 && ctx->dpe == 1) return kt ? horizon_impl<2, 1, 1>(ctx, S, cell_begin, cell_end) : horizon_impl<2, 1, 0>(ctx, S, cell_begin, cell_end);
+    const bool fast = ctx->P.k.fast != 0;
+    if (ctx->dim == 2 && ctx->dpe == 3) return with_kt(fast, [&](auto kt) { return horizon_impl<2, 3, decltype(kt)::value>(ctx, S, cell_begin, cell_end); });
+    if (ctx->dim == 2 && ctx->dpe == 6) return with_kt(fast, [&](auto kt) { return horizon_impl<2, 6, decltype(kt)::value>(ctx, S, cell_begin, cell_end); });
+    if (ctx->dim == 2 && ctx->dpe == 1) return with_kt(fast, [&](auto kt) { return horizon_impl<2, 1, decltype(kt)::value>(ctx, S, cell_begin, cell_end); });
     if (ctx->dim == 1 && ctx->dpe == 2) return horizon_impl<1, 2, 0>(ctx, S, cell_begin, cell_end);
     if (ctx->dim == 1 && ctx->dpe == 1) return horizon_impl<1, 1, 0>(ctx, S, cell_begin, cell_end);
     if (ctx->dim == 1 && ctx->dpe == 3) return horizon_impl<1, 3, 0>(ctx, S, cell_begin, cell_end);
@@ -2936,21 +2849,16 @@ int pnl_assemble_clusters_tiled(pnl_context *ctx, const pnl_cluster_plan *pl, in
     if ((rc = ensure(ctx, ctx->b_cpD, sizeof(double)*(size_t)std::max(pl->num_dslots, 1)*(dpe*(dpe+1)/2)))) return rc;
     CT.D = (double*)ctx->b_cpD.p;
     ctx->visited_pairs = 0; ctx->visited_is_assembled = false;
-    const bool kt = ctx->P.k.fast;
-    if (dim == 2 && dpe == 3)
-        return kt ? clusters_tiled_impl<2, 3, TILE_P1, 1>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot)
-                  : clusters_tiled_impl<2, 3, TILE_P1, 0>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot);
-    if (dim == 2 && dpe == 6)
-        return kt ? clusters_tiled_impl<2, 6, TILE_P2, 1>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot)
-                  : clusters_tiled_impl<2, 6, TILE_P2, 0>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot);
-    if (dim == 1 && dpe == 2)
-        return kt ? clusters_tiled_impl<1, 2, TILE_P1, 1>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot)
-                  : clusters_tiled_impl<1, 2, TILE_P1, 0>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot);
-    // P0 (intervals and triangles), P2 and P3 on intervals
+    // triangles P1, P2, intervals P1; P0 (intervals and triangles), P2 and P3 on intervals
 #define PNL_CT(D_, E_, T_) \
     if (dim == D_ && dpe == E_) \
-        return kt ? clusters_tiled_impl<D_, E_, T_, 1>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot) \
-                  : clusters_tiled_impl<D_, E_, T_, 0>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot);
+        return with_kt(ctx->P.k.fast, [&](auto kt) { \
+            return clusters_tiled_impl<D_, E_, T_, decltype(kt)::value>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, \
+                                                                        pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot); \
+        });
+    PNL_CT(2, 3, TILE_P1)
+    PNL_CT(2, 6, TILE_P2)
+    PNL_CT(1, 2, TILE_P1)
     PNL_CT(2, 1, TILE_P1)
     PNL_CT(1, 1, TILE_P1)
     PNL_CT(1, 3, TILE_P2)
@@ -3102,20 +3010,28 @@ int pnl_h2_setup(pnl_context *ctx, const pnl_h2_plan *pl) {
     return PNL_OK;
 }
 
-int pnl_h2_matvec(pnl_context *ctx, const double *x, double *y) {
-    if (!ctx || !x || !y) return PNL_ERR_INVALID;
-    if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
-    const H2Dev &H = ctx->h2;
+// the three phases of the H2 matvec on the coefficient arrays H.cup / H.cdown (the context's own, or the caller's)
+static int h2_upward(pnl_context *ctx, const H2Dev &H, const double *x) {
     const int nlev = (int)ctx->h2_levels.size();
     const int *lev = (const int*)ctx->b_h2[17].p;
     HIPCHK(ctx, hipMemsetAsync(H.cup, 0, sizeof(double)*(size_t)H.nnodes*H.M, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(H.cdown, 0, sizeof(double)*(size_t)H.nnodes*H.M, ctx->stream));
     hipLaunchKernelGGL(k_h2_up_leaves, dim3(H.nleaves), dim3(64), 0, ctx->stream, H, x);
     for (int l = nlev-1; l >= 1; l--) {
         const int n = (int)ctx->h2_levels[l].size();
         if (n) hipLaunchKernelGGL(k_h2_up_level, dim3(n), dim3(64), 0, ctx->stream, H, lev+ctx->h2_level_off[l], n);
     }
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+static int h2_interact(pnl_context *ctx, const H2Dev &H) {
+    HIPCHK(ctx, hipMemsetAsync(H.cdown, 0, sizeof(double)*(size_t)H.nnodes*H.M, ctx->stream));
     if (H.nfar) hipLaunchKernelGGL(k_h2_far, dim3(H.nfar), dim3(64), 0, ctx->stream, H);
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+static int h2_downward(pnl_context *ctx, const H2Dev &H, double *y) {
+    const int nlev = (int)ctx->h2_levels.size();
+    const int *lev = (const int*)ctx->b_h2[17].p;
     for (int l = 1; l < nlev; l++) {
         const int n = (int)ctx->h2_levels[l].size();
         if (n) hipLaunchKernelGGL(k_h2_down_level, dim3(n), dim3(64), 0, ctx->stream, H, lev+ctx->h2_level_off[l], n);
@@ -3123,6 +3039,14 @@ int pnl_h2_matvec(pnl_context *ctx, const double *x, double *y) {
     hipLaunchKernelGGL(k_h2_down_leaves, dim3(H.nleaves), dim3(64), 0, ctx->stream, H, y);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
+}
+
+int pnl_h2_matvec(pnl_context *ctx, const double *x, double *y) {
+    if (!ctx || !x || !y) return PNL_ERR_INVALID;
+    if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
+    int rc;
+    if ((rc = h2_upward(ctx, ctx->h2, x)) || (rc = h2_interact(ctx, ctx->h2))) return rc;
+    return h2_downward(ctx, ctx->h2, y);
 }
 
 // kernel interpolants K[nfar][M][M] (which = 0) and leaf values V (which = 1: the blocks V_leaf[ndofs][M] of the plan's leaves, one
@@ -3154,16 +3078,7 @@ int pnl_h2_upward(pnl_context *ctx, const double *x, double *cup) {
     if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
     H2Dev H = ctx->h2;
     H.cup = cup;
-    const int nlev = (int)ctx->h2_levels.size();
-    const int *lev = (const int*)ctx->b_h2[17].p;
-    HIPCHK(ctx, hipMemsetAsync(cup, 0, sizeof(double)*(size_t)H.nnodes*H.M, ctx->stream));
-    hipLaunchKernelGGL(k_h2_up_leaves, dim3(H.nleaves), dim3(64), 0, ctx->stream, H, x);
-    for (int l = nlev-1; l >= 1; l--) {
-        const int n = (int)ctx->h2_levels[l].size();
-        if (n) hipLaunchKernelGGL(k_h2_up_level, dim3(n), dim3(64), 0, ctx->stream, H, lev+ctx->h2_level_off[l], n);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
+    return h2_upward(ctx, H, x);
 }
 
 int pnl_h2_interact(pnl_context *ctx, const double *cup, double *cdown) {
@@ -3171,10 +3086,7 @@ int pnl_h2_interact(pnl_context *ctx, const double *cup, double *cdown) {
     if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
     H2Dev H = ctx->h2;
     H.cup = const_cast<double*>(cup); H.cdown = cdown;
-    HIPCHK(ctx, hipMemsetAsync(cdown, 0, sizeof(double)*(size_t)H.nnodes*H.M, ctx->stream));
-    if (H.nfar) hipLaunchKernelGGL(k_h2_far, dim3(H.nfar), dim3(64), 0, ctx->stream, H);
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
+    return h2_interact(ctx, H);
 }
 
 int pnl_h2_downward(pnl_context *ctx, double *cdown, double *y) {
@@ -3182,15 +3094,7 @@ int pnl_h2_downward(pnl_context *ctx, double *cdown, double *y) {
     if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
     H2Dev H = ctx->h2;
     H.cdown = cdown;
-    const int nlev = (int)ctx->h2_levels.size();
-    const int *lev = (const int*)ctx->b_h2[17].p;
-    for (int l = 1; l < nlev; l++) {
-        const int n = (int)ctx->h2_levels[l].size();
-        if (n) hipLaunchKernelGGL(k_h2_down_level, dim3(n), dim3(64), 0, ctx->stream, H, lev+ctx->h2_level_off[l], n);
-    }
-    hipLaunchKernelGGL(k_h2_down_leaves, dim3(H.nleaves), dim3(64), 0, ctx->stream, H, y);
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
+    return h2_downward(ctx, H, y);
 }
 
 int pnl_spmv(pnl_context *ctx, const double *data, const double *diag, const double *x, double *y) {

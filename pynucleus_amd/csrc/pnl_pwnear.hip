@@ -8,6 +8,7 @@
 namespace {
 #include "pnl_pointwise.h"
 }
+#include "pnl_launch.h"
 
 namespace {
 
@@ -48,20 +49,15 @@ int pairs_near_impl(pnl_context *ctx, int np, int nt, int nd, const PwNear &NR) 
         hipLaunchKernelGGL((k_pw_classify_near<DIM, DPE>), dim3((nd+PNL_NTHREADS-1)/PNL_NTHREADS), dim3(PNL_NTHREADS), 0, ctx->stream, P, W,
                            (const int*)ctx->b_mp_pairs.p, (const int*)ctx->b_mp_sorted.p, nd, (int4*)ctx->b_wl.p,
                            (unsigned*)ctx->b_wlcount.p, ctx->wl_cap);
-        unsigned *hist = (unsigned*)ctx->b_wlaux.p, *offs = hist+(PNL_WL_BINS+1), *coff = offs+(PNL_WL_BINS+1), *cursor = coff+(PNL_WL_BINS+1);
-        HIPCHK(ctx, hipMemsetAsync(hist, 0, sizeof(unsigned)*(PNL_WL_BINS+1), ctx->stream));
-        const int4 *wl = (const int4*)ctx->b_wl.p;
-        const unsigned *wlc = (const unsigned*)ctx->b_wlcount.p;
-        hipLaunchKernelGGL(k_wl_hist, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, wlc, ctx->wl_cap, hist);
-        hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(64), 0, ctx->stream, (const unsigned*)hist, offs, coff, cursor);
-        hipLaunchKernelGGL(k_wl_scatter, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, wlc, ctx->wl_cap, (const unsigned*)offs, cursor,
-                           (int4*)ctx->b_wlsorted.p);
-        hipLaunchKernelGGL(k_pw_stats_near, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, P, (const unsigned*)hist);
+        WlBins B;
+        if ((rc = wl_sort(ctx, (const int4*)ctx->b_wl.p, (const unsigned*)ctx->b_wlcount.p, ctx->wl_cap, (unsigned*)ctx->b_wlaux.p,
+                          (int4*)ctx->b_wlsorted.p, B))) return rc;
+        hipLaunchKernelGGL(k_pw_stats_near, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, P, (const unsigned*)B.hist);
         const int tab_max = 256;
         const size_t lds = sizeof(double)*((size_t)tab_max*ST+(size_t)(PNL_NTHREADS/16)*tab_max*2);
         auto kfun = k_pw_distant<DIM, DPE, true>;
         HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kfun, dim3(256*4), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int4*)ctx->b_wlsorted.p, (const unsigned*)offs,
+        hipLaunchKernelGGL(kfun, dim3(256*4), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int4*)ctx->b_wlsorted.p, (const unsigned*)B.offs,
                            (double*)nullptr, 0ll, (double*)nullptr, tab_max, 0, NR);
         HIPCHK(ctx, hipGetLastError());
     }
