@@ -310,6 +310,10 @@ inline void kt_end(pnl_context *ctx, int slot) { (void)hipEventRecord(ctx->kev[s
 // pnl_hip.hip: joins the vertex-order search finalize() started and uploads the permuted cell tables (sets have_tile_order)
 int pnl_tile_order_ready(pnl_context *ctx);
 
+// pnl_hip.hip: what pnl_h2_setup (pnl_h2.hip) shares with the assemblies of a constant or piecewise constant order -- kernels, order
+// formulas and rules are set, the tables derived from mesh and DoF map exist (finalize), the problem description holds the current class
+int pnl_assembly_prepare(pnl_context *ctx);
+
 // pnl_hip.hip / pnl_pwnear.hip: kernels with an order per quadrature point
 int pnl_pw_prepare(pnl_context *ctx, int need_boundary);
 int pnl_pw_h2_interp(pnl_context *ctx);

@@ -95,11 +95,11 @@ __device__ __forceinline__ long long pnl_row(const DevProblem &P, int I) { retur
 // ... and the column of global DoF J (the columns of a rank's slab are the DoFs of its cells and of all later cells)
 __device__ __forceinline__ int pnl_col(const DevProblem &P, int J) { return P.colmap ? P.colmap[J] : J; }
 
-// H2 far field (clusterMethodCy.pyx; kernels in pnl_kernels.h)
 // copy table of k_fold_mirror (pnl_tile2.h): storage offset of the copy's row, block << 5 | local DoF, slot column
 #define PNL_FOLD_TAB 63
 struct FoldEntry { long long off; int ar, cy; };
 
+// H2 far field (clusterMethodCy.pyx; kernels in pnl_h2.hip, k_h2_kernel_interp_pw in pnl_pointwise.h)
 struct H2Dev {
     int dim, m, M, nnodes, nleaves, nfar;
     const double *box;          // [nnodes][dim][2]
@@ -113,6 +113,23 @@ struct H2Dev {
     const double *T;            // [nnodes][M_parent][M_child] transfer operator of every non-root node
     double *cup, *cdown;        // [nnodes][M]
 };
+
+// j-th Chebyshev node of [a, b]: eta_j = cos((2 (m-j) - 1) pi / (2m)) (clusterMethodCy.pyx:2173, 1255)
+__device__ __forceinline__ double cheb_node(double a, double b, int m, int j) {
+    return (b-a)*0.5*(cos((2.0*(m-j)-1.0)/(2.0*m)*3.14159265358979323846)+1.0)+a;
+}
+
+// 1D Lagrange polynomial l on the Chebyshev nodes of [a, b] at x
+__device__ __forceinline__ double lagrange1d(double a, double b, int m, int l, double x) {
+    const double xl = cheb_node(a, b, m, l);
+    double v = 1.;
+    for (int k = 0; k < m; k++)
+        if (k != l) {
+            const double xk = cheb_node(a, b, m, k);
+            v *= (x-xk)/(xl-xk);
+        }
+    return v;
+}
 
 // order per quadrature point (kernels in pnl_pointwise.h)
 struct PwDev {

@@ -1422,110 +1422,21 @@ int dispatch(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, int nt
             return fail(ctx, PNL_ERR_UNSUPPORTED, "finite-horizon kernels are assembled from an explicit pair list (pnl_assemble_pairs_masked, "
                         "nonlocalBuilder.getSparse): the all-pairs dense loop has no REMOTE / CUT handling");
     refresh_tables(ctx);
-    if (ctx->dim == 2 && ctx->dpe == 3) return assemble_impl<2, 3, TILE_P1>(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
-    if (ctx->dim == 2 && ctx->dpe == 6) return assemble_impl<2, 6, TILE_P2>(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
-    if (ctx->dim == 1 && ctx->dpe == 2) return assemble_impl<1, 2, TILE_P1>(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
-    if (ctx->dim == 1 && ctx->dpe == 3) return assemble_impl<1, 3, TILE_P2>(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
-    // P0 and P3 on intervals (the reference's fixtures --elementP0 / --elementP3; FL1 is generic in the DoFs per element)
-    if (ctx->dim == 2 && ctx->dpe == 1) return assemble_impl<2, 1, TILE_P1>(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
-    if (ctx->dim == 1 && ctx->dpe == 1) return assemble_impl<1, 1, TILE_P1>(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
-    if (ctx->dim == 1 && ctx->dpe == 4) return assemble_impl<1, 4, TILE_P2>(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
-    return fail(ctx, PNL_ERR_UNSUPPORTED, "unsupported (dim=%d, dofs_per_element=%d)", ctx->dim, ctx->dpe);
-}
-
-// ---- GEMV / CG kernels ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_gemv(const double *__restrict__ A, long long ldA, int n, const double *__restrict__ x, double *__restrict__ y) {
-    // one wave per row; 16 B per lane per load
-    const int lane = threadIdx.x & 63;
-    const int row = (blockIdx.x*PNL_NTHREADS+threadIdx.x) >> 6;
-    if (row >= n) return;
-    const double *__restrict__ a = A+(long long)row*ldA;
-    double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
-    // 16-byte loads need both the row and x aligned (x may be a storage-offset view); four of them per lane in flight
-    // (6.0 TB/s at n = 48,769 against 5.4 with one)
-    const bool aligned = ((((uintptr_t)a) | ((uintptr_t)x)) & 15) == 0;
-    if (aligned) {
-        const int n2 = n >> 1;
-        const double2 *a2 = (const double2*)a;
-        const double2 *x2 = (const double2*)x;
-        int j = lane;
-        for (; j+192 < n2; j += 256) {
-            const double2 v0 = a2[j], v1 = a2[j+64], v2 = a2[j+128], v3 = a2[j+192];
-            const double2 w0 = x2[j], w1 = x2[j+64], w2 = x2[j+128], w3 = x2[j+192];
-            s0 = __builtin_fma(v0.x, w0.x, s0); s1 = __builtin_fma(v0.y, w0.y, s1);
-            s2 = __builtin_fma(v1.x, w1.x, s2); s3 = __builtin_fma(v1.y, w1.y, s3);
-            s0 = __builtin_fma(v2.x, w2.x, s0); s1 = __builtin_fma(v2.y, w2.y, s1);
-            s2 = __builtin_fma(v3.x, w3.x, s2); s3 = __builtin_fma(v3.y, w3.y, s3);
-        }
-        for (; j < n2; j += 64) {
-            const double2 av = a2[j], xv = x2[j];
-            s0 = __builtin_fma(av.x, xv.x, s0);
-            s1 = __builtin_fma(av.y, xv.y, s1);
-        }
-        if ((n & 1) && lane == 0) s0 = __builtin_fma(a[n-1], x[n-1], s0);
-    } else {
-        for (int j = lane; j < n; j += 64) s0 = __builtin_fma(a[j], x[j], s0);
-    }
-    const double s = wave_sum((s0+s1)+(s2+s3));
-    if (lane == 0) y[row] = s;
-}
-
-// y += (A^T) x contribution for the one-sided storage: each wave takes a row I and adds A[I,J] x_I to y_J
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_gemv_t_add(const double *__restrict__ A, long long ldA, int n, const double *__restrict__ x, double *__restrict__ y,
-             int rows_per_block) {
-    // block handles rows [r0, r1): lane-owned column sums, then one atomic per column
-    const int r0 = blockIdx.y*rows_per_block, r1 = min(n, r0+rows_per_block);
-    const int j = blockIdx.x*PNL_NTHREADS+threadIdx.x;
-    if (j >= n) return;
-    double s = 0.;
-    for (int r = r0; r < r1; r++) s = __builtin_fma(A[(long long)r*ldA+j], x[r], s);
-    if (s != 0.) atomic_add_f64(&y[j], s);
-}
-
-__global__ void __launch_bounds__(PNL_NTHREADS) k_dot(const double *__restrict__ a, const double *__restrict__ b, int n, double *out) {
-    double s = 0.;
-    for (int i = blockIdx.x*PNL_NTHREADS+threadIdx.x; i < n; i += gridDim.x*PNL_NTHREADS) s = __builtin_fma(a[i], b[i], s);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) atomic_add_f64(out, s);
-}
-
-__global__ void __launch_bounds__(PNL_NTHREADS) k_diag_inv(const double *__restrict__ A, long long ldA, int n, double *__restrict__ dinv) {
-    const int i = blockIdx.x*PNL_NTHREADS+threadIdx.x;
-    if (i < n) dinv[i] = 1./A[(long long)i*ldA+i];
-}
-
-// r = b - Ax given Ax in t ; z = dinv*r ; p = z
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_cg_init(const double *__restrict__ b, const double *__restrict__ Ax, const double *__restrict__ dinv, int n, double *r, double *p) {
-    const int i = blockIdx.x*PNL_NTHREADS+threadIdx.x;
-    if (i < n) { const double ri = b[i]-Ax[i]; r[i] = ri; p[i] = dinv[i]*ri; }
-}
-
-// x += alpha p ; r -= alpha Ap ; z = dinv r   (alpha = scal[0]/scal[1])
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_cg_update(const double *__restrict__ scal, const double *__restrict__ p, const double *__restrict__ Ap,
-            const double *__restrict__ dinv, int n, double *x, double *r, double *z) {
-    const int i = blockIdx.x*PNL_NTHREADS+threadIdx.x;
-    const double alpha = scal[0]/scal[1];
-    if (i < n) {
-        x[i] = __builtin_fma(alpha, p[i], x[i]);
-        const double ri = __builtin_fma(-alpha, Ap[i], r[i]);
-        r[i] = ri;
-        z[i] = dinv[i]*ri;
-    }
-}
-
-// p = z + (beta/betaOld) p   (beta = scal[2], betaOld = scal[0])
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_cg_dir(const double *__restrict__ scal, const double *__restrict__ z, int n, double *p) {
-    const int i = blockIdx.x*PNL_NTHREADS+threadIdx.x;
-    const double t = scal[2]/scal[0];
-    if (i < n) p[i] = __builtin_fma(t, p[i], z[i]);
+    return with_shape(ctx, [&](auto D, auto E) {
+        constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;
+        return assemble_impl<DIM, DPE, tile_cells<DIM, DPE>>(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
+    });
 }
 
 }  // namespace
+
+// other translation units (pnl_h2.hip): see pnl_context.h
+int pnl_assembly_prepare(pnl_context *ctx) {
+    int rc;
+    if ((rc = check_ready(ctx)) || (rc = finalize(ctx))) return rc;
+    refresh_tables(ctx);
+    return PNL_OK;
+}
 
 // =================================================================================================
 // Are all cell pairs of the tile (block a, block b) distant pairs of ONE quadrature order q <= qlimit?  Returns q or 0.
@@ -2670,17 +2581,10 @@ int pnl_assemble_pairs_masked(pnl_context *ctx, int np, const int32_t *pairs, co
         ctx->orient = ko%norient;
         if (ctx->nlab > 0) { ctx->cur = k; refresh_tables(ctx); }
         const bool fast = ctx->P.k.fast != 0, first = ko == 0;
-        if (ctx->dim == 2 && ctx->dpe == 3)
-            rc = with_kt(fast, [&](auto kt) { return pairs_masked_impl<2, 3, decltype(kt)::value>(ctx, np, S, true, first); });
-        else if (ctx->dim == 2 && ctx->dpe == 6)
-            rc = with_kt(fast, [&](auto kt) { return pairs_masked_impl<2, 6, decltype(kt)::value>(ctx, np, S, true, first); });
-        else if (ctx->dim == 2 && ctx->dpe == 1)
-            rc = with_kt(fast, [&](auto kt) { return pairs_masked_impl<2, 1, decltype(kt)::value>(ctx, np, S, true, first); });
-        else if (ctx->dim == 1 && ctx->dpe == 2) rc = pairs_masked_impl<1, 2, 0>(ctx, np, S, true, first);
-        else if (ctx->dim == 1 && ctx->dpe == 1) rc = pairs_masked_impl<1, 1, 0>(ctx, np, S, true, first);
-        else if (ctx->dim == 1 && ctx->dpe == 3) rc = pairs_masked_impl<1, 3, 0>(ctx, np, S, true, first);
-        else if (ctx->dim == 1 && ctx->dpe == 4) rc = pairs_masked_impl<1, 4, 0>(ctx, np, S, true, first);
-        else rc = fail(ctx, PNL_ERR_UNSUPPORTED, "unsupported (dim=%d, dofs_per_element=%d)", ctx->dim, ctx->dpe);
+        rc = with_shape(ctx, [&](auto D, auto E) {
+            constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;
+            return with_kt_2d<DIM>(fast, [&](auto kt) { return pairs_masked_impl<DIM, DPE, decltype(kt)::value>(ctx, np, S, true, first); });
+        });
         if (rc) break;
     }
     ctx->cur = cur0; ctx->orient = 0;
@@ -2707,14 +2611,10 @@ int pnl_assemble_pairs_in_horizon_range(pnl_context *ctx, double *data, double *
     if ((rc = sparse_ready(ctx, data, diag, S))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
     const bool fast = ctx->P.k.fast != 0;
-    if (ctx->dim == 2 && ctx->dpe == 3) return with_kt(fast, [&](auto kt) { return horizon_impl<2, 3, decltype(kt)::value>(ctx, S, cell_begin, cell_end); });
-    if (ctx->dim == 2 && ctx->dpe == 6) return with_kt(fast, [&](auto kt) { return horizon_impl<2, 6, decltype(kt)::value>(ctx, S, cell_begin, cell_end); });
-    if (ctx->dim == 2 && ctx->dpe == 1) return with_kt(fast, [&](auto kt) { return horizon_impl<2, 1, decltype(kt)::value>(ctx, S, cell_begin, cell_end); });
-    if (ctx->dim == 1 && ctx->dpe == 2) return horizon_impl<1, 2, 0>(ctx, S, cell_begin, cell_end);
-    if (ctx->dim == 1 && ctx->dpe == 1) return horizon_impl<1, 1, 0>(ctx, S, cell_begin, cell_end);
-    if (ctx->dim == 1 && ctx->dpe == 3) return horizon_impl<1, 3, 0>(ctx, S, cell_begin, cell_end);
-    if (ctx->dim == 1 && ctx->dpe == 4) return horizon_impl<1, 4, 0>(ctx, S, cell_begin, cell_end);
-    return fail(ctx, PNL_ERR_UNSUPPORTED, "unsupported (dim=%d, dofs_per_element=%d)", ctx->dim, ctx->dpe);
+    return with_shape(ctx, [&](auto D, auto E) {
+        constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;
+        return with_kt_2d<DIM>(fast, [&](auto kt) { return horizon_impl<DIM, DPE, decltype(kt)::value>(ctx, S, cell_begin, cell_end); });
+    });
 }
 
 int pnl_assemble_boundary_masked(pnl_context *ctx, int ni, const int32_t *cells, const int32_t *facets, const uint32_t *masks,
@@ -2737,14 +2637,7 @@ int pnl_assemble_boundary_masked(pnl_context *ctx, int ni, const int32_t *cells,
     SparseOut S;
     if ((rc = sparse_ready(ctx, data, diag, S))) return rc;
     if (ni == 0) return PNL_OK;
-    if (ctx->dim == 2 && ctx->dpe == 3) return boundary_masked_impl<2, 3>(ctx, ni, fac, S);
-    if (ctx->dim == 2 && ctx->dpe == 6) return boundary_masked_impl<2, 6>(ctx, ni, fac, S);
-    if (ctx->dim == 2 && ctx->dpe == 1) return boundary_masked_impl<2, 1>(ctx, ni, fac, S);
-    if (ctx->dim == 1 && ctx->dpe == 2) return boundary_masked_impl<1, 2>(ctx, ni, fac, S);
-    if (ctx->dim == 1 && ctx->dpe == 1) return boundary_masked_impl<1, 1>(ctx, ni, fac, S);
-    if (ctx->dim == 1 && ctx->dpe == 3) return boundary_masked_impl<1, 3>(ctx, ni, fac, S);
-    if (ctx->dim == 1 && ctx->dpe == 4) return boundary_masked_impl<1, 4>(ctx, ni, fac, S);
-    return fail(ctx, PNL_ERR_UNSUPPORTED, "unsupported (dim=%d, dofs_per_element=%d)", ctx->dim, ctx->dpe);
+    return with_shape(ctx, [&](auto D, auto E) { return boundary_masked_impl<decltype(D)::value, decltype(E)::value>(ctx, ni, fac, S); });
 }
 
 int pnl_assemble_clusters_tiled(pnl_context *ctx, const pnl_cluster_plan *pl, int cluster_boundary, double *data, double *diag) {
@@ -2849,271 +2742,13 @@ int pnl_assemble_clusters_tiled(pnl_context *ctx, const pnl_cluster_plan *pl, in
     if ((rc = ensure(ctx, ctx->b_cpD, sizeof(double)*(size_t)std::max(pl->num_dslots, 1)*(dpe*(dpe+1)/2)))) return rc;
     CT.D = (double*)ctx->b_cpD.p;
     ctx->visited_pairs = 0; ctx->visited_is_assembled = false;
-    // triangles P1, P2, intervals P1; P0 (intervals and triangles), P2 and P3 on intervals
-#define PNL_CT(D_, E_, T_) \
-    if (dim == D_ && dpe == E_) \
-        return with_kt(ctx->P.k.fast, [&](auto kt) { \
-            return clusters_tiled_impl<D_, E_, T_, decltype(kt)::value>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev, sing_pair_dev, \
-                                                                        pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot); \
+    return with_shape(ctx, [&](auto D, auto E) {
+        constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;
+        return with_kt(ctx->P.k.fast, [&](auto kt) {
+            return clusters_tiled_impl<DIM, DPE, tile_cells<DIM, DPE>, decltype(kt)::value>(ctx, pl, CT, cluster_boundary, d_cell, d_pair, sing_dev,
+                                                                                          sing_pair_dev, pair_foff, fvid, fgeo, maxf, bt_cell, bt_facet, bt_slot);
         });
-    PNL_CT(2, 3, TILE_P1)
-    PNL_CT(2, 6, TILE_P2)
-    PNL_CT(1, 2, TILE_P1)
-    PNL_CT(2, 1, TILE_P1)
-    PNL_CT(1, 1, TILE_P1)
-    PNL_CT(1, 3, TILE_P2)
-    PNL_CT(1, 4, TILE_P2)
-#undef PNL_CT
-    return fail(ctx, PNL_ERR_UNSUPPORTED, "unsupported (dim=%d, dofs_per_element=%d)", dim, dpe);
-}
-
-int pnl_h2_setup(pnl_context *ctx, const pnl_h2_plan *pl) {
-    if (!ctx || !pl) return PNL_ERR_INVALID;
-    int rc;
-    if (ctx->have_pw) {
-        // order per quadrature point: no kernel block of a class, the order function evaluates s(x) (pnl_pwnear.hip)
-        if (ctx->pw.type == 5) return fail(ctx, PNL_ERR_UNSUPPORTED, "H2 far field of an order given as a finite element function");
-        if ((rc = pnl_pw_prepare(ctx, 0))) return rc;
-    } else {
-    if ((rc = check_ready(ctx))) return rc;
-    if ((rc = finalize(ctx))) return rc;
-    refresh_tables(ctx);
-    // finite horizon: every admissible pair must lie inside it (pnl_tree_build_horizon drops the pairs beyond the horizon and keeps the
-    // ones it may cut in the near field, clusterMethodCy.pyx:4069-4090); the interpolants are those of the kernel itself
-    if (!std::isinf(ctx->C().kern[0].horizon2)) {
-        if (ctx->have_xform) return fail(ctx, PNL_ERR_UNSUPPORTED, "H2 far field of a finite horizon: l2 ball only");
-        if (!pl->box || (pl->nfar > 0 && !pl->far)) return PNL_ERR_INVALID;
-        const double h2 = ctx->C().kern[0].horizon2;
-        for (int p = 0; p < pl->nfar; p++) {
-            const double *a = pl->box+(size_t)pl->far[2*p]*ctx->dim*2, *b = pl->box+(size_t)pl->far[2*p+1]*ctx->dim*2;
-            // maxDistBoxes as the reference writes it (interactionDomains.pyx:325-337): what its admissibility test compares with the
-            // horizon; interpolation nodes that do lie beyond the horizon get the kernel value 0 there and here (kern_eval)
-            double d2 = 0.;
-            for (int d = 0; d < ctx->dim; d++) {
-                const bool first = a[2*d] > b[2*d];
-                const double e = std::max((first ? a[2*d+1] : b[2*d+1])-(first ? b[2*d] : a[2*d]), 0.);
-                d2 += e*e;
-            }
-            if (d2 > h2*(1.+1e-12))
-                return fail(ctx, PNL_ERR_INVALID, "H2 far field: the clusters of admissible pair %d reach beyond the horizon", p);
-        }
-    }
-    }
-    // (the admissible pairs are ORDERED -- (n1, n2) and (n2, n1) are two entries, each with the class of its orientation -- so a
-    // non-symmetric order table needs nothing beyond its far_class)
-    if (ctx->nlab > 0 && pl->nfar > 0 && !pl->far_class)
-        return fail(ctx, PNL_ERR_UNSUPPORTED, "H2 far field of a variable order: a kernel class per admissible pair is needed");
-    if (pl->far_class)
-        for (int i = 0; i < pl->nfar; i++)
-            if (pl->far_class[i] < 0 || pl->far_class[i] >= (int)ctx->cls.size()) return fail(ctx, PNL_ERR_INVALID, "far pair %d: bad kernel class", i);
-    const int dim = ctx->dim, m = pl->m;
-    if (pl->nnodes <= 0 || pl->nleaves <= 0 || pl->nfar < 0 || m < 1 || m > 16 || pl->nq <= 0) return fail(ctx, PNL_ERR_INVALID, "bad H2 plan sizes");
-    int M = 1;
-    for (int d = 0; d < dim; d++) M *= m;
-    int nroot = 0;
-    for (int n = 0; n < pl->nnodes; n++) {
-        if (pl->parent[n] < -1 || pl->parent[n] >= pl->nnodes || pl->level[n] < 0 || pl->level[n] >= pl->nlevels)
-            return fail(ctx, PNL_ERR_INVALID, "node %d: bad parent / level", n);
-        if (pl->parent[n] < 0) nroot++;
-        else if (pl->level[pl->parent[n]] != pl->level[n]-1) return fail(ctx, PNL_ERR_INVALID, "node %d: level is not its parent's + 1", n);
-    }
-    if (nroot != 1) return fail(ctx, PNL_ERR_INVALID, "the tree needs exactly one root");
-    for (int i = 0; i < 2*pl->nfar; i++)
-        if (pl->far[i] < 0 || pl->far[i] >= pl->nnodes) return fail(ctx, PNL_ERR_INVALID, "far pair out of range");
-    std::vector<long long> voff(pl->nleaves);
-    long long vtot = 0;
-    std::vector<char> covered(ctx->N, 0);
-    for (int l = 0; l < pl->nleaves; l++) {
-        if (pl->leaf_node[l] < 0 || pl->leaf_node[l] >= pl->nnodes) return fail(ctx, PNL_ERR_INVALID, "leaf %d: bad node", l);
-        voff[l] = vtot;
-        vtot += (long long)(pl->leaf_dof_off[l+1]-pl->leaf_dof_off[l])*M;
-        for (int t = pl->leaf_dof_off[l]; t < pl->leaf_dof_off[l+1]; t++) {
-            const int I = pl->leaf_dofs[t];
-            if (I < 0 || I >= ctx->N || covered[I] || (t > pl->leaf_dof_off[l] && pl->leaf_dofs[t-1] >= I))
-                return fail(ctx, PNL_ERR_INVALID, "leaf %d: DoFs must be sorted and the leaves must partition the DoFs", l);
-            covered[I] = 1;
-        }
-        for (int t = pl->leaf_cell_off[l]; t < pl->leaf_cell_off[l+1]; t++)
-            if (pl->leaf_cells[t] < 0 || pl->leaf_cells[t] >= ctx->nc) return fail(ctx, PNL_ERR_INVALID, "leaf %d: bad cell", l);
-    }
-    if (!pl->partial_leaves)
-        for (int I = 0; I < ctx->N; I++)
-            if (!covered[I]) return fail(ctx, PNL_ERR_INVALID, "DoF %d belongs to no leaf (set partial_leaves for a rank-local plan)", I);
-    DevBuf *B = ctx->b_h2;
-    H2Dev &H = ctx->h2;
-    std::memset(&H, 0, sizeof(H));
-    H.dim = dim; H.m = m; H.M = M; H.nnodes = pl->nnodes; H.nleaves = pl->nleaves; H.nfar = pl->nfar;
-    if ((rc = upload(ctx, B[0], pl->box, (size_t)pl->nnodes*dim*2))) return rc;
-    if ((rc = upload(ctx, B[1], pl->parent, (size_t)pl->nnodes))) return rc;
-    if ((rc = upload(ctx, B[2], pl->leaf_node, (size_t)pl->nleaves))) return rc;
-    if ((rc = upload(ctx, B[3], pl->leaf_dof_off, (size_t)pl->nleaves+1))) return rc;
-    if ((rc = upload(ctx, B[4], pl->leaf_dofs, (size_t)pl->leaf_dof_off[pl->nleaves]))) return rc;
-    if ((rc = upload(ctx, B[5], pl->leaf_cell_off, (size_t)pl->nleaves+1))) return rc;
-    if ((rc = upload(ctx, B[6], pl->leaf_cells, (size_t)pl->leaf_cell_off[pl->nleaves]))) return rc;
-    if ((rc = upload(ctx, B[7], voff.data(), voff.size()))) return rc;
-    ctx->h2_vtot = vtot;
-    if ((rc = upload(ctx, B[8], pl->far, (size_t)2*pl->nfar))) return rc;
-    if ((rc = upload(ctx, B[9], pl->transfer, (size_t)pl->nnodes*M*M))) return rc;
-    if ((rc = ensure(ctx, B[10], sizeof(double)*(size_t)std::max<long long>(vtot, 1)))) return rc;
-    if ((rc = ensure(ctx, B[11], sizeof(double)*(size_t)std::max(pl->nfar, 1)*M*M))) return rc;
-    if ((rc = ensure(ctx, B[12], sizeof(double)*(size_t)pl->nnodes*M))) return rc;
-    if ((rc = ensure(ctx, B[13], sizeof(double)*(size_t)pl->nnodes*M))) return rc;
-    if ((rc = upload(ctx, B[14], pl->qbary, (size_t)3*pl->nq))) return rc;
-    if ((rc = upload(ctx, B[15], pl->qw, (size_t)pl->nq))) return rc;
-    if ((rc = upload(ctx, B[16], pl->qphi, (size_t)pl->nq*ctx->dpe))) return rc;
-    H.box = (const double*)B[0].p; H.parent = (const int*)B[1].p; H.leaf_node = (const int*)B[2].p;
-    H.leaf_dof_off = (const int*)B[3].p; H.leaf_dofs = (const int*)B[4].p; H.leaf_cell_off = (const int*)B[5].p;
-    H.leaf_cells = (const int*)B[6].p; H.leaf_val_off = (const long long*)B[7].p; H.far = (const int*)B[8].p;
-    H.T = (const double*)B[9].p; H.V = (double*)B[10].p; H.K = (double*)B[11].p; H.cup = (double*)B[12].p; H.cdown = (double*)B[13].p;
-    // nodes per level (children lists), concatenated on the device
-    ctx->h2_levels.assign(pl->nlevels, std::vector<int>());
-    for (int n = 0; n < pl->nnodes; n++)
-        if (pl->parent[n] >= 0) ctx->h2_levels[pl->level[n]].push_back(n);
-    std::vector<int> cat;
-    ctx->h2_level_off.assign(pl->nlevels+1, 0);
-    for (int l = 0; l < pl->nlevels; l++) {
-        ctx->h2_level_off[l] = cat.size();
-        cat.insert(cat.end(), ctx->h2_levels[l].begin(), ctx->h2_levels[l].end());
-    }
-    ctx->h2_level_off[pl->nlevels] = cat.size();
-    if ((rc = upload(ctx, B[17], cat.data(), cat.size()))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(H.V, 0, sizeof(double)*(size_t)std::max<long long>(vtot, 1), ctx->stream));
-    const double *qb = (const double*)B[14].p, *qw = (const double*)B[15].p, *qp = (const double*)B[16].p;
-    if (dim == 2 && ctx->dpe == 3) hipLaunchKernelGGL((k_h2_leaf_values<2, 3>), dim3(pl->nleaves), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, pl->nq, qb, qw, qp);
-    else if (dim == 2 && ctx->dpe == 6) hipLaunchKernelGGL((k_h2_leaf_values<2, 6>), dim3(pl->nleaves), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, pl->nq, qb, qw, qp);
-    else if (dim == 1 && ctx->dpe == 2) hipLaunchKernelGGL((k_h2_leaf_values<1, 2>), dim3(pl->nleaves), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, pl->nq, qb, qw, qp);
-    else if (dim == 2 && ctx->dpe == 1) hipLaunchKernelGGL((k_h2_leaf_values<2, 1>), dim3(pl->nleaves), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, pl->nq, qb, qw, qp);
-    else if (dim == 1 && ctx->dpe == 1) hipLaunchKernelGGL((k_h2_leaf_values<1, 1>), dim3(pl->nleaves), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, pl->nq, qb, qw, qp);
-    else if (dim == 1 && ctx->dpe == 3) hipLaunchKernelGGL((k_h2_leaf_values<1, 3>), dim3(pl->nleaves), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, pl->nq, qb, qw, qp);
-    else if (dim == 1 && ctx->dpe == 4) hipLaunchKernelGGL((k_h2_leaf_values<1, 4>), dim3(pl->nleaves), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, pl->nq, qb, qw, qp);
-    else return fail(ctx, PNL_ERR_UNSUPPORTED, "unsupported (dim=%d, dofs_per_element=%d)", dim, ctx->dpe);
-    if (pl->nfar > 0) {
-        const DevKernel *kcls = nullptr;
-        const int *fcls = nullptr;
-        if (pl->far_class) {
-            std::vector<DevKernel> kc;
-            for (auto *c : ctx->cls) kc.push_back(to_dev(c->kern[0], dim));
-            if ((rc = upload(ctx, B[18], kc.data(), kc.size()))) return rc;
-            if ((rc = upload(ctx, B[19], pl->far_class, (size_t)pl->nfar))) return rc;
-            kcls = (const DevKernel*)B[18].p; fcls = (const int*)B[19].p;
-        }
-        if (ctx->have_pw) {
-            // order per quadrature point: the kernel with the order at the nodes of the row cluster (pnl_pwnear.hip)
-            if ((rc = pnl_pw_h2_interp(ctx))) return rc;
-        } else
-        if (dim == 2) hipLaunchKernelGGL((k_h2_kernel_interp<2>), dim3(pl->nfar), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, kcls, fcls);
-        else hipLaunchKernelGGL((k_h2_kernel_interp<1>), dim3(pl->nfar), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, H, kcls, fcls);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_h2 = true;
-    return PNL_OK;
-}
-
-// the three phases of the H2 matvec on the coefficient arrays H.cup / H.cdown (the context's own, or the caller's)
-static int h2_upward(pnl_context *ctx, const H2Dev &H, const double *x) {
-    const int nlev = (int)ctx->h2_levels.size();
-    const int *lev = (const int*)ctx->b_h2[17].p;
-    HIPCHK(ctx, hipMemsetAsync(H.cup, 0, sizeof(double)*(size_t)H.nnodes*H.M, ctx->stream));
-    hipLaunchKernelGGL(k_h2_up_leaves, dim3(H.nleaves), dim3(64), 0, ctx->stream, H, x);
-    for (int l = nlev-1; l >= 1; l--) {
-        const int n = (int)ctx->h2_levels[l].size();
-        if (n) hipLaunchKernelGGL(k_h2_up_level, dim3(n), dim3(64), 0, ctx->stream, H, lev+ctx->h2_level_off[l], n);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
-}
-static int h2_interact(pnl_context *ctx, const H2Dev &H) {
-    HIPCHK(ctx, hipMemsetAsync(H.cdown, 0, sizeof(double)*(size_t)H.nnodes*H.M, ctx->stream));
-    if (H.nfar) hipLaunchKernelGGL(k_h2_far, dim3(H.nfar), dim3(64), 0, ctx->stream, H);
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
-}
-static int h2_downward(pnl_context *ctx, const H2Dev &H, double *y) {
-    const int nlev = (int)ctx->h2_levels.size();
-    const int *lev = (const int*)ctx->b_h2[17].p;
-    for (int l = 1; l < nlev; l++) {
-        const int n = (int)ctx->h2_levels[l].size();
-        if (n) hipLaunchKernelGGL(k_h2_down_level, dim3(n), dim3(64), 0, ctx->stream, H, lev+ctx->h2_level_off[l], n);
-    }
-    hipLaunchKernelGGL(k_h2_down_leaves, dim3(H.nleaves), dim3(64), 0, ctx->stream, H, y);
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
-}
-
-int pnl_h2_matvec(pnl_context *ctx, const double *x, double *y) {
-    if (!ctx || !x || !y) return PNL_ERR_INVALID;
-    if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
-    int rc;
-    if ((rc = h2_upward(ctx, ctx->h2, x)) || (rc = h2_interact(ctx, ctx->h2))) return rc;
-    return h2_downward(ctx, ctx->h2, y);
-}
-
-// kernel interpolants K[nfar][M][M] (which = 0) and leaf values V (which = 1: the blocks V_leaf[ndofs][M] of the plan's leaves, one
-// after the other) between the device and the host: the H2 operator file (clusterMethodCy.pyx:2449-2550) stores them
-static int h2_copy(pnl_context *ctx, int which, double *host, bool to_host) {
-    if (!ctx || !host) return PNL_ERR_INVALID;
-    if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
-    if (which != 0 && which != 1) return fail(ctx, PNL_ERR_INVALID, "pnl_h2_get / _set: which = 0 (interpolants) or 1 (leaf values)");
-    const H2Dev &H = ctx->h2;
-    const size_t n = which == 0 ? (size_t)H.nfar*H.M*H.M : (size_t)ctx->h2_vtot;
-    double *dev = which == 0 ? H.K : H.V;
-    if (n) HIPCHK(ctx, hipMemcpyAsync(to_host ? (void*)host : (void*)dev, to_host ? (const void*)dev : (const void*)host, n*sizeof(double),
-                                      to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PNL_OK;
-}
-int pnl_h2_get(pnl_context *ctx, int which, double *dst_host) { return h2_copy(ctx, which, dst_host, true); }
-int pnl_h2_set(pnl_context *ctx, int which, const double *src_host) { return h2_copy(ctx, which, const_cast<double*>(src_host), false); }
-
-int pnl_h2_sizes(pnl_context *ctx, int32_t *out2) {
-    if (!ctx || !out2) return PNL_ERR_INVALID;
-    if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
-    out2[0] = ctx->h2.nnodes; out2[1] = ctx->h2.M;
-    return PNL_OK;
-}
-
-int pnl_h2_upward(pnl_context *ctx, const double *x, double *cup) {
-    if (!ctx || !x || !cup) return PNL_ERR_INVALID;
-    if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
-    H2Dev H = ctx->h2;
-    H.cup = cup;
-    return h2_upward(ctx, H, x);
-}
-
-int pnl_h2_interact(pnl_context *ctx, const double *cup, double *cdown) {
-    if (!ctx || !cup || !cdown) return PNL_ERR_INVALID;
-    if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
-    H2Dev H = ctx->h2;
-    H.cup = const_cast<double*>(cup); H.cdown = cdown;
-    return h2_interact(ctx, H);
-}
-
-int pnl_h2_downward(pnl_context *ctx, double *cdown, double *y) {
-    if (!ctx || !cdown || !y) return PNL_ERR_INVALID;
-    if (!ctx->have_h2) return fail(ctx, PNL_ERR_STATE, "pnl_h2_setup first");
-    H2Dev H = ctx->h2;
-    H.cdown = cdown;
-    return h2_downward(ctx, H, y);
-}
-
-int pnl_spmv(pnl_context *ctx, const double *data, const double *diag, const double *x, double *y) {
-    if (!ctx || !x || !y) return PNL_ERR_INVALID;
-    if (ctx->sp_nnz < 0) return fail(ctx, PNL_ERR_STATE, "upload the sparsity pattern first");
-    if (!data && ctx->sp_nnz > 0) return fail(ctx, PNL_ERR_INVALID, "null matrix data");
-    const int n = ctx->N;
-    if (diag) HIPCHK(ctx, hipMemsetAsync(y, 0, sizeof(double)*n, ctx->stream));
-    hipLaunchKernelGGL(k_spmv, dim3((n+3)/4), dim3(PNL_NTHREADS), 0, ctx->stream, (const int*)ctx->b_sp_indptr.p,
-                       (const int*)ctx->b_sp_indices.p, data, diag, n, x, y);
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
-}
-
-int pnl_inv_diagonal(pnl_context *ctx, const double *A, int64_t ldA, int n, double *dinv) {
-    if (!ctx || !A || !dinv || n <= 0 || ldA < n) return fail(ctx, PNL_ERR_INVALID, "bad arguments");
-    hipLaunchKernelGGL(k_diag_inv, dim3((n+PNL_NTHREADS-1)/PNL_NTHREADS), dim3(PNL_NTHREADS), 0, ctx->stream, A, (long long)ldA, n, dinv);
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
+    });
 }
 
 // ---- non-symmetric kernels with an order s(x) per quadrature point ------------------------------------------------------
@@ -3295,77 +2930,6 @@ int pnl_get_kernel_ms(pnl_context *ctx, float *out, int n) {
         out[s] = 0.f;
         if (ctx->kev_set[s]) HIPCHK(ctx, hipEventElapsedTime(&out[s], ctx->kev[s][0], ctx->kev[s][1]));
     }
-    return PNL_OK;
-}
-
-int pnl_gemv(pnl_context *ctx, const double *A, int64_t ldA, int n, const double *x, double *y, int symmetric_half) {
-    if (!ctx || !A || !x || !y || n <= 0 || ldA < n) return fail(ctx, PNL_ERR_INVALID, "bad gemv arguments");
-    // 2: A is stored in full and is symmetric -- its upper triangle is read once for both A x and A^T x (4 n^2 bytes, pnl_gemv2.hip)
-    if (symmetric_half == 2) return pnl_launch_gemv_symmetric(ctx, A, (long long)ldA, n, x, 1., 0., nullptr, y);
-    hipLaunchKernelGGL(k_gemv, dim3((n+3)/4), dim3(PNL_NTHREADS), 0, ctx->stream, A, (long long)ldA, n, x, y);
-    HIPCHK(ctx, hipGetLastError());
-    if (symmetric_half) {
-        const int rows = 128;
-        hipLaunchKernelGGL(k_gemv_t_add, dim3((n+PNL_NTHREADS-1)/PNL_NTHREADS, (n+rows-1)/rows), dim3(PNL_NTHREADS), 0, ctx->stream,
-                           A, (long long)ldA, n, x, y, rows);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return PNL_OK;
-}
-
-int pnl_cg_jacobi(pnl_context *ctx, const double *A, int64_t ldA, int n, const double *b, double *x, double tol, int maxiter,
-                  int *iters, double *residual) {
-    if (!ctx || !A || !b || !x || n <= 0 || ldA < n || maxiter < 0) return fail(ctx, PNL_ERR_INVALID, "bad cg arguments");
-    int rc;
-    for (int i = 0; i < 5; i++)
-        if ((rc = ensure(ctx, ctx->b_vec[i], sizeof(double)*n))) return rc;
-    if ((rc = ensure(ctx, ctx->b_scal, sizeof(double)*4))) return rc;
-    double *r = (double*)ctx->b_vec[0].p, *p = (double*)ctx->b_vec[1].p, *Ap = (double*)ctx->b_vec[2].p,
-           *z = (double*)ctx->b_vec[3].p, *dinv = (double*)ctx->b_vec[4].p, *scal = (double*)ctx->b_scal.p;
-    const int gv = (n+PNL_NTHREADS-1)/PNL_NTHREADS, gd = std::min(gv, 1024);
-    hipStream_t st = ctx->stream;
-    auto dot = [&](const double *u, const double *v, int slot) {
-        (void)hipMemsetAsync(scal+slot, 0, sizeof(double), st);
-        hipLaunchKernelGGL(k_dot, dim3(gd), dim3(PNL_NTHREADS), 0, st, u, v, n, scal+slot);
-    };
-    double hs[4];
-    // solvers.pyx:363-444 with the Jacobi preconditioner (:229-245); convergence in the preconditioner norm
-    // CG needs a symmetric operator: every product reads the upper triangle only (pnl_gemv2.hip; 4 n^2 bytes instead of 8 n^2)
-    auto gemv = [&](const double *v, double *out) { return pnl_launch_gemv_symmetric(ctx, A, (long long)ldA, n, v, 1., 0., nullptr, out); };
-    hipLaunchKernelGGL(k_diag_inv, dim3(gv), dim3(PNL_NTHREADS), 0, st, A, (long long)ldA, n, dinv);
-    if ((rc = gemv(x, Ap))) return rc;
-    hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(PNL_NTHREADS), 0, st, b, (const double*)Ap, (const double*)dinv, n, r, p);
-    dot(r, p, 0);                                                // betaOld = r . Br
-    HIPCHK(ctx, hipMemcpyAsync(hs, scal, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    double conv = std::sqrt(hs[0]);
-    int it = 0, k = 0;
-    if (conv > tol) {
-        for (it = 0; it < maxiter; it++) {
-            if ((rc = gemv(p, Ap))) return rc;
-            dot(p, Ap, 1);
-            hipLaunchKernelGGL(k_cg_update, dim3(gv), dim3(PNL_NTHREADS), 0, st, (const double*)scal, (const double*)p,
-                               (const double*)Ap, (const double*)dinv, n, x, r, z);
-            if (k == 50) {
-                // recalculate the residual to limit rounding drift (solvers.pyx:412-415)
-                if ((rc = gemv(x, Ap))) return rc;
-                hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(PNL_NTHREADS), 0, st, b, (const double*)Ap, (const double*)dinv, n, r, z);
-                k = 0;
-            }
-            dot(r, z, 2);                                        // beta = r . Br
-            HIPCHK(ctx, hipMemcpyAsync(hs, scal, 3*sizeof(double), hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            conv = std::sqrt(hs[2]);
-            if (conv <= tol) break;
-            hipLaunchKernelGGL(k_cg_dir, dim3(gv), dim3(PNL_NTHREADS), 0, st, (const double*)scal, (const double*)z, n, p);
-            // betaOld = beta
-            HIPCHK(ctx, hipMemcpyAsync(scal, scal+2, sizeof(double), hipMemcpyDeviceToDevice, st));
-            k++;
-        }
-    }
-    HIPCHK(ctx, hipGetLastError());
-    if (iters) *iters = it;
-    if (residual) *residual = conv;
     return PNL_OK;
 }
 

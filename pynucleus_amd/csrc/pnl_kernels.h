@@ -9,6 +9,8 @@
 //                    the Duffy-type quadrature points, butterfly reduction, atomic scatter.
 //   k_boundary_*     Omega x Omega^c term (cell x boundary facet).
 //   k_scatter_diag   adds the per-cell diagonal blocks, k_mirror symmetrises the cross part.
+// Near field only: the H2 far field is pnl_h2.hip, the GEMV / SpMV / CG kernels are in pnl_solver.hip.  pnl_hip.hip, pnl_pwnear.hip
+// and pnl_selftest.hip include this file; every non-template kernel here is compiled into each of them.
 //
 // Reference routines restated per kernel are cited at each kernel (paths under
 // /root/reference/nl/PyNucleus_nl; NO = nonlocalOperator_{SCALAR}.pxi, NA = nonlocalAssembly_{SCALAR}.pxi,
@@ -3295,42 +3297,6 @@ k_boundary_items(const DevProblem P, const double *__restrict__ verts, const int
     }
 }
 
-// ---- near-field matvec: CSR_LinearOperator / SSS_LinearOperator matvec (CSR_LinearOperator_{SCALAR}.pxi:259-284,
-// SSS_LinearOperator_{SCALAR}.pxi:146-176).  One wave per row; SSS adds the mirrored entries with atomics.
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_spmv(const int *__restrict__ indptr, const int *__restrict__ indices, const double *__restrict__ data,
-       const double *__restrict__ diag, int n, const double *__restrict__ x, double *__restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    const int row = (blockIdx.x*PNL_NTHREADS+threadIdx.x) >> 6;
-    if (row >= n) return;
-    const int b = indptr[row], e = indptr[row+1];
-    const double xi = x[row];
-    double s = 0.;
-    int t = b+lane;
-    if (!diag) {
-        // four independent (index, value, x) load chains per lane in flight: rows of the near field hold ~1000 entries
-        double s1 = 0., s2 = 0., s3 = 0.;
-        for (; t+192 < e; t += 256) {
-            const int J0 = indices[t], J1 = indices[t+64], J2 = indices[t+128], J3 = indices[t+192];
-            const double a0 = data[t], a1 = data[t+64], a2 = data[t+128], a3 = data[t+192];
-            s = __builtin_fma(a0, x[J0], s); s1 = __builtin_fma(a1, x[J1], s1);
-            s2 = __builtin_fma(a2, x[J2], s2); s3 = __builtin_fma(a3, x[J3], s3);
-        }
-        s += s1+(s2+s3);
-    }
-    for (; t < e; t += 64) {
-        const int J = indices[t];
-        const double a = data[t];
-        s = __builtin_fma(a, x[J], s);
-        if (diag) atomic_add_f64(&y[J], a*xi);
-    }
-    s = wave_sum(s);
-    if (lane == 0) {
-        if (diag) atomic_add_f64(&y[row], __builtin_fma(diag[row], xi, s));
-        else y[row] = s;
-    }
-}
-
 // ---- tiled near field: scatter of the per-(cluster pair, cell) diagonal blocks -----------------------------------------
 // D[d][.] of cell X = d_cell[d] in cluster pair d_pair[d]: every ordered local pair (p, q) goes to (I, J) = (ld[p], ld[q]) if
 // the DoF pair belongs to the cluster pair (mirror images are their own ordered pairs; SSS keeps I >= J)
@@ -3465,193 +3431,6 @@ k_cluster_boundary(const DevProblem P, const double *__restrict__ verts, const i
         if (Dl[e] != 0.) atomic_add_f64(&D[(size_t)d*ND+e], Dl[e]);
     if (overflow) atomicAdd(&P.counters[5], (unsigned long long)overflow);
     if (npairs) { atomicAdd(&P.counters[3], npairs); atomicAdd(&P.counters[4], nevals); }
-}
-
-// =====================================================================================================================
-// H2 far field (clusterMethodCy.pyx): Chebyshev interpolation of the kernel on admissible cluster pairs
-// (assembleFarFieldInteractions :2153-2238, factor -2 for the (u(x)-u(y))(v(x)-v(y)) form), leaf values
-// int phi_I L_alpha (enterLeafValues :1205-1325), upward / downward passes with the transfer operators
-// (:1092-1124, :1157-1180; the transfer matrices :2004-2073 are built on the host) and H2Matrix.matvec :2269-2295.
-// Tensor index alpha = alpha_0 + m alpha_1 (coordinate 0 fastest) in every array of this file.
-// struct H2Dev: pnl_device.h
-
-// j-th Chebyshev node of [a, b]: eta_j = cos((2 (m-j) - 1) pi / (2m)) (clusterMethodCy.pyx:2173, 1255)
-__device__ __forceinline__ double cheb_node(double a, double b, int m, int j) {
-    return (b-a)*0.5*(cos((2.0*(m-j)-1.0)/(2.0*m)*3.14159265358979323846)+1.0)+a;
-}
-
-// 1D Lagrange polynomial l on the Chebyshev nodes of [a, b] at x
-__device__ __forceinline__ double lagrange1d(double a, double b, int m, int l, double x) {
-    const double xl = cheb_node(a, b, m, l);
-    double v = 1.;
-    for (int k = 0; k < m; k++)
-        if (k != l) {
-            const double xk = cheb_node(a, b, m, k);
-            v *= (x-xk)/(xl-xk);
-        }
-    return v;
-}
-
-template <int DIM>
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_h2_kernel_interp(const DevProblem P, const H2Dev H, const DevKernel *__restrict__ kcls, const int *__restrict__ far_class) {
-    const int pr = blockIdx.x, n1 = H.far[2*pr], n2 = H.far[2*pr+1];
-    const DevKernel kn = far_class ? kcls[far_class[pr]] : P.k;
-    const double *b1 = H.box+(size_t)n1*DIM*2, *b2 = H.box+(size_t)n2*DIM*2;
-    for (int t = threadIdx.x; t < H.M*H.M; t += PNL_NTHREADS) {
-        const int i = t/H.M, j = t-i*H.M;
-        double d2 = 0.;
-        int ii = i, jj = j;
-#pragma unroll
-        for (int d = 0; d < DIM; d++) {
-            const double x = cheb_node(b1[2*d], b1[2*d+1], H.m, ii % H.m), y = cheb_node(b2[2*d], b2[2*d+1], H.m, jj % H.m);
-            ii /= H.m; jj /= H.m;
-            d2 += (x-y)*(x-y);
-        }
-        H.K[(size_t)pr*H.M*H.M+t] = -2.*kern_eval<0>(kn, d2);
-    }
-}
-
-// V_leaf[lcl_dof][alpha] = sum over the cells of the leaf and the quadrature points of vol w phi_k(x) L_alpha(x)
-template <int DIM, int DPE>
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_h2_leaf_values(const DevProblem P, const H2Dev H, int nq, const double *__restrict__ qbary, const double *__restrict__ qw,
-                 const double *__restrict__ qphi) {
-    constexpr int NV = DIM+1;
-    const int lf = blockIdx.x, node = H.leaf_node[lf];
-    const double *bx = H.box+(size_t)node*DIM*2;
-    const int *dofs = H.leaf_dofs+H.leaf_dof_off[lf];
-    const int nd = H.leaf_dof_off[lf+1]-H.leaf_dof_off[lf];
-    const int *cells = H.leaf_cells+H.leaf_cell_off[lf];
-    const int ncl = H.leaf_cell_off[lf+1]-H.leaf_cell_off[lf];
-    double *V = H.V+H.leaf_val_off[lf];
-    // Chebyshev nodes of the leaf's box, once per workgroup (the cosines were 3/4 of the kernel: 5.2 -> 1.x ms at 49k DoFs)
-    constexpr int MAXM = 64;
-    __shared__ double s_node[DIM][MAXM];
-    const bool tab = H.m <= MAXM;
-    if (tab) {
-        for (int t = threadIdx.x; t < DIM*H.m; t += PNL_NTHREADS) s_node[t/H.m][t % H.m] = cheb_node(bx[2*(t/H.m)], bx[2*(t/H.m)+1], H.m, t % H.m);
-        __syncthreads();
-    }
-    for (int t = threadIdx.x; t < ncl*H.M; t += PNL_NTHREADS) {
-        const int c = cells[t/H.M], alpha = t % H.M;
-        int lcl[DPE];
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < DPE; k++) {
-            const int I = P.cdof[(size_t)k*P.ncp+c];
-            int lo = 0, hi = nd;
-            while (lo < hi) { const int mid = (lo+hi) >> 1; if (dofs[mid] < I) lo = mid+1; else hi = mid; }
-            lcl[k] = (I >= 0 && lo < nd && dofs[lo] == I) ? lo : -1;
-            any = any || lcl[k] >= 0;
-        }
-        if (!any) continue;
-        double acc[DPE];
-#pragma unroll
-        for (int k = 0; k < DPE; k++) acc[k] = 0.;
-        const double vol = P.cvol[c];
-        for (int j = 0; j < nq; j++) {
-            double L = 1.;
-            int aa = alpha;
-#pragma unroll
-            for (int d = 0; d < DIM; d++) {
-                double x = 0.;
-#pragma unroll
-                for (int v = 0; v < NV; v++) x = __builtin_fma(qbary[3*j+v], P.cellv[(size_t)(v*DIM+d)*P.ncp+c], x);
-                const int l = aa % H.m;
-                if (tab) {
-                    // lagrange1d with the nodes from the table: the same operations in the same order
-                    const double xl = s_node[d][l];
-                    double v = 1.;
-                    for (int k = 0; k < H.m; k++)
-                        if (k != l) { const double xk = s_node[d][k]; v *= (x-xk)/(xl-xk); }
-                    L *= v;
-                } else L *= lagrange1d(bx[2*d], bx[2*d+1], H.m, l, x);
-                aa /= H.m;
-            }
-            const double wl = vol*qw[j]*L;
-#pragma unroll
-            for (int k = 0; k < DPE; k++) acc[k] = __builtin_fma(wl, qphi[j*DPE+k], acc[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < DPE; k++)
-            if (lcl[k] >= 0) atomic_add_f64(&V[(size_t)lcl[k]*H.M+alpha], acc[k]);
-    }
-}
-
-// upward pass, leaves: cup[node][alpha] = sum_dofs x[dof] V[dof][alpha]
-__global__ void __launch_bounds__(64)
-k_h2_up_leaves(const H2Dev H, const double *__restrict__ x) {
-    const int lf = blockIdx.x, node = H.leaf_node[lf];
-    const int *dofs = H.leaf_dofs+H.leaf_dof_off[lf];
-    const int nd = H.leaf_dof_off[lf+1]-H.leaf_dof_off[lf];
-    const double *V = H.V+H.leaf_val_off[lf];
-    for (int a = threadIdx.x; a < H.M; a += 64) {
-        double s = 0.;
-        for (int k = 0; k < nd; k++) s = __builtin_fma(x[dofs[k]], V[(size_t)k*H.M+a], s);
-        H.cup[(size_t)node*H.M+a] = s;
-    }
-}
-
-// y[i] += sum_j B[i][j] x[j] for a row-major M x M block, one wave: the lanes run over the COLUMNS, so a row is read as contiguous
-// segments (a lane per row reads with a stride of M doubles: 64 cache lines per load), one wave reduction per row; lane i keeps row i and
-// the results leave as one coalesced set of atomics per 64 rows
-__device__ __forceinline__ void h2_block_matvec_add(const double *__restrict__ B, int M, const double *__restrict__ x, double *__restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    for (int i0 = 0; i0 < M; i0 += 64) {
-        double mine = 0.;
-        const int rows = min(64, M-i0);
-        for (int ii = 0; ii < rows; ii++) {
-            const double *__restrict__ row = B+(size_t)(i0+ii)*M;
-            double s = 0.;
-            for (int j = lane; j < M; j += 64) s = __builtin_fma(row[j], x[j], s);
-            s = wave_sum(s);
-            mine = (lane == ii) ? s : mine;
-        }
-        if (lane < rows) atomic_add_f64(&y[i0+lane], mine);
-    }
-}
-
-// upward pass, one level: cup[parent] += T_child cup[child] for the nodes of the level (list of children)
-__global__ void __launch_bounds__(64)
-k_h2_up_level(const H2Dev H, const int *__restrict__ nodes, int n) {
-    const int c = nodes[blockIdx.x], p = H.parent[c];
-    (void)n;
-    h2_block_matvec_add(H.T+(size_t)c*H.M*H.M, H.M, H.cup+(size_t)c*H.M, H.cup+(size_t)p*H.M);
-}
-
-// far field: cdown[n1] += K cup[n2]
-__global__ void __launch_bounds__(64)
-k_h2_far(const H2Dev H) {
-    const int pr = blockIdx.x, n1 = H.far[2*pr], n2 = H.far[2*pr+1];
-    h2_block_matvec_add(H.K+(size_t)pr*H.M*H.M, H.M, H.cup+(size_t)n2*H.M, H.cdown+(size_t)n1*H.M);
-}
-
-// downward pass, one level: cdown[child] += T_child^T cdown[parent]
-__global__ void __launch_bounds__(64)
-k_h2_down_level(const H2Dev H, const int *__restrict__ nodes, int n) {
-    const int c = nodes[blockIdx.x], p = H.parent[c];
-    (void)n;
-    const double *T = H.T+(size_t)c*H.M*H.M;
-    for (int j = threadIdx.x; j < H.M; j += 64) {
-        double s = 0.;
-        for (int i = 0; i < H.M; i++) s = __builtin_fma(T[(size_t)i*H.M+j], H.cdown[(size_t)p*H.M+i], s);
-        H.cdown[(size_t)c*H.M+j] += s;           // every child is written by one workgroup, after its parent's level
-    }
-}
-
-// downward pass, leaves: y[dof] += sum_alpha V[dof][alpha] cdown[node][alpha]
-__global__ void __launch_bounds__(64)
-k_h2_down_leaves(const H2Dev H, double *__restrict__ y) {
-    const int lf = blockIdx.x, node = H.leaf_node[lf];
-    const int *dofs = H.leaf_dofs+H.leaf_dof_off[lf];
-    const int nd = H.leaf_dof_off[lf+1]-H.leaf_dof_off[lf];
-    const double *V = H.V+H.leaf_val_off[lf];
-    for (int k = threadIdx.x; k < nd; k += 64) {
-        double s = 0.;
-        for (int a = 0; a < H.M; a++) s = __builtin_fma(V[(size_t)k*H.M+a], H.cdown[(size_t)node*H.M+a], s);
-        y[dofs[k]] += s;                         // leaves partition the DoFs
-    }
 }
 
 // ---------------------------------------------------------------------------------------------

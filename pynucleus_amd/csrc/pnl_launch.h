@@ -1,21 +1,7 @@
 // Internal, host only: the launch sequences that pnl_hip.hip and pnl_pwnear.hip share.  Include it behind pnl_kernels.h (the
 // k_wl_* kernels) and pnl_context.h; every function is static, each translation unit launches its own copies of the kernels.
 #pragma once
-#include <type_traits>
-
-// runtime value -> template argument: f receives a std::integral_constant and returns the launcher's code
-// number of common vertices - 1 of a touching pair -> SLOT of its rule (the last slot of the dimension: identical cells)
-template <int DIM, class F>
-static int with_slot(int s, F &&f) {
-    if (s == 0) return f(std::integral_constant<int, 0>{});
-    if (s == 1) return f(std::integral_constant<int, 1>{});
-    return f(std::integral_constant<int, (DIM == 2 ? 2 : 1)>{});
-}
-// quarter-integer exponent (DevKernel::fast) -> KT 1, general exponent -> KT 0
-template <class F>
-static int with_kt(bool fast, F &&f) {
-    return fast ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
-}
+#include "pnl_dispatch.h"
 
 // counting sort of a work list by order: histogram, offsets, cursors of the bins (PNL_WL_BINS + 1 words each, carved out of aux_base)
 struct WlBins { unsigned *hist, *offs, *coff, *cursor; };
