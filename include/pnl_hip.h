@@ -533,6 +533,70 @@ int pnl_theta_step(pnl_mg *mg, const double *S_dev, int64_t ldS, const int32_t *
                    int *iters, double *residual);
 /* 1/diag(A) into dinv_dev (jacobi_solver.setup, solvers.pyx:233-237) */
 int pnl_inv_diagonal(pnl_context *ctx, const double *A_dev, int64_t ldA, int n, double *dinv_dev);
+/* Jacobi-preconditioned CG on (scale M) x = b for a CSR matrix on the device (n rows, symmetric positive definite, the diagonal
+ * stored): the loop of pnl_cg_jacobi -- same update order, convergence on sqrt(r.Br) <= tol, residual recomputed every 50
+ * iterations -- with the product of pnl_csr_matvec.  What the reference does with `cg-jacobi` on the mass matrix
+ * (solverBuilder(t, 1., 0.), timestepping.py:377-682).  x_dev holds the initial guess unless x_is_zero, and the result. */
+int pnl_csr_cg_jacobi(pnl_context *ctx, int n, const int32_t *indptr_dev, const int32_t *indices_dev, const double *data_dev, double scale,
+                      const double *b_dev, double *x_dev, double tol, int maxiter, int x_is_zero, int *iters, double *residual);
+
+/* ---- pointwise nonlinearities against the test functions (csrc/pnl_reaction.hip): assembleNonlinearity
+ *      (fem/PyNucleus_fem/femCy.pyx:3087-3178) on the device ----------------------------------------------------------------------
+ * A space is the cell -> DoF table dofs[ncells][dofs_per_cell] (negative: no DoF, its value counts as 0), the cell volumes
+ * vol[ncells] and a volume rule: phi[dofs_per_cell][nq] = the local shape functions at the nq <= 7 nodes, w[nq] (summing to 1).
+ * dofs_per_cell = 2, 3 or 6.  The space owns the inverted index DoF -> (cell, local index) in ascending cell order and the
+ * workspace of the local contributions. */
+typedef struct pnl_fe_space pnl_fe_space;
+int pnl_fe_space_create(pnl_context *ctx, int ncells, int dofs_per_cell, int nq, int ndofs, const int32_t *dofs_host, const double *vol_host,
+                        const double *phi_host, const double *w_host, pnl_fe_space **out);
+int pnl_fe_space_destroy(pnl_fe_space *space);
+/* PNL_FUN_BRUSSELATOR (2 -> 2, params B, Q): z = B u + Q^2 v + (B/Q) u^2 + 2 Q u v + u^2 v, f = (-u + z, -z) (femCy.pyx:3025-3041);
+ * PNL_FUN_CUBIC (1 -> 1, no params): u^3 - u (CahnHilliard_F_prime) */
+enum pnl_function { PNL_FUN_BRUSSELATOR = 0, PNL_FUN_CUBIC = 1 };
+/* R = beta R + alpha N(U),  N(U)[o][I] = sum over (c, m) with dof(c, m) = I of vol_c sum_q w_q f_o(u(c, q)) phi_m(xi_q),
+ * u_j(c, q) = sum_m U[j][dof(c, m)] phi_m(xi_q).  U_dev[nin][ldU], R_dev[nout][ldR], ldU, ldR >= ndofs.  No float atomics: the
+ * same input gives the same bits.  PNL_ERR_INVALID for an unknown function or nin / nout / nparams that are not the function's.
+ * Asynchronous on the context's stream. */
+int pnl_assemble_nonlinearity(pnl_fe_space *space, int fun, const double *params_host, int nparams, int nin, const double *U_dev,
+                              int64_t ldU, int nout, double alpha, double beta, double *R_dev, int64_t ldR);
+
+/* ---- IMEX Runge-Kutta for  m_c M u_c' + S u_c - N_c(u) = g_c(t),  c < ncomp  (IMEX._stepOfPicard, timestepping.py:377-682;
+ *      signs as there: E = -N(U), I = S U) ---------------------------------------------------------------------------------------
+ * Tableau AE, AI [s][s] row-major (AE strictly lower, AI lower triangular, one value gamma on the diagonal of AI at the stages
+ * that are solved), bE, bI [s].  S_dev: the dense symmetric operator, M: the CSR mass matrix, both shared by the components;
+ * fun / params: the nonlinearity, its number of inputs = outputs = ncomp.  solver PNL_IMEX_CG_MG: mg[c] is the multigrid object
+ * on the hierarchy of m_c M + dt gamma S (pnl_mg_cg to tol / maxiter); PNL_IMEX_CHOL: chol_dev[c] / ldchol[c] is the Cholesky
+ * factor of that matrix (pnl_potrf; pnl_potrs).  mass_tol / mass_maxiter: the mass solve at the end of a sweep
+ * (pnl_csr_cg_jacobi).  All device arrays stay owned by the caller and must outlive the object. */
+#define PNL_IMEX_MAX_STAGES 4
+#define PNL_IMEX_MAX_COMP 2
+enum { PNL_IMEX_CG_MG = 0, PNL_IMEX_CHOL = 1 };
+typedef struct {
+    int32_t s, ncomp, n, fun, nparams, solver, maxiter, mass_maxiter;
+    double AE[PNL_IMEX_MAX_STAGES*PNL_IMEX_MAX_STAGES], AI[PNL_IMEX_MAX_STAGES*PNL_IMEX_MAX_STAGES];
+    double bE[PNL_IMEX_MAX_STAGES], bI[PNL_IMEX_MAX_STAGES];
+    double mass_scale[PNL_IMEX_MAX_COMP], params[4];
+    double dt, tol, mass_tol;
+    const double *S_dev;
+    int64_t ldS;
+    const int32_t *M_indptr_dev, *M_indices_dev;
+    const double *M_data_dev;
+    pnl_fe_space *space;
+    pnl_mg *mg[PNL_IMEX_MAX_COMP];
+    const double *chol_dev[PNL_IMEX_MAX_COMP];
+    int64_t ldchol[PNL_IMEX_MAX_COMP];
+} pnl_imex_desc;
+typedef struct pnl_imex pnl_imex;
+int pnl_imex_create(pnl_context *ctx, const pnl_imex_desc *desc, pnl_imex **out);
+int pnl_imex_destroy(pnl_imex *imex);
+/* One sweep (u_prev, u) -> u_new with the vectors [ncomp][n] in HBM.  Stage k: U_k = u if row k of AE is zero, else per component
+ *   (m_c M + dt gamma S) U_k = m_c M u_prev - dt sum_{j<k} (AE[k][j] E_j + AI[k][j] I_j) + dt sum_{j<=k} AI[k][j] g_j
+ * from the initial guess u; E_k = -N(U_k) and I_k = S U_k are formed only if a later stage or the final update uses them.  Then
+ *   m_c M u_new = m_c M u_prev - dt sum_k (bE[k] E_k + bI[k] I_k) + dt sum_k bI[k] g_k
+ * from the initial guess u.  u_dev receives u_new; u_prev_dev may be u_dev (a plain step).  force_dev: g as [s][ncomp][n], or NULL.
+ * iters_out (host, may be NULL): [(s + 1) ncomp] iterations of the stage solves [k][c], then of the mass solves [c].  The
+ * right-hand sides are formed by one kernel each from the stored rows; stage storage is one block owned by the object. */
+int pnl_imex_sweep(pnl_imex *imex, const double *u_prev_dev, double *u_dev, const double *force_dev, int32_t *iters_out);
 
 /* ---- direct solver for the dense symmetric positive definite operators (csrc/pnl_direct.hip): what lu_solver.setup / solve
  *      (base/PyNucleus_base/solvers.pyx:80-186: dense copy, getrf, getrs) is for `--matrixFormat dense --solver lu`.  The operators

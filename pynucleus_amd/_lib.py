@@ -32,7 +32,13 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_assemble_pairs_in_horizon', 'pnl_assemble_pairs_in_horizon_range', 'pnl_set_nonsymmetric', 'pnl_set_order_function', 'pnl_upload_pointwise_rules', 'pnl_assemble_dense_pointwise',
            'pnl_assemble_pairs_masked_pointwise', 'pnl_assemble_boundary_masked_pointwise',
            'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest',
-           'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs']
+           'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs',
+           'pnl_csr_cg_jacobi', 'pnl_fe_space_create', 'pnl_fe_space_destroy', 'pnl_assemble_nonlinearity', 'pnl_imex_create',
+           'pnl_imex_destroy', 'pnl_imex_sweep']
+
+PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
+PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
+PNL_IMEX_MAX_STAGES, PNL_IMEX_MAX_COMP = 4, 2
 
 
 def source_sha16():
@@ -87,6 +93,17 @@ class pnl_h2_plan(C.Structure):
                 [(n, C.c_void_p) for n in ('box', 'parent', 'level', 'leaf_node', 'leaf_dof_off', 'leaf_dofs', 'leaf_cell_off',
                                            'leaf_cells', 'far', 'transfer', 'qbary', 'qw', 'qphi', 'far_class')] +
                 [('partial_leaves', C.c_int32)])
+
+
+class pnl_imex_desc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ('s', 'ncomp', 'n', 'fun', 'nparams', 'solver', 'maxiter', 'mass_maxiter')] +
+                [('AE', C.c_double*(PNL_IMEX_MAX_STAGES**2)), ('AI', C.c_double*(PNL_IMEX_MAX_STAGES**2)),
+                 ('bE', C.c_double*PNL_IMEX_MAX_STAGES), ('bI', C.c_double*PNL_IMEX_MAX_STAGES),
+                 ('mass_scale', C.c_double*PNL_IMEX_MAX_COMP), ('params', C.c_double*4),
+                 ('dt', C.c_double), ('tol', C.c_double), ('mass_tol', C.c_double),
+                 ('S_dev', C.c_void_p), ('ldS', C.c_int64), ('M_indptr_dev', C.c_void_p), ('M_indices_dev', C.c_void_p),
+                 ('M_data_dev', C.c_void_p), ('space', C.c_void_p), ('mg', C.c_void_p*PNL_IMEX_MAX_COMP),
+                 ('chol_dev', C.c_void_p*PNL_IMEX_MAX_COMP), ('ldchol', C.c_int64*PNL_IMEX_MAX_COMP)])
 
 
 class PnlError(RuntimeError):
@@ -181,6 +198,13 @@ def load():
     L.pnl_potrs.argtypes = [vp, vp, i64, i32, vp, i64, i32]
     L.pnl_getrf.argtypes = [vp, vp, i64, i32, vp, C.POINTER(C.c_int)]
     L.pnl_getrs.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32]
+    L.pnl_csr_cg_jacobi.argtypes = [vp, i32, vp, vp, vp, dbl, vp, vp, dbl, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.pnl_fe_space_create.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp)]
+    L.pnl_fe_space_destroy.argtypes = [vp]
+    L.pnl_assemble_nonlinearity.argtypes = [vp, i32, vp, i32, i32, vp, i64, i32, dbl, dbl, vp, i64]
+    L.pnl_imex_create.argtypes = [vp, C.POINTER(pnl_imex_desc), C.POINTER(vp)]
+    L.pnl_imex_destroy.argtypes = [vp]
+    L.pnl_imex_sweep.argtypes = [vp, vp, vp, vp, vp]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
     L.pnl_upload_sparsity_device.argtypes = [vp, i32, vp, vp]
     L.pnl_set_classes.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -643,6 +667,53 @@ class Context:
     def getrs(self, LU_ptr, ldLU, n, piv_ptr, B_ptr, ldb, nrhs):
         self.check(self.L.pnl_getrs(self.h, C.c_void_p(LU_ptr) if LU_ptr else None, int(ldLU), int(n), C.c_void_p(piv_ptr) if piv_ptr else None,
                                     C.c_void_p(B_ptr) if B_ptr else None, int(ldb), int(nrhs)))
+
+    # -- mass solve, nonlinearities, IMEX sweeps (pnl_solver.hip, pnl_reaction.hip) -----------------
+    def csr_cg_jacobi(self, n, indptr_ptr, indices_ptr, data_ptr, scale, b_ptr, x_ptr, tol, maxiter, x_is_zero=False):
+        it, res = C.c_int(0), C.c_double(0.)
+        self.check(self.L.pnl_csr_cg_jacobi(self.h, int(n), C.c_void_p(indptr_ptr), C.c_void_p(indices_ptr), C.c_void_p(data_ptr), float(scale),
+                                            C.c_void_p(b_ptr), C.c_void_p(x_ptr), float(tol), int(maxiter), int(bool(x_is_zero)),
+                                            C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def _check_strict(self, rc):
+        """like check, but a bad argument is a PnlError (the calls below take user-chosen functions and sizes)"""
+        if rc == PNL_ERR_INVALID:
+            raise PnlError('status {}: {}'.format(rc, self.L.pnl_error_string(self.h).decode()))
+        self.check(rc)
+
+    def fe_space_create(self, dofs, vol, phi, w, ndofs):
+        d, pd = _hp(dofs, np.int32)
+        v, pv = _hp(vol, np.float64)
+        ph, pph = _hp(phi, np.float64)
+        ww, pw = _hp(w, np.float64)
+        assert d.ndim == 2 and v.shape == (d.shape[0],) and ph.shape == (d.shape[1], ww.shape[0])
+        out = C.c_void_p()
+        self._check_strict(self.L.pnl_fe_space_create(self.h, d.shape[0], d.shape[1], ww.shape[0], int(ndofs), pd, pv, pph, pw, C.byref(out)))
+        return out
+
+    def fe_space_destroy(self, space):
+        self.L.pnl_fe_space_destroy(space)
+
+    def assemble_nonlinearity(self, space, fun, params, nin, U_ptr, ldU, nout, alpha, beta, R_ptr, ldR):
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        self._check_strict(self.L.pnl_assemble_nonlinearity(space, int(fun), p.ctypes.data if p.size else None, int(p.size), int(nin),
+                                                            C.c_void_p(U_ptr), int(ldU), int(nout), float(alpha), float(beta),
+                                                            C.c_void_p(R_ptr), int(ldR)))
+
+    def imex_create(self, desc):
+        out = C.c_void_p()
+        self._check_strict(self.L.pnl_imex_create(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def imex_destroy(self, imex):
+        self.L.pnl_imex_destroy(imex)
+
+    def imex_sweep(self, imex, u_prev_ptr, u_ptr, force_ptr, niters):
+        its = np.zeros(int(niters), dtype=np.int32)
+        self._check_strict(self.L.pnl_imex_sweep(imex, C.c_void_p(u_prev_ptr), C.c_void_p(u_ptr), C.c_void_p(force_ptr) if force_ptr else None,
+                                                 its.ctypes.data))
+        return its
 
     def inv_diagonal(self, A_ptr, ldA, n, out_ptr):
         self.check(self.L.pnl_inv_diagonal(self.h, C.c_void_p(A_ptr), int(ldA), int(n), C.c_void_p(out_ptr)))

@@ -241,6 +241,18 @@ k_cg_dir(const double *__restrict__ scal, const double *__restrict__ z, int n, d
     if (i < n) p[i] = __builtin_fma(t, p[i], z[i]);
 }
 
+// dinv[row] = 1 / (scale * M[row][row]) for a CSR matrix (a row without a stored diagonal gives inf: the solve then reports nan)
+__global__ void __launch_bounds__(PNL_NTHREADS)
+k_csr_diag_inv(int n, const int *__restrict__ indptr, const int *__restrict__ indices, const double *__restrict__ data, double scale,
+               double *__restrict__ dinv) {
+    const int row = blockIdx.x*PNL_NTHREADS+threadIdx.x;
+    if (row >= n) return;
+    double d = 0.;
+    for (int k = indptr[row]; k < indptr[row+1]; k++)
+        if (indices[k] == row) d += data[k];
+    dinv[row] = 1./(scale*d);
+}
+
 inline unsigned blocks_for(long long n) { return (unsigned)std::max<long long>(1, (n+PNL_NTHREADS-1)/PNL_NTHREADS); }
 
 int gemv(pnl_context *ctx, const double *A, int64_t ldA, int nrows, int ncols, const double *x, double alpha, double beta, const double *b,
@@ -426,6 +438,65 @@ int pnl_cg_jacobi(pnl_context *ctx, const double *A, int64_t ldA, int n, const d
             if (k == 50) {
                 // recalculate the residual to limit rounding drift (solvers.pyx:412-415)
                 if ((rc = gemv(x, Ap))) return rc;
+                hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(PNL_NTHREADS), 0, st, b, (const double*)Ap, (const double*)dinv, n, r, z);
+                k = 0;
+            }
+            dot(r, z, 2);                                        // beta = r . Br
+            HIPCHK(ctx, hipMemcpyAsync(hs, scal, 3*sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            conv = std::sqrt(hs[2]);
+            if (conv <= tol) break;
+            hipLaunchKernelGGL(k_cg_dir, dim3(gv), dim3(PNL_NTHREADS), 0, st, (const double*)scal, (const double*)z, n, p);
+            // betaOld = beta
+            HIPCHK(ctx, hipMemcpyAsync(scal, scal+2, sizeof(double), hipMemcpyDeviceToDevice, st));
+            k++;
+        }
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (iters) *iters = it;
+    if (residual) *residual = conv;
+    return PNL_OK;
+}
+
+// the loop of pnl_cg_jacobi on (scale M) x = b with the CSR product of pnl_csr_matvec
+int pnl_csr_cg_jacobi(pnl_context *ctx, int n, const int32_t *indptr, const int32_t *indices, const double *data, double scale, const double *b,
+                      double *x, double tol, int maxiter, int x_is_zero, int *iters, double *residual) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (!indptr || !indices || !data || !b || !x || n <= 0 || maxiter < 0 || !(scale > 0.)) return fail(ctx, PNL_ERR_INVALID, "bad csr cg arguments");
+    int rc;
+    for (int i = 0; i < 5; i++)
+        if ((rc = ensure(ctx, ctx->b_vec[i], sizeof(double)*n))) return rc;
+    if ((rc = ensure(ctx, ctx->b_scal, sizeof(double)*4))) return rc;
+    double *r = (double*)ctx->b_vec[0].p, *p = (double*)ctx->b_vec[1].p, *Ap = (double*)ctx->b_vec[2].p,
+           *z = (double*)ctx->b_vec[3].p, *dinv = (double*)ctx->b_vec[4].p, *scal = (double*)ctx->b_scal.p;
+    const int gv = (n+PNL_NTHREADS-1)/PNL_NTHREADS, gd = std::min(gv, 1024);
+    hipStream_t st = ctx->stream;
+    auto dot = [&](const double *u, const double *v, int slot) {
+        (void)hipMemsetAsync(scal+slot, 0, sizeof(double), st);
+        hipLaunchKernelGGL(k_dot, dim3(gd), dim3(PNL_NTHREADS), 0, st, u, v, n, scal+slot);
+    };
+    double hs[4];
+    auto spmv = [&](const double *v, double *out) { return csr(ctx, n, indptr, indices, data, v, scale, 0., out); };
+    hipLaunchKernelGGL(k_csr_diag_inv, dim3(gv), dim3(PNL_NTHREADS), 0, st, n, indptr, indices, data, scale, dinv);
+    if (x_is_zero) {
+        HIPCHK(ctx, hipMemsetAsync(x, 0, sizeof(double)*n, st));
+        HIPCHK(ctx, hipMemsetAsync(Ap, 0, sizeof(double)*n, st));
+    } else if ((rc = spmv(x, Ap))) return rc;
+    hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(PNL_NTHREADS), 0, st, b, (const double*)Ap, (const double*)dinv, n, r, p);
+    dot(r, p, 0);                                                // betaOld = r . Br
+    HIPCHK(ctx, hipMemcpyAsync(hs, scal, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    double conv = std::sqrt(hs[0]);
+    int it = 0, k = 0;
+    if (conv > tol) {
+        for (it = 0; it < maxiter; it++) {
+            if ((rc = spmv(p, Ap))) return rc;
+            dot(p, Ap, 1);
+            hipLaunchKernelGGL(k_cg_update, dim3(gv), dim3(PNL_NTHREADS), 0, st, (const double*)scal, (const double*)p,
+                               (const double*)Ap, (const double*)dinv, n, x, r, z);
+            if (k == 50) {
+                // recalculate the residual to limit rounding drift (solvers.pyx:412-415)
+                if ((rc = spmv(x, Ap))) return rc;
                 hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(PNL_NTHREADS), 0, st, b, (const double*)Ap, (const double*)dinv, n, r, z);
                 k = 0;
             }

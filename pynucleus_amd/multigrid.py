@@ -121,10 +121,11 @@ def _seed_mesh(domain):
 class fractionalHierarchy:
     """Levels 0 .. noRef of uniformly refined meshes with the nonlocal operator assembled on every one of them
     (helpers.py:312-380 with 'assemble': 'ALL').  levels[l] = {'mesh', 'DoFMap', 'A' (Dense_LinearOperator in HBM),
-    'M' (scipy CSR, buildMass), 'P', 'R' (scipy CSR; l > 0)}."""
+    'M' (scipy CSR, buildMass), 'P', 'R' (scipy CSR; l > 0)}.  zeroExterior is passed to the builders: False with tag=NO_BOUNDARY gives
+    the regional (Neumann) operator."""
 
     def __init__(self, domain, noRef, kernel, params=None, element='P1', buildMass=False, tag=None, device=None, mesh=None,
-                 matrixFormat='dense', h2MinDoFs=2000):
+                 matrixFormat='dense', h2MinDoFs=2000, zeroExterior=True):
         from .dofmap import dofmapFactory
         from .mesh import PHYSICAL
         from .builder import nonlocalBuilder
@@ -138,7 +139,7 @@ class fractionalHierarchy:
             if lvl > 0:
                 mesh = mesh.refine()
             dm = dofmapFactory(element, mesh, PHYSICAL if tag is None else tag)
-            b = nonlocalBuilder(dm, kernel, dict(self.params), device=device)
+            b = nonlocalBuilder(dm, kernel, dict(self.params), zeroExterior=zeroExterior, device=device)
             # matrixFormat 'H2': the levels with at least h2MinDoFs DoFs carry the H2 operator (getH2), the coarse ones stay dense
             A = b.getH2() if (matrixFormat.upper() == 'H2' and dm.num_dofs >= h2MinDoFs) else b.getDense()
             b.context().synchronize()

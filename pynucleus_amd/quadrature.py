@@ -168,6 +168,43 @@ class simplexXiaoGimbutas(simplexQuadratureRule):
         self.order = order
 
 
+class Gauss1D(simplexQuadratureRule):
+    """Gauss-Legendre rule on an interval, exact to degree ``order``: ceil((order + 1) / 2) points, barycentric nodes [2, n],
+    weights summing to 1 (the volume rule of the nonlinearity assembly in 1D: order 3, two points)."""
+
+    def __init__(self, order, dim=1):
+        k = max((int(order)+2)//2, 1)
+        x, w = np.polynomial.legendre.leggauss(k)                  # on [-1, 1], weights summing to 2
+        lam = 0.5*(1.+x)
+        super().__init__(np.stack([1.-lam, lam]), 0.5*w, dim, 1)
+        self.order = 2*k-1
+
+
+class Gauss2D(simplexQuadratureRule):
+    """Symmetric rules on a triangle, barycentric nodes [3, n], weights summing to 1.  order <= 2: the three edge midpoints with
+    weights 1/3; order <= 5: Radon's seven points -- the centroid with weight 9/40 and two orbits (a, a, 1 - 2a) with
+    a = (6 -+ sqrt(15))/21 and weights (155 -+ sqrt(15))/1200."""
+
+    def __init__(self, order, dim=2):
+        order = int(order)
+        if order <= 2:
+            nodes = np.array([[.5, .5, 0.], [0., .5, .5], [.5, 0., .5]]).T
+            weights = np.full(3, 1./3.)
+            self.order = 2
+        elif order <= 5:
+            r = np.sqrt(15.)
+            cols, wts = [[1./3., 1./3., 1./3.]], [9./40.]
+            for a, w in (((6.-r)/21., (155.-r)/1200.), ((6.+r)/21., (155.+r)/1200.)):
+                b = 1.-2.*a
+                cols += [[b, a, a], [a, b, a], [a, a, b]]
+                wts += [w, w, w]
+            nodes, weights = np.array(cols).T, np.array(wts)
+            self.order = 5
+        else:
+            raise NotImplementedError('Gauss2D of order {}: orders up to 5 are tabulated'.format(order))
+        super().__init__(nodes, weights, dim, 2)
+
+
 class doubleSimplexQuadratureRule(quadratureRule):
     def __init__(self, rule1, rule2):
         self.rule1 = rule1
