@@ -313,6 +313,19 @@ int pnl_tile_order_ready(pnl_context *ctx);
 // pnl_hip.hip: what pnl_h2_setup (pnl_h2.hip) shares with the assemblies of a constant or piecewise constant order -- kernels, order
 // formulas and rules are set, the tables derived from mesh and DoF map exist (finalize), the problem description holds the current class
 int pnl_assembly_prepare(pnl_context *ctx);
+// its two halves: the checks with finalize; the problem description of the class / orientation ctx->cur / ctx->orient (launches nothing)
+int pnl_assembly_ready(pnl_context *ctx);
+void pnl_refresh_tables(pnl_context *ctx);
+// pnl_hip.hip: counting sort of a work list by order (k_wl_hist / _scan / _scatter): histogram, offsets, 16-pair chunk offsets and cursors
+// of the bins, PNL_WL_BINS + 1 words each, carved out of aux_base
+struct WlBins { unsigned *hist, *offs, *coff, *cursor; };
+int pnl_wl_sort(pnl_context *ctx, const int4 *wl, const unsigned *count, unsigned cap, unsigned *aux_base, int4 *sorted, WlBins &B);
+// pnl_hip.hip: the per-cell diagonal blocks D into the dense matrix (k_scatter_diag<ctx->dpe>, dpe 2, 3 or 6)
+void pnl_scatter_diag(pnl_context *ctx, const DevProblem &P, const double *D, double *A, int64_t ldA);
+// pnl_hip.hip, host only: the one order <= qlimit of all cell pairs of the tile (block ta, block tb), 0 where that cannot be proved
+int pnl_tile_uniform_order(const pnl_context *ctx, const pnl_order_formula &F, int ta, int tb, int qlimit);
+// pnl_sparse.hip: pnl_assembly_ready, the uploaded pattern and the output checked, pnl_refresh_tables, S filled in -- in that order
+int pnl_sparse_ready(pnl_context *ctx, double *data, double *diag, SparseOut &S);
 
 // pnl_hip.hip / pnl_pwnear.hip: kernels with an order per quadrature point
 int pnl_pw_prepare(pnl_context *ctx, int need_boundary);

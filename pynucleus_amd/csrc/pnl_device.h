@@ -148,6 +148,14 @@ struct PwDev {
     long long sv_stride;        // ncp
 };
 
+// CSR / SSS target of the pair assemblies (sparse_add, pnl_kernels.h; host side: pnl_sparse_ready, pnl_context.h)
+struct SparseOut {
+    const int *indptr, *indices;
+    double *data, *diag;
+    const int *pairs;                    // [np][2] cell pairs, c1 <= c2
+    const unsigned long long *masks;     // [np][4] requested entries of the symmetric local matrix (256-bit MASK_t)
+};
+
 // block-slot storage of the one-sided operator (pnl_tile2.h)
 struct SlotOut {
     double *A2;                 // block-slot storage (nullptr: flush with atomics into A)

@@ -1,5 +1,6 @@
 // Internal, host only: runtime value -> template argument.  f receives std::integral_constants and returns the launcher's code.
-// Needs pnl_context.h only, so that a unit without the kernels of pnl_kernels.h (pnl_h2.hip) can include it; pnl_launch.h brings it.
+// Needs pnl_context.h only and names no kernel, so that a unit without the kernels of pnl_kernels.h (pnl_h2.hip) can include it;
+// pnl_launch.h, whose templates do name those kernels, brings it.
 #pragma once
 #include <type_traits>
 

@@ -5,7 +5,6 @@
 // pnl_kernels.h on one HIP stream.  No Python or torch types cross this boundary.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -14,7 +13,6 @@
 #include <vector>
 #include "pnl_hip.h"
 #include "pnl_kernels.h"
-#include "pnl_pointwise.h"
 #include "pnl_bndtile.h"
 
 #include <thread>
@@ -534,25 +532,47 @@ void refresh_tables(pnl_context *ctx) {
 }
 
 
+// A <- A + A^T on the strict off-diagonal (cross contributions were written on one side only)
+__global__ void __launch_bounds__(PNL_NTHREADS)
+k_mirror(double *__restrict__ A, long long ldA, int N) {
+    __shared__ double t1[32][33], t2[32][33];
+    const int nb = (N+31)/32;
+    // linear block id over the upper block triangle
+    int bid = blockIdx.x;
+    int bi = 0;
+    {
+        // solve bi from bid = bi*nb - bi(bi-1)/2 + (bj-bi)
+        double fb = ((2.*nb+1.)-sqrt((2.*nb+1.)*(2.*nb+1.)-8.*bid))*0.5;
+        bi = (int)fb;
+        while (bi > 0 && (long long)bi*nb-(long long)bi*(bi-1)/2 > bid) bi--;
+        while ((long long)(bi+1)*nb-(long long)(bi+1)*bi/2 <= bid) bi++;
+    }
+    const int bj = bi+(bid-(int)((long long)bi*nb-(long long)bi*(bi-1)/2));
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
+    for (int r = ty; r < 32; r += 8) {
+        const int I = bi*32+r, J = bj*32+tx;
+        t1[r][tx] = (I < N && J < N) ? A[(long long)I*ldA+J] : 0.;
+        const int I2 = bj*32+r, J2 = bi*32+tx;
+        t2[r][tx] = (I2 < N && J2 < N) ? A[(long long)I2*ldA+J2] : 0.;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+        const int I = bi*32+r, J = bj*32+tx;
+        if (I < N && J < N) {
+            if (bi != bj) A[(long long)I*ldA+J] = t1[r][tx]+t2[tx][r];
+            else if (r != tx) A[(long long)I*ldA+J] = t1[r][tx]+t1[tx][r];
+        }
+        const int I2 = bj*32+r, J2 = bi*32+tx;
+        if (bi != bj && I2 < N && J2 < N) A[(long long)I2*ldA+J2] = t2[r][tx]+t1[tx][r];
+    }
+}
+
 // the per-cell diagonal blocks D (packed upper triangles, cells of P) into the dense matrix / into the sparse data
 template <int DPE>
 void scatter_diag(pnl_context *ctx, const DevProblem &P, const double *D, double *A, int64_t ldA) {
     const long long nt = (long long)ctx->nc*DPE*DPE;
     hipLaunchKernelGGL((k_scatter_diag<DPE>), dim3((unsigned)((nt+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0, ctx->stream, P, D,
                        A, (long long)ldA);
-}
-template <int DPE>
-void scatter_diag_sparse(pnl_context *ctx, const double *D, const SparseOut &S) {
-    const long long n = (long long)ctx->nc*(DPE*(DPE+1)/2);
-    hipLaunchKernelGGL((k_scatter_diag_sparse<DPE>), dim3((unsigned)((n+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0, ctx->stream,
-                       ctx->P, D, ctx->nc, S);
-}
-
-// end of an assembly path that skips its later phases: their events, so that the phase timers read zero
-int finish_events(pnl_context *ctx, int from) {
-    for (int e = from; e < 8; e++) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
-    ctx->ev_valid = true; ctx->tiles_launched = true;
-    return PNL_OK;
 }
 
 template <int DIM, int DPE, int KT>
@@ -629,49 +649,6 @@ struct ClassFork {
     ~ClassFork() { join(); }
 };
 
-// dynamic LDS of the work-list kernels: the rule copy (+ for P2 the column sums of the PNL_NTHREADS / 16 pairs of a chunk) of
-// k_worklist_sorted; for P2 the per-lane column sums of k_worklist_lane (eval_distant_blocked)
-template <int DPE>
-static int wl_tab_max(int wl_kb) {
-    // points of the largest rule that is staged; larger rules are read from global memory, point pair by point pair (slow: at 49,152
-    // P2 cells of the 12-sector disc, s = 0.7, 100,000 near pairs take the rules of 240 and 256 points -- 6e9 of the 13e9 kernel values
-    // of the work lists).  P2 (one workgroup per CU for its registers anyway): 320 ... 512 points, 80 + 128 bytes of LDS per point.
-    const int t = (wl_kb*1024)/((4+DPE)*(int)sizeof(double));
-    return wl_csum_lds(DPE) ? std::max(320, std::min(t, 512)) : t;
-}
-template <int DPE>
-static size_t wl_sorted_lds(int tab_max) {
-    return sizeof(double)*((size_t)tab_max*(4+DPE)+(wl_csum_lds(DPE) ? (size_t)(PNL_NTHREADS/16)*tab_max : 0));
-}
-template <typename F>
-static size_t wl_lane_lds(F fun, int dpe, int kt) {
-    const size_t b = wl_lane_blocked(dpe, kt) ? sizeof(double)*PNL_WL_LANE_MAXPTS*PNL_NTHREADS : 0;
-    if (b) (void)hipFuncSetAttribute((const void*)fun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-    return b;
-}
-
-// sorted evaluation of a work list: the orders with at most PNL_WL_LANE_MAXPTS points one pair per lane (k_worklist_lane, if
-// `lane`), the others 16 lanes per pair with the rule in LDS (k_worklist_sorted; bins nmin .. last_bin).  kb_option / kb_default:
-// KB of LDS for the rule copy; rules with more points are read from global memory.  18 KB are 8 workgroups per CU
-// (60 KB / 2 workgroups per CU was 0.6 ms slower at 98,304 cells in the dense path and 4 ms at C4 in the cluster path)
-template <int DIM, int DPE, int KT, bool SPARSE>
-int worklist_eval(pnl_context *ctx, const char *kb_option, int kb_default, const int4 *sorted, const WlBins &B, double *A, int64_t ldA,
-                  double *D, const SparseOut &S, const ClusterTiles &CT, int last_bin, int nmin, bool lane, int lane_flags) {
-    const int wl_kb = pnl_tune(kb_option) ? std::max(4, atoi(pnl_tune(kb_option))) : kb_default;
-    const int tab_max = wl_tab_max<DPE>(wl_kb);
-    const int wl_grid = 256*std::max(1, std::min(8, 150/(wl_kb+(KT == 0 ? 3 : 0))));      // KT == 0: + 3 KB of power tables
-    const size_t lds = wl_sorted_lds<DPE>(tab_max);
-    auto wfun = k_worklist_sorted<DIM, DPE, KT, SPARSE>;
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)wfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (lane)
-        hipLaunchKernelGGL((k_worklist_lane<DIM, DPE, KT, SPARSE>), dim3(256*4), dim3(PNL_NTHREADS), wl_lane_lds(k_worklist_lane<DIM, DPE, KT, SPARSE>, DPE, KT), ctx->stream, ctx->P,
-                           sorted, (const unsigned*)B.offs, A, (long long)ldA, D, S, lane_flags, CT);
-    hipLaunchKernelGGL(wfun, dim3(wl_grid), dim3(PNL_NTHREADS), lds, ctx->stream, ctx->P, sorted, (const unsigned*)B.offs,
-                       (const unsigned*)B.coff, A, (long long)ldA, D, tab_max, S, last_bin, nmin, CT);
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
-}
-
 // counting sort of a work-list region by order, then the sorted evaluation;
 // region: which copy of the sort buffers to use (passes that may run concurrently need their own)
 template <int DIM, int DPE, int KT>
@@ -682,7 +659,7 @@ int run_worklist(pnl_context *ctx, const int4 *wl, const unsigned *wlc, unsigned
     if ((rc = ensure(ctx, ctx->b_wlaux, sizeof(unsigned)*(4*(PNL_WL_BINS+1))*nregions))) return rc;
     const int4 *wlsorted = (const int4*)ctx->b_wlsorted.p+(size_t)region*cap;
     WlBins B;
-    if ((rc = wl_sort(ctx, wl, wlc, cap, (unsigned*)ctx->b_wlaux.p+(size_t)region*4*(PNL_WL_BINS+1), (int4*)wlsorted, B))) return rc;
+    if ((rc = pnl_wl_sort(ctx, wl, wlc, cap, (unsigned*)ctx->b_wlaux.p+(size_t)region*4*(PNL_WL_BINS+1), (int4*)wlsorted, B))) return rc;
     int dbg = 0;
 #ifdef PNL_DEBUG_ABLATE
     dbg = pnl_tune("PNL_WL_DBG") ? atoi(pnl_tune("PNL_WL_DBG")) : 0;
@@ -767,30 +744,6 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
         ctx->fold_event_set = true;
     }
     return run_worklist<DIM, DPE, KT>(ctx, (const int4*)ctx->b_wl.p, wlc, ctx->wl_cap_each, A, ldA, ctx->symflush || SO.A2 != nullptr);
-}
-
-// touching pairs (k_singular_pairs): the rule of the slot staged in LDS if it needs at most 150 KB, else read from global memory;
-// at most 256 * min(workgroups per CU, 4) workgroups, fewer if `want` (the site's own count) is smaller; INT_MAX selects that
-// fixed grid (the sparse path, whose pairs are counted on the device)
-template <int DIM, int DPE, int SLOT, int KT, bool SPARSE>
-int launch_singular_pairs(pnl_context *ctx, int want, const int2 *pairs, int np, double *A, int64_t ldA, int cell_begin, int cell_end,
-                          const SparseOut &S, const int4 *sorted, const unsigned *offs, const ClusterTiles &CT) {
-    const int M = ctx->P.sM[SLOT], rows = ctx->P.sRows[SLOT];
-    const size_t lds = sizeof(double)*(size_t)(2*(DIM+1)+1+rows)*M;
-    const bool stage = lds <= 150*1024;
-    const int per_cu = stage ? std::max(1, (int)((160*1024)/std::max<size_t>(lds, 1))) : 4;
-    const int grid = std::min(want, 256*std::min(per_cu, 4));
-    auto launch = [&](auto kfun, size_t bytes) {
-        hipLaunchKernelGGL(kfun, dim3(grid), dim3(PNL_SING_THREADS), bytes, ctx->stream, ctx->P, pairs, np, A, (long long)ldA, cell_begin,
-                           cell_end, S, sorted, offs, CT);
-    };
-    if (stage) {
-        auto kfun = k_singular_pairs<DIM, DPE, SLOT, KT, true, SPARSE>;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        launch(kfun, lds);
-    } else launch(k_singular_pairs<DIM, DPE, SLOT, KT, false, SPARSE>, 0);
-    HIPCHK(ctx, hipGetLastError());
-    return PNL_OK;
 }
 
 template <int DIM, int DPE, int KT>
@@ -1185,62 +1138,6 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
     return PNL_OK;
 }
 
-// ---- masked pair assembly into CSR / SSS (assembleClusters) --------------------------------------------------------
-// classify == false: the work list b_mp_wl[0..np) has been filled on the device (k_fh_pairs)
-template <int DIM, int DPE, int KT>
-int pairs_masked_impl(pnl_context *ctx, int np, const SparseOut &S, bool classify = true, bool first = true, bool keepD = false) {
-    int rc;
-    if ((rc = ensure(ctx, ctx->b_mp_wl, (size_t)np*sizeof(int4)))) return rc;
-    if ((rc = ensure(ctx, ctx->b_mp_sorted, (size_t)np*sizeof(int4)))) return rc;
-    if ((rc = ensure(ctx, ctx->b_mp_aux, sizeof(unsigned)*(4*(PNL_WL_BINS+1)+1)))) return rc;
-    unsigned *count = (unsigned*)ctx->b_mp_aux.p+4*(PNL_WL_BINS+1);      // behind the four bin arrays of wl_sort
-    int4 *wl = (int4*)ctx->b_mp_wl.p, *sorted = (int4*)ctx->b_mp_sorted.p;
-    const unsigned unp = (unsigned)np;
-    HIPCHK(ctx, hipMemcpyAsync(count, &unp, sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // unp lives on this stack frame
-    if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    if (classify)
-        hipLaunchKernelGGL((k_mp_classify<DIM, DPE>), dim3((np+PNL_NTHREADS-1)/PNL_NTHREADS), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
-                           S.pairs, np, wl);
-    WlBins B;
-    if ((rc = wl_sort(ctx, wl, count, unp, (unsigned*)ctx->b_mp_aux.p, sorted, B))) return rc;
-    hipLaunchKernelGGL(k_mp_stats, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, ctx->P, (const unsigned*)B.hist);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    {
-        // no masks (getSparse): diagonal blocks through the per-cell buffer, one scatter per cell at the end
-        constexpr int ND = DPE*(DPE+1)/2;
-        double *Dbuf = S.masks ? nullptr : (double*)ctx->b_D.p;
-        if (Dbuf && !keepD) HIPCHK(ctx, hipMemsetAsync(Dbuf, 0, sizeof(double)*(size_t)ctx->ncp*ND, ctx->stream));      // keepD: the tiles of a finite horizon have been there
-        // 60 KB of rule copy and the bins up to PNL_MAXQ: differences from the dense path that are kept, not decided
-        const int nmin = ctx->wl_lane ? PNL_WL_LANE_MAXPTS+1 : 0;
-        if ((rc = worklist_eval<DIM, DPE, KT, true>(ctx, "PNL_WL_MP_KB", 60, sorted, B, nullptr, 0, Dbuf, S, ClusterTiles{}, PNL_MAXQ, nmin,
-                                                    ctx->wl_lane, 0))) return rc;
-        if (Dbuf) scatter_diag_sparse<DPE>(ctx, Dbuf, S);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    // touching pairs: bins 121 (common vertex), 122 (common edge / identical in 1D), 123 (identical in 2D)
-    unsigned hh[PNL_WL_BINS+1];
-    HIPCHK(ctx, hipMemcpyAsync(hh, B.hist, sizeof(hh), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int s = 0; s < DIM+1; s++)
-        if (hh[121+s] && !ctx->C().have_sing[0][s]) return fail(ctx, PNL_ERR_STATE, "singular rule for %d common vertices not uploaded", s+1);
-    for (int s = 0; s < DIM+1; s++)
-        if (hh[121+s] && (rc = with_slot<DIM>(s, [&](auto slot) {
-                // the pairs come from the sorted list: the fixed grid of the sparse path, whatever their number
-                return launch_singular_pairs<DIM, DPE, decltype(slot)::value, KT, true>(ctx, INT_MAX, nullptr, 0, nullptr, 0, 0, 0, S, sorted, B.offs,
-                                                                                        ClusterTiles{});
-            }))) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    ctx->ev_valid = true;
-    ctx->tiles_launched = true;
-    return PNL_OK;
-}
-
 template <int DIM, int DPE>
 int boundary_masked_impl(pnl_context *ctx, int ni, double fac, const SparseOut &S) {
     const int grid = std::min((ni+3)/4, 256*8);
@@ -1317,7 +1214,7 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
         if ((rc = ensure(ctx, ctx->b_wlsorted, (size_t)ctx->wl_cap*sizeof(int4)))) return rc;
         if ((rc = ensure(ctx, ctx->b_wlaux, sizeof(unsigned)*(4*(PNL_WL_BINS+1))))) return rc;
         WlBins B;
-        if ((rc = wl_sort(ctx, (const int4*)ctx->b_wl.p, (const unsigned*)ctx->b_wlcount.p, ctx->wl_cap, (unsigned*)ctx->b_wlaux.p,
+        if ((rc = pnl_wl_sort(ctx, (const int4*)ctx->b_wl.p, (const unsigned*)ctx->b_wlcount.p, ctx->wl_cap, (unsigned*)ctx->b_wlaux.p,
                           (int4*)ctx->b_wlsorted.p, B))) return rc;
         // the lane kernel whatever the option PNL_WL_LANE says, and with it nmin: a difference from the other two paths that is kept, not decided
         if ((rc = worklist_eval<DIM, DPE, KT, false>(ctx, "PNL_WL_CL_KB", 18, (const int4*)ctx->b_wlsorted.p, B, nullptr, 0, nullptr, SparseOut{},
@@ -1430,11 +1327,111 @@ int dispatch(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, int nt
 
 }  // namespace
 
-// other translation units (pnl_h2.hip): see pnl_context.h
+// other translation units (pnl_h2.hip, pnl_sparse.hip, pnl_pwnear.hip): see pnl_context.h
+int pnl_assembly_ready(pnl_context *ctx) {
+    int rc;
+    if ((rc = check_ready(ctx))) return rc;
+    return finalize(ctx);
+}
+void pnl_refresh_tables(pnl_context *ctx) { refresh_tables(ctx); }
 int pnl_assembly_prepare(pnl_context *ctx) {
     int rc;
-    if ((rc = check_ready(ctx)) || (rc = finalize(ctx))) return rc;
+    if ((rc = pnl_assembly_ready(ctx))) return rc;
     refresh_tables(ctx);
+    return PNL_OK;
+}
+void pnl_scatter_diag(pnl_context *ctx, const DevProblem &P, const double *D, double *A, int64_t ldA) {
+    if (ctx->dpe == 2) scatter_diag<2>(ctx, P, D, A, ldA);
+    else if (ctx->dpe == 3) scatter_diag<3>(ctx, P, D, A, ldA);
+    else scatter_diag<6>(ctx, P, D, A, ldA);
+}
+
+// counting sort of a work list by order (WlBins: pnl_context.h)
+__global__ void __launch_bounds__(PNL_NTHREADS)
+k_wl_hist(const int4 *__restrict__ wl, const unsigned *__restrict__ wl_count, unsigned wl_cap, unsigned *__restrict__ hist) {
+    __shared__ unsigned h[PNL_WL_BINS];
+    if (threadIdx.x < PNL_WL_BINS) h[threadIdx.x] = 0;
+    __syncthreads();
+    const unsigned count = min(*wl_count, wl_cap);
+    for (unsigned i = blockIdx.x*PNL_NTHREADS+threadIdx.x; i < count; i += gridDim.x*PNL_NTHREADS)
+        atomicAdd(&h[(wl[i].w >> 16) & (PNL_WL_BINS-1)], 1u);
+    __syncthreads();
+    if (threadIdx.x < PNL_WL_BINS && h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+
+// offs[q] = first sorted position of order q, chunk_off[q] = first 16-pair chunk of order q; both have PNL_WL_BINS+1 entries
+__global__ void k_wl_scan(const unsigned *__restrict__ hist, unsigned *__restrict__ offs, unsigned *__restrict__ chunk_off,
+                          unsigned *__restrict__ cursor) {
+    if (threadIdx.x == 0) {
+        unsigned run = 0, crun = 0;
+        for (int q = 0; q < PNL_WL_BINS; q++) {
+            offs[q] = run; chunk_off[q] = crun; cursor[q] = 0;
+            run += hist[q]; crun += (hist[q]+15)/16;
+        }
+        offs[PNL_WL_BINS] = run; chunk_off[PNL_WL_BINS] = crun;
+    }
+}
+
+// Stable within a wave's slice: every wave owns a contiguous part of its workgroup's input range and hands out positions in
+// input order (ballot ranks), so runs of consecutive entries with one key stay consecutive.  The producers append whole
+// waves of neighbouring pairs (k_fh_pairs: 64 consecutive cells c1 against one c2), and the consumers run 64 consecutive
+// sorted entries per wave: coalesced cell data, neighbouring pattern rows, shared cells that can be summed over the wave.
+__global__ void __launch_bounds__(PNL_NTHREADS)
+k_wl_scatter(const int4 *__restrict__ wl, const unsigned *__restrict__ wl_count, unsigned wl_cap, const unsigned *__restrict__ offs,
+             unsigned *__restrict__ cursor, int4 *__restrict__ sorted) {
+    constexpr int NW = PNL_NTHREADS/64;
+    __shared__ unsigned h[NW][PNL_WL_BINS], base[NW][PNL_WL_BINS];
+    const unsigned count = min(*wl_count, wl_cap);
+    const unsigned per = (count+gridDim.x-1)/gridDim.x;
+    const unsigned b0 = blockIdx.x*per, b1 = min(count, b0+per);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned perw = ((b1 > b0 ? b1-b0 : 0u)+NW-1)/NW;
+    const unsigned i0 = min(b1, b0+wave*perw), i1 = min(b1, i0+perw);
+    const unsigned long long lt = (1ull << lane)-1ull;
+    for (int t = threadIdx.x; t < NW*PNL_WL_BINS; t += PNL_NTHREADS) (&h[0][0])[t] = 0;
+    __syncthreads();
+    // pass 1: keys per wave slice; pass 2 hands out positions with the same loop
+    auto sweep = [&](bool place) {
+        for (unsigned i = i0; i < i1; i += 64) {
+            const bool act = i+lane < i1;
+            int4 e = make_int4(0, 0, 0, 0);
+            if (act) e = wl[i+lane];
+            const int q = act ? ((e.w >> 16) & (PNL_WL_BINS-1)) : -1;
+            unsigned long long todo = __ballot(act);
+            while (todo) {
+                const int leader = __ffsll((long long)todo)-1;
+                const int qL = __builtin_amdgcn_readlane(q, leader);
+                const unsigned long long same = __ballot(q == qL);
+                if (place) {
+                    const unsigned start = base[wave][qL]+h[wave][qL];          // the wave is the only writer of its row
+                    if (q == qL) sorted[start+__popcll(same & lt)] = e;
+                }
+                __builtin_amdgcn_wave_barrier();
+                if (lane == leader) h[wave][qL] += (unsigned)__popcll(same);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                todo &= ~same;
+            }
+        }
+    };
+    sweep(false);
+    __syncthreads();
+    if (threadIdx.x < PNL_WL_BINS) {
+        unsigned tot = 0;
+        for (int w = 0; w < NW; w++) tot += h[w][threadIdx.x];
+        unsigned run = tot ? offs[threadIdx.x]+atomicAdd(&cursor[threadIdx.x], tot) : 0u;
+        for (int w = 0; w < NW; w++) { base[w][threadIdx.x] = run; run += h[w][threadIdx.x]; h[w][threadIdx.x] = 0; }
+    }
+    __syncthreads();
+    sweep(true);
+}
+
+int pnl_wl_sort(pnl_context *ctx, const int4 *wl, const unsigned *count, unsigned cap, unsigned *aux_base, int4 *sorted, WlBins &B) {
+    B.hist = aux_base; B.offs = B.hist+(PNL_WL_BINS+1); B.coff = B.offs+(PNL_WL_BINS+1); B.cursor = B.coff+(PNL_WL_BINS+1);
+    HIPCHK(ctx, hipMemsetAsync(B.hist, 0, sizeof(unsigned)*(PNL_WL_BINS+1), ctx->stream));
+    hipLaunchKernelGGL(k_wl_hist, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, count, cap, B.hist);
+    hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(64), 0, ctx->stream, (const unsigned*)B.hist, B.offs, B.coff, B.cursor);
+    hipLaunchKernelGGL(k_wl_scatter, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, count, cap, (const unsigned*)B.offs, B.cursor, sorted);
     return PNL_OK;
 }
 
@@ -1447,7 +1444,7 @@ int pnl_assembly_prepare(pnl_context *ctx) {
 // f >= num_min/den_max > q-1 for ONE role (for all pairs of the tile) gives order >= q.  dmin > hmax_a + hmax_b also rules
 // out shared vertices (a vertex is closer than 2/3 h to its cell's centre).  Anything not provably uniform goes to the
 // general kernel, whose per-pair formula decides.
-static int tile_uniform_order(const pnl_context *ctx, const pnl_order_formula &F, int ta, int tb, int qlimit) {
+int pnl_tile_uniform_order(const pnl_context *ctx, const pnl_order_formula &F, int ta, int tb, int qlimit) {
     if (ta == tb) return 0;
     const auto &A = ctx->blocks[ta], &B = ctx->blocks[tb];
     if (!A.full || !B.full || !(F.e >= 0.) || !(F.den0 > 0.)) return 0;
@@ -1476,269 +1473,6 @@ static int tile_uniform_order(const pnl_context *ctx, const pnl_order_formula &F
         }
     return 0;
 }
-static bool tile_is_uniform(const pnl_context *ctx, const pnl_order_formula &F, int ta, int tb) { return tile_uniform_order(ctx, F, ta, tb, 2) == 2; }
-
-namespace {
-template <int DIM, int DPE>
-int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, int cell_begin, int cell_end, int npairs,
-                   int nbpairs) {
-    // P1: tile kernels with LDS sub-blocks (k_pw_tile, k_pw_mixed, k_pw_lane).  P2 (FL2:894-1184 is element-agnostic): every
-    // distant pair through classification, the sorted work list and k_pw_distant (16 lanes per pair, global atomics)
-    constexpr int NV = DIM+1, ND = DPE*(DPE+1)/2, ST = 4+DPE;
-    constexpr bool P1el = DPE == NV;
-    const bool P1 = P1el && ctx->pw.type != 5;           // a P1 order function (type 5) is known per cell: the generic kernels
-    int rc;
-    DevProblem &P = ctx->P;
-    P.qmax = ctx->qmax;
-    P.off = (const int*)ctx->b_off.p; P.bary = (const double*)ctx->b_bary.p; P.w = (const double*)ctx->b_w.p;
-    P.phi = (const double*)ctx->b_phi.p; P.foff = (const int*)ctx->b_foff.p; P.fbary = (const double*)ctx->b_fbary.p;
-    P.fw = (const double*)ctx->b_fw.p;
-    P.cur_class = -1;
-    const PwDev &W = ctx->pw;
-    HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->b_D.p, 0, sizeof(double)*(size_t)ctx->ncp*ND, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    ctx->tiles_launched = true; ctx->pure_launched = false;
-    const int nbk = (ctx->nc+63)/64;
-    {
-        // work list: only the pairs whose rule has more than 16 points arrive there when the tiles evaluate the others
-        // themselves (overflow is detected by pnl_get_counters); the tile-less variant lists every pair of the cell range
-        double pairs = 0.;
-        for (long long c = cell_begin; c < cell_end; c++) pairs += (double)(ctx->nc-c);
-        const bool tiles_evaluate = P1 && ctx->tile == 64 && !pnl_tune("PNL_PW_NOMIXED");
-        const size_t want = tiles_evaluate ? (size_t)std::min<double>(std::max<double>(pairs*0.1, 1 << 20), 400e6)
-                                           : (size_t)std::max<double>(pairs, 1024.);
-        if (want > 1500000000ull) return fail(ctx, PNL_ERR_UNSUPPORTED, "%zu pairs exceed the work list of the pointwise path", want);
-        if (ctx->wl_cap < want) {
-            if ((rc = ensure(ctx, ctx->b_wl, want*sizeof(int4)))) return rc;
-            ctx->wl_cap = (unsigned)want;
-        }
-        if ((rc = ensure(ctx, ctx->b_wlsorted, (size_t)ctx->wl_cap*sizeof(int4)))) return rc;
-        if ((rc = ensure(ctx, ctx->b_wlcount, sizeof(unsigned)*PNL_WL_SLOTS))) return rc;
-        if ((rc = ensure(ctx, ctx->b_wlaux, sizeof(unsigned)*(4*(PNL_WL_BINS+1))))) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));
-        ctx->wl_slots = 1; ctx->wl_cap_each = ctx->wl_cap;
-    }
-    // block tiles of the upper triangle: uniform ones (every pair provably of order 2 for every pair order in the range of
-    // the two blocks) go to k_pw_tile, the others through classification and the sorted work list
-    std::vector<int2> mixed, uniform;
-    {
-        const int T = 64;
-        std::vector<double> smin(nbk, 1e300), smax(nbk, -1e300);
-        for (int c = 0; c < ctx->nc; c++) {
-            const int b = c/T;
-            smin[b] = std::min(smin[b], ctx->pw_cell_smax[c]); smax[b] = std::max(smax[b], ctx->pw_cell_smax[c]);
-        }
-        auto formula = [&](double sv) {
-            pnl_order_formula F;
-            std::memset(&F, 0, sizeof(F));
-            F.c0 = W.c0;
-            if (DIM == 2) { F.a = sv-1.; F.b = 1.; F.e = sv; F.den0 = 0.4; } else { F.a = 2.*sv-1.; F.b = 0.; F.e = 2.*sv; F.den0 = 0.8; }
-            return F;
-        };
-        const bool allow = P1 && ctx->tile == T && ctx->qmax >= 2 && !pnl_tune("PNL_PW_NOTILE");
-        const int a0 = cell_begin/T, a1 = (cell_end+T-1)/T;
-        for (int d = 0; d < nbk; d++)
-            for (int a = a0; a < a1 && a+d < nbk; a++) {
-                const int b = a+d;
-                // the pair order max(m_c1, m_c2) lies between the larger of the block minima and the larger of the maxima; the
-                // formula is linear in it, so the two end points bound it
-                const double lo = std::max(smin[a], smin[b]), hi = std::max(smax[a], smax[b]);
-                bool u = allow && a*T >= cell_begin && (a+1)*T <= cell_end && tile_is_uniform(ctx, formula(lo), a, b) &&
-                         tile_is_uniform(ctx, formula(hi), a, b);
-                (u ? uniform : mixed).push_back(make_int2(a, b));
-            }
-        std::vector<int2> all(mixed);
-        all.insert(all.end(), uniform.begin(), uniform.end());
-        if ((rc = upload(ctx, ctx->b_tiles, all.data(), all.size()))) return rc;
-        ctx->tiles_cached.clear(); ctx->tiles_cb = -1;            // b_tiles no longer holds the dense tile list
-    }
-    if constexpr (P1el) if (P1 && !uniform.empty()) {
-        const int acc_stride = ctx->nU+1;
-        constexpr int NP = DIM == 2 ? 3 : 2;
-        const size_t lds = sizeof(double)*(64*NP*DIM+2*64*NP+64+2*64*ND)+sizeof(int)*(64*DPE+64)
-                           +2*sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
-        auto tfun = k_pw_tile<DIM>;
-        const PersistentGrid g = persistent_grid(ctx, tfun, PNL_NTHREADS, lds, (int)uniform.size(), 1);
-        if (g.rc) return g.rc;
-        hipLaunchKernelGGL(tfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int2*)ctx->b_tiles.p+mixed.size(),
-                           (int)uniform.size(), A, (long long)ldA, (double*)ctx->b_D.p, acc_stride);
-        HIPCHK(ctx, hipGetLastError());
-        ctx->pure_launched = true;
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-    // the other tiles: classification, in-tile evaluation of the rules with at most 16 points (LDS sub-blocks), work list for the rest
-    const bool in_tile = P1 && ctx->tile == 64 && !pnl_tune("PNL_PW_NOMIXED");
-    if constexpr (P1el) if (!mixed.empty() && in_tile) {
-        const int acc_stride = ctx->nU+1;
-        const size_t lds = sizeof(double)*(PNL_PW_LANE_MAXPTS*ST+64*PNL_PW_LANE_MAXPTS*2+2*64*ND)+sizeof(unsigned short)*64*64
-                           +sizeof(int)*(3*PNL_PW_NBUCK+2*64*DPE)+2*sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
-        if (lds > 160*1024) return fail(ctx, PNL_ERR_UNSUPPORTED, "a block of 64 cells touches %d DoFs: LDS sub-blocks of %zu bytes exceed 160 KiB", ctx->nU, lds);
-        auto mfun = k_pw_mixed<DIM>;
-        const PersistentGrid g = persistent_grid(ctx, mfun, PNL_NTHREADS, lds, (int)mixed.size(), 1);
-        if (g.rc) return g.rc;
-        if ((rc = ensure(ctx, ctx->b_tilectr, sizeof(unsigned)))) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
-        hipLaunchKernelGGL(mfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int2*)ctx->b_tiles.p, (int)mixed.size(), A,
-                           (long long)ldA, (double*)ctx->b_D.p, acc_stride, (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, ctx->wl_cap,
-                           cell_begin, cell_end, (unsigned*)ctx->b_tilectr.p);
-    }
-    if (!mixed.empty() && !in_tile)
-        hipLaunchKernelGGL((k_pw_classify<DIM, DPE>), dim3((unsigned)mixed.size()), dim3(PNL_NTHREADS), 0, ctx->stream, P, W,
-                           (const int2*)ctx->b_tiles.p, (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, ctx->wl_cap, cell_begin, cell_end);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    {
-        WlBins B;
-        if ((rc = wl_sort(ctx, (const int4*)ctx->b_wl.p, (const unsigned*)ctx->b_wlcount.p, ctx->wl_cap, (unsigned*)ctx->b_wlaux.p,
-                          (int4*)ctx->b_wlsorted.p, B))) return rc;
-        hipLaunchKernelGGL(k_pw_stats, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, P, (const unsigned*)B.hist);
-        // LDS: rule table + order / scaling of the second cell's points for the 16 pairs of a chunk
-        const int tab_max = 256;
-        const size_t lds = sizeof(double)*((size_t)tab_max*ST+(size_t)(PNL_NTHREADS/16)*tab_max*2);
-        auto kfun = k_pw_distant<DIM, DPE>;
-        HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const bool lane_kernel = P1 && !pnl_tune("PNL_PW_NOLANE");      // (with the in-tile evaluation only the rules of more than 16 points arrive here)
-        if constexpr (P1el) if (lane_kernel)
-            hipLaunchKernelGGL((k_pw_lane<DIM>), dim3(256*2), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, (const int4*)ctx->b_wlsorted.p,
-                               (const unsigned*)B.offs, A, (long long)ldA, (double*)ctx->b_D.p);
-        hipLaunchKernelGGL(kfun, dim3(256*4), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int4*)ctx->b_wlsorted.p,
-                           (const unsigned*)B.offs, A, (long long)ldA, (double*)ctx->b_D.p, tab_max, lane_kernel ? PNL_PW_LANE_MAXPTS+1 : 0, PwNear{});
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    if (npairs > 0) {
-        const unsigned grid = (unsigned)((2ll*npairs*64+PNL_NTHREADS-1)/PNL_NTHREADS);
-        const int4 *pp = (const int4*)ctx->b_pw_pairs.p;
-        hipLaunchKernelGGL((k_pw_singular<DIM, DPE, 0>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, pp, npairs, A, (long long)ldA, cell_begin, cell_end, PwNear{}, (const int*)nullptr);
-        hipLaunchKernelGGL((k_pw_singular<DIM, DPE, 1>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, pp, npairs, A, (long long)ldA, cell_begin, cell_end, PwNear{}, (const int*)nullptr);
-        if (DIM == 2)
-            hipLaunchKernelGGL((k_pw_singular<DIM, DPE, (DIM == 2 ? 2 : 1)>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, pp, npairs, A, (long long)ldA, cell_begin, cell_end, PwNear{}, (const int*)nullptr);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    if (zero_exterior && cell_end > cell_begin) {
-        const int ncell = cell_end-cell_begin, gx = (ncell+PNL_NTHREADS-1)/PNL_NTHREADS;
-        int per = 16;
-        while (per > 1 && (long long)gx*((ctx->nb+per-1)/per) < 4096) per >>= 1;
-        hipLaunchKernelGGL((k_pw_boundary_distant<DIM, DPE>), dim3(gx, (ctx->nb+per-1)/per), dim3(PNL_NTHREADS), 0, ctx->stream, P, W,
-                           (double*)ctx->b_D.p, cell_begin, cell_end, per);
-        if (nbpairs > 0) {
-            const unsigned grid = (unsigned)(((long long)nbpairs*64+PNL_NTHREADS-1)/PNL_NTHREADS);
-            const int4 *bp = (const int4*)ctx->b_pw_bpairs.p;
-            hipLaunchKernelGGL((k_pw_boundary_singular<DIM, DPE, 0>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, bp, nbpairs, (double*)ctx->b_D.p, cell_begin, cell_end);
-            if (DIM == 2)
-                hipLaunchKernelGGL((k_pw_boundary_singular<DIM, DPE, (DIM == 2 ? 1 : 0)>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, bp, nbpairs, (double*)ctx->b_D.p, cell_begin, cell_end);
-        }
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    scatter_diag<DPE>(ctx, P, (const double*)ctx->b_D.p, A, ldA);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    ctx->ev_valid = true;
-    return PNL_OK;
-}
-}  // namespace
-
-// getSparse without a host pair list: block tiles the horizon can reach -> k_fh_pairs -> the sorted pipeline of the masked path
-namespace {
-template <int DIM, int DPE, int KT>
-int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
-    int rc;
-    const int T = ctx->tile, nbk = ctx->nblocks;
-    const double delta = std::sqrt(ctx->C().kern[0].horizon2);
-    const bool whole = cell_begin <= 0 && cell_end >= ctx->nc;
-    std::vector<int2> tiles;
-    for (int a = 0; a < nbk; a++)
-        for (int b = a; b < nbk; b++) {
-            // a range of first cells (the reference's cellNo1 split, NA:1280-1285): only block rows that hold one
-            if ((a+1)*T <= cell_begin || a*T >= cell_end) continue;
-            const auto &A = ctx->blocks[a], &B = ctx->blocks[b];
-            const double dx = A.tcx-B.tcx, dy = A.tcy-B.tcy;
-            // every vertex of a block lies within trad of (tcx, tcy) (vertices within h of their cell's centre)
-            if (std::sqrt(dx*dx+dy*dy)-A.trad-B.trad <= delta) tiles.push_back(make_int2(a, b));
-        }
-    if ((rc = upload(ctx, ctx->b_tiles, tiles.data(), tiles.size()))) return rc;
-    ctx->tiles_cached.clear(); ctx->tiles_cb = -1;            // b_tiles no longer holds the dense tile list
-    const size_t per_tile = (size_t)T*T, chunk_tiles = std::max<size_t>(1, (size_t)(48u << 20)/per_tile);
-    const size_t cap = std::min(tiles.size(), chunk_tiles)*per_tile;
-    if ((rc = ensure(ctx, ctx->b_mp_pairs, cap*sizeof(int2)))) return rc;
-    if ((rc = ensure(ctx, ctx->b_mp_wl, cap*sizeof(int4)))) return rc;
-    if ((rc = ensure(ctx, ctx->b_wlcount, sizeof(unsigned)*PNL_WL_SLOTS))) return rc;
-    ctx->wl_slots = 1; ctx->wl_cap_each = (unsigned)cap;
-    S.pairs = (const int*)ctx->b_mp_pairs.p;
-    S.masks = nullptr;
-    unsigned long long total = 0;
-    bool first = true;
-    // The pairs inside the horizon are integrated by the tile kernel (LDS sub-block, one pattern search per sub-block entry
-    // instead of one per pair and entry); what it cannot do itself -- pairs cut by the horizon, touching pairs, orders
-    // without a packed rule -- it hands to the sorted sparse pipeline through the far list.  PNL_FH_NOTILES=1 keeps the
-    // pair generator k_fh_pairs, which sends every pair down that pipeline.
-    constexpr int TILE = (DPE == 6 || (DIM == 1 && DPE == 3)) ? 32 : 64, ND = DPE*(DPE+1)/2;
-    using TS = TileSmem<DIM, DPE, TILE, KT == 0>;
-    const int acc_stride = acc_stride_of(ctx->nU, TS::fixed_bytes);
-    const size_t lds = TS::fixed_bytes+sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
-    // piecewise-constant order: the candidate pairs of a chunk once (k_fh_pairs), then the sorted pipeline once per order class and
-    // orientation, whose classification keeps the pairs of the class (like pnl_assemble_pairs_masked)
-    const bool var = ctx->nlab > 0;
-    const bool use_tiles = T == TILE && lds <= 160*1024 && !pnl_tune("PNL_FH_NOTILES") && !var;
-    if (!use_tiles && !whole) return fail(ctx, PNL_ERR_UNSUPPORTED, "a range of first cells needs the tile route of the finite-horizon assembly");
-    ctx->visited_is_assembled = use_tiles;
-    for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk_tiles) {
-        const int nt = (int)std::min(chunk_tiles, tiles.size()-t0);
-        HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));
-        if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        if (use_tiles) {
-            auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false, true>;
-            const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT, true), lds, nt, 2);
-            if (g.rc) return g.rc;
-            if ((rc = ensure(ctx, ctx->b_tilectr, sizeof(unsigned)))) return rc;
-            HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
-            HIPCHK(ctx, hipMemsetAsync(ctx->b_D.p, 0, sizeof(double)*(size_t)ctx->ncp*ND, ctx->stream));
-            ClusterTiles CT{};
-            CT.S = S;
-            CT.wl_ds = (int2*)ctx->b_mp_pairs.p;                   // the pairs of the far-list entries
-            SlotOut SOk{};
-            SOk.nU = ctx->nU;                                      // rows of the LDS sub-block
-            hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT, true)), lds, ctx->stream, ctx->P, (const int2*)ctx->b_tiles.p+t0,
-                               (double*)nullptr, 0ll, (double*)ctx->b_D.p, std::max(cell_begin, 0), std::min(cell_end, ctx->nc), acc_stride, (int4*)ctx->b_mp_wl.p,
-                               (unsigned*)ctx->b_wlcount.p, (unsigned)cap, 0, nt, CT, (unsigned*)ctx->b_tilectr.p, SOk);
-        } else
-            hipLaunchKernelGGL((k_fh_pairs<DIM, DPE>), dim3(nt), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, (const int2*)ctx->b_tiles.p+t0, T,
-                               (int2*)ctx->b_mp_pairs.p, (int4*)ctx->b_mp_wl.p, (unsigned*)ctx->b_wlcount.p, (unsigned)cap);
-        HIPCHK(ctx, hipGetLastError());
-        unsigned np = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&np, ctx->b_wlcount.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (np > cap) return fail(ctx, PNL_ERR_STATE, "far list of the finite-horizon tiles overflowed (%u > %zu)", np, cap);
-        total += np;
-        if (np && var) {
-            const int ncls = (int)ctx->cls.size(), norient = ctx->nonsym ? 2 : 1, cur0 = ctx->cur;
-            for (int ko = 0; ko < ncls*norient && !rc; ko++) {
-                ctx->cur = ko/norient; ctx->orient = ko%norient;
-                refresh_tables(ctx);
-                rc = pairs_masked_impl<DIM, DPE, 0>(ctx, (int)np, S, true, false, false);
-            }
-            ctx->cur = cur0; ctx->orient = 0;
-            refresh_tables(ctx);
-            if (rc) return rc;
-        } else
-        if (np && (rc = pairs_masked_impl<DIM, DPE, KT>(ctx, (int)np, S, false, false, use_tiles))) return rc;
-        if (!np && use_tiles) {
-            // no far entries in this chunk: the diagonal blocks of its tiles still have to reach the matrix
-            scatter_diag_sparse<DPE>(ctx, (const double*)ctx->b_D.p, S);
-            if ((rc = finish_events(ctx, 1))) return rc;
-        }
-        first = false;
-    }
-    ctx->visited_pairs = total;
-    if (total == 0 && (rc = finish_events(ctx, 1))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));     // pnl_get_counters reads it as the dense work-list fill
-    return PNL_OK;
-}
-}  // namespace
 
 // ---- options (pnl_context.h: pnl_tune) --------------------------------------------------------------------------------------
 #include <deque>
@@ -2245,7 +1979,7 @@ static int upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_beg
                     if (!has) { qof[i] = -1; continue; }
                     single = blk_labels[t.x].size() == 1 && blk_labels[t.y].size() == 1;
                 }
-                int q = (allow && single) ? tile_uniform_order(ctx, forms[k], t.x, t.y, qlimit) : 0;
+                int q = (allow && single) ? pnl_tile_uniform_order(ctx, forms[k], t.x, t.y, qlimit) : 0;
                 if (q == 2 && !q2ok) q = 0;
                 // the cell range of the MPI-style split applies to the a-cells: only blocks entirely inside qualify
                 if (q && filter && !(t.x*T >= cell_begin && (t.x+1)*T <= cell_end)) q = 0;
@@ -2456,7 +2190,7 @@ int pnl_block_row_costs(pnl_context *ctx, double *out, int n) {
             for (int a = t; a < nb; a += nthreads) {
                 double c = w_cells;
                 for (int b = a; b < nb; b++) {
-                    const int q = allow ? tile_uniform_order(ctx, F, a, b, qlimit) : 0;
+                    const int q = allow ? pnl_tile_uniform_order(ctx, F, a, b, qlimit) : 0;
                     c += q == 2 ? 1. : (q ? w_uni3 : w_mixed);
                 }
                 out[a] = c;
@@ -2503,120 +2237,6 @@ int pnl_assemble_dense_tiles(pnl_context *ctx, double *A, int64_t ldA, int zero_
     return rc;
 }
 
-int pnl_upload_sparsity(pnl_context *ctx, int nnz, const int32_t *indptr, const int32_t *indices) {
-    if (!ctx) return PNL_ERR_INVALID;
-    if (!ctx->have_dofs) return fail(ctx, PNL_ERR_STATE, "upload the DoF map first");
-    if (nnz < 0 || !indptr || (nnz && !indices) || indptr[0] != 0 || indptr[ctx->N] != nnz)
-        return fail(ctx, PNL_ERR_INVALID, "bad sparsity pattern (nnz=%d)", nnz);
-    for (int i = 0; i < ctx->N; i++) {
-        if (indptr[i+1] < indptr[i]) return fail(ctx, PNL_ERR_INVALID, "indptr is not monotone at row %d", i);
-        for (int t = indptr[i]; t < indptr[i+1]; t++)
-            if (indices[t] < 0 || indices[t] >= ctx->N || (t > indptr[i] && indices[t] <= indices[t-1]))
-                return fail(ctx, PNL_ERR_INVALID, "row %d of the pattern is not sorted / in range", i);
-    }
-    int rc;
-    if ((rc = upload(ctx, ctx->b_sp_indptr, indptr, (size_t)ctx->N+1))) return rc;
-    if ((rc = upload(ctx, ctx->b_sp_indices, indices, (size_t)nnz))) return rc;
-    ctx->sp_nnz = nnz;
-    return PNL_OK;
-}
-
-int pnl_upload_sparsity_device(pnl_context *ctx, int nnz, const int32_t *indptr_dev, const int32_t *indices_dev) {
-    if (!ctx) return PNL_ERR_INVALID;
-    if (!ctx->have_dofs) return fail(ctx, PNL_ERR_STATE, "upload the DoF map first");
-    if (nnz < 0 || !indptr_dev || (nnz && !indices_dev)) return fail(ctx, PNL_ERR_INVALID, "bad sparsity pattern (nnz=%d)", nnz);
-    int rc;
-    if ((rc = ensure(ctx, ctx->b_sp_indptr, sizeof(int32_t)*((size_t)ctx->N+1)))) return rc;
-    if ((rc = ensure(ctx, ctx->b_sp_indices, sizeof(int32_t)*(size_t)std::max(nnz, 1)))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->b_sp_indptr.p, indptr_dev, sizeof(int32_t)*((size_t)ctx->N+1), hipMemcpyDeviceToDevice, ctx->stream));
-    if (nnz) HIPCHK(ctx, hipMemcpyAsync(ctx->b_sp_indices.p, indices_dev, sizeof(int32_t)*(size_t)nnz, hipMemcpyDeviceToDevice, ctx->stream));
-    int32_t ends[2] = {-1, -1};
-    HIPCHK(ctx, hipMemcpyAsync(&ends[0], ctx->b_sp_indptr.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ends[1], (const int32_t*)ctx->b_sp_indptr.p+ctx->N, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ends[0] != 0 || ends[1] != nnz) { ctx->sp_nnz = -1; return fail(ctx, PNL_ERR_INVALID, "bad sparsity pattern: indptr runs from %d to %d, nnz=%d", ends[0], ends[1], nnz); }
-    ctx->sp_nnz = nnz;
-    return PNL_OK;
-}
-
-static int sparse_ready(pnl_context *ctx, double *data, double *diag, SparseOut &S) {
-    int rc;
-    if ((rc = check_ready(ctx))) return rc;
-    if ((rc = finalize(ctx))) return rc;
-    if (ctx->sp_nnz < 0) return fail(ctx, PNL_ERR_STATE, "upload the sparsity pattern first");
-    if (!data && ctx->sp_nnz > 0) return fail(ctx, PNL_ERR_INVALID, "null output");
-    refresh_tables(ctx);
-    S.indptr = (const int*)ctx->b_sp_indptr.p; S.indices = (const int*)ctx->b_sp_indices.p;
-    S.data = data; S.diag = diag;
-    S.pairs = (const int*)ctx->b_mp_pairs.p; S.masks = (const unsigned long long*)ctx->b_mp_masks.p;
-    return PNL_OK;
-}
-
-int pnl_assemble_pairs_masked(pnl_context *ctx, int np, const int32_t *pairs, const uint64_t *masks, double *data, double *diag) {
-    if (!ctx) return PNL_ERR_INVALID;
-    if (np < 0 || (np && !pairs)) return fail(ctx, PNL_ERR_INVALID, "bad pair list");
-    for (int i = 0; i < np; i++)
-        if (pairs[2*i] < 0 || pairs[2*i] > pairs[2*i+1] || pairs[2*i+1] >= ctx->nc)
-            return fail(ctx, PNL_ERR_INVALID, "pair %d = (%d, %d) is not an ordered pair of cells", i, pairs[2*i], pairs[2*i+1]);
-    int rc;
-    if ((rc = upload(ctx, ctx->b_mp_pairs, pairs, (size_t)2*np))) return rc;
-    if (masks && (rc = upload(ctx, ctx->b_mp_masks, masks, (size_t)4*np))) return rc;
-    if (!std::isinf(ctx->C().kern[0].horizon2) && ctx->qmax > PNL_CUT_SHIFT)
-        return fail(ctx, PNL_ERR_UNSUPPORTED, "finite horizon: upload distant rules up to order %d at most", PNL_CUT_SHIFT);
-    SparseOut S;
-    if ((rc = sparse_ready(ctx, data, diag, S))) return rc;
-    if (!masks) S.masks = nullptr;               // every entry of every pair is requested
-    HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
-    ctx->visited_pairs = (unsigned long long)np; ctx->visited_is_assembled = false;
-    if (np == 0) return PNL_OK;
-    // variable order (piecewise constant, symmetric table): the pair list once per class, k_mp_classify keeps the pairs of the
-    // class (the interface terms of NA:1966-2156 are boundary items, pnl_assemble_boundary_masked after pnl_select_class)
-    // non-symmetric class table (NA:1776-1840 with symmetricCells == False): the listed pairs (c1 <= c2) once per orientation, each
-    // with the class of its orientation and half the kernel (the machinery applies the factor 2 of the symmetric case); the masks
-    // of (c1, c2) and (c2, c1) request the same DoF pairs, so the list of the symmetric case serves both
-    const int ncls = ctx->nlab > 0 ? (int)ctx->cls.size() : 1, cur0 = ctx->cur;
-    const int norient = (ctx->nlab > 0 && ctx->nonsym) ? 2 : 1;
-    for (int ko = 0; ko < ncls*norient; ko++) {
-        const int k = ko/norient;
-        ctx->orient = ko%norient;
-        if (ctx->nlab > 0) { ctx->cur = k; refresh_tables(ctx); }
-        const bool fast = ctx->P.k.fast != 0, first = ko == 0;
-        rc = with_shape(ctx, [&](auto D, auto E) {
-            constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;
-            return with_kt_2d<DIM>(fast, [&](auto kt) { return pairs_masked_impl<DIM, DPE, decltype(kt)::value>(ctx, np, S, true, first); });
-        });
-        if (rc) break;
-    }
-    ctx->cur = cur0; ctx->orient = 0;
-    if (norient > 1) refresh_tables(ctx);
-    return rc;
-}
-
-int pnl_assemble_pairs_in_horizon(pnl_context *ctx, double *data, double *diag) {
-    return pnl_assemble_pairs_in_horizon_range(ctx, data, diag, 0, ctx ? ctx->nc : 0);
-}
-
-int pnl_assemble_pairs_in_horizon_range(pnl_context *ctx, double *data, double *diag, int cell_begin, int cell_end) {
-    if (!ctx) return PNL_ERR_INVALID;
-    if (cell_begin < 0 || cell_end > ctx->nc || cell_begin > cell_end) return fail(ctx, PNL_ERR_INVALID, "bad cell range");
-    int rc;
-    if ((rc = check_ready(ctx))) return rc;
-    if ((rc = finalize(ctx))) return rc;
-    // (a non-symmetric order table would need the pairs the horizon cuts re-triangulated with the roles of the two cells swapped in the
-    // second orientation, NA:1418 swapCells: the cut evaluation of the sorted pipeline takes the listed order)
-    if (ctx->nlab > 0 && ctx->nonsym) return fail(ctx, PNL_ERR_UNSUPPORTED, "finite horizon with a non-symmetric order table");
-    if (std::isinf(ctx->C().kern[0].horizon2)) return fail(ctx, PNL_ERR_STATE, "pnl_assemble_pairs_in_horizon needs a finite horizon");
-    if (ctx->qmax > PNL_CUT_SHIFT) return fail(ctx, PNL_ERR_UNSUPPORTED, "finite horizon: upload distant rules up to order %d at most", PNL_CUT_SHIFT);
-    SparseOut S;
-    if ((rc = sparse_ready(ctx, data, diag, S))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
-    const bool fast = ctx->P.k.fast != 0;
-    return with_shape(ctx, [&](auto D, auto E) {
-        constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;
-        return with_kt_2d<DIM>(fast, [&](auto kt) { return horizon_impl<DIM, DPE, decltype(kt)::value>(ctx, S, cell_begin, cell_end); });
-    });
-}
-
 int pnl_assemble_boundary_masked(pnl_context *ctx, int ni, const int32_t *cells, const int32_t *facets, const uint32_t *masks,
                                  double fac, double *data, double *diag) {
     if (!ctx) return PNL_ERR_INVALID;
@@ -2635,7 +2255,7 @@ int pnl_assemble_boundary_masked(pnl_context *ctx, int ni, const int32_t *cells,
     if ((rc = upload(ctx, ctx->b_bi_facets, facets, (size_t)ni*ctx->dim))) return rc;
     if ((rc = upload(ctx, ctx->b_bi_masks, masks, (size_t)ni))) return rc;
     SparseOut S;
-    if ((rc = sparse_ready(ctx, data, diag, S))) return rc;
+    if ((rc = pnl_sparse_ready(ctx, data, diag, S))) return rc;
     if (ni == 0) return PNL_OK;
     return with_shape(ctx, [&](auto D, auto E) { return boundary_masked_impl<decltype(D)::value, decltype(E)::value>(ctx, ni, fac, S); });
 }
@@ -2646,7 +2266,7 @@ int pnl_assemble_clusters_tiled(pnl_context *ctx, const pnl_cluster_plan *pl, in
     if (!std::isinf(ctx->C().kern[0].horizon2)) return fail(ctx, PNL_ERR_UNSUPPORTED, "tiled cluster assembly: infinite horizon only");
     int rc;
     SparseOut S;
-    if ((rc = sparse_ready(ctx, data, diag, S))) return rc;
+    if ((rc = pnl_sparse_ready(ctx, data, diag, S))) return rc;
     if (pl->tile != ctx->tile) return fail(ctx, PNL_ERR_INVALID, "plan built for tiles of %d cells, the kernels use %d", pl->tile, ctx->tile);
     if (pl->npairs < 0 || pl->ntiles < 0 || pl->num_dslots < 0 || pl->chunk_stride < 1) return fail(ctx, PNL_ERR_INVALID, "bad plan sizes");
     const int T = pl->tile, dim = ctx->dim, dpe = ctx->dpe;
@@ -2816,8 +2436,8 @@ int pnl_upload_pointwise_rules(pnl_context *ctx, int which, int panel, int nkeys
 
 }  // extern "C"
 
-// what every assembly with an order per quadrature point needs before its first launch (pnl_assemble_dense_pointwise here, the
-// near-field entry points in pnl_pwnear.hip): padded cell tables, the per-cell / per-facet largest orders and the vertex values of
+// what every assembly with an order per quadrature point needs before its first launch (the entry points are in
+// pnl_pwnear.hip; nothing is launched here): padded cell tables, the per-cell / per-facet largest orders and the vertex values of
 // a P1 order function on the device, the distant rules in the problem description
 int pnl_pw_prepare(pnl_context *ctx, int need_boundary) {
     int rc;
@@ -2857,36 +2477,6 @@ int pnl_pw_prepare(pnl_context *ctx, int need_boundary) {
 }
 
 extern "C" {
-
-int pnl_assemble_dense_pointwise(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, int cell_begin, int cell_end,
-                                 int npairs, const int32_t *pairs, int nbpairs, const int32_t *bpairs) {
-    if (!ctx) return PNL_ERR_INVALID;
-    int rc;
-    if ((rc = pnl_pw_prepare(ctx, zero_exterior))) return rc;
-    if (!A || ldA < ctx->N) return fail(ctx, PNL_ERR_INVALID, "bad output matrix (ldA=%lld, num_dofs=%d)", (long long)ldA, ctx->N);
-    if (cell_begin < 0 || cell_end > ctx->nc || cell_begin > cell_end) return fail(ctx, PNL_ERR_INVALID, "bad cell range");
-    if (npairs < 0 || nbpairs < 0 || (npairs && !pairs) || (nbpairs && !bpairs)) return fail(ctx, PNL_ERR_INVALID, "bad pair lists");
-    for (int t = 0; t < npairs; t++) {
-        const int32_t *q = pairs+4*(size_t)t;
-        if (q[0] < 0 || q[1] < q[0] || q[1] >= ctx->nc || q[2] < 1 || q[2] > ctx->dim+1 || q[3] < 0 || q[3] >= ctx->pw_nkeys[0])
-            return fail(ctx, PNL_ERR_INVALID, "bad touching pair %d", t);
-    }
-    for (int t = 0; t < nbpairs; t++) {
-        const int32_t *q = bpairs+4*(size_t)t;
-        if (q[0] < 0 || q[0] >= ctx->nc || q[1] < 0 || q[1] >= ctx->nb || q[2] < 1 || q[2] > ctx->dim || q[3] < 0 || q[3] >= ctx->pw_nkeys[1])
-            return fail(ctx, PNL_ERR_INVALID, "bad touching cell/facet pair %d", t);
-    }
-    if ((rc = upload(ctx, ctx->b_pw_pairs, pairs, (size_t)4*npairs))) return rc;
-    if ((rc = upload(ctx, ctx->b_pw_bpairs, bpairs, (size_t)4*nbpairs))) return rc;
-    unsigned long long visited = 0;
-    for (long long c = cell_begin; c < cell_end; c++) visited += (unsigned long long)(ctx->nc-c);
-    ctx->visited_pairs = visited; ctx->visited_is_assembled = false;
-    if (ctx->dim == 2)
-        return ctx->dpe == 6 ? pointwise_impl<2, 6>(ctx, A, ldA, zero_exterior, cell_begin, cell_end, npairs, nbpairs)
-                             : pointwise_impl<2, 3>(ctx, A, ldA, zero_exterior, cell_begin, cell_end, npairs, nbpairs);
-    return ctx->dpe == 3 ? pointwise_impl<1, 3>(ctx, A, ldA, zero_exterior, cell_begin, cell_end, npairs, nbpairs)
-                         : pointwise_impl<1, 2>(ctx, A, ldA, zero_exterior, cell_begin, cell_end, npairs, nbpairs);
-}
 
 int pnl_get_counters(pnl_context *ctx, int64_t *out, int n) {
     if (!ctx || !out || n <= 0) return PNL_ERR_INVALID;

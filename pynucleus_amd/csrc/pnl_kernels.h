@@ -8,9 +8,10 @@
 //   k_singular_pairs one wave per touching cell pair (common vertex / edge / identical), lanes over
 //                    the Duffy-type quadrature points, butterfly reduction, atomic scatter.
 //   k_boundary_*     Omega x Omega^c term (cell x boundary facet).
-//   k_scatter_diag   adds the per-cell diagonal blocks, k_mirror symmetrises the cross part.
-// Near field only: the H2 far field is pnl_h2.hip, the GEMV / SpMV / CG kernels are in pnl_solver.hip.  pnl_hip.hip, pnl_pwnear.hip
-// and pnl_selftest.hip include this file; every non-template kernel here is compiled into each of them.
+//   k_scatter_diag   adds the per-cell diagonal blocks (k_mirror, which symmetrises the cross part, is in pnl_hip.hip).
+// Near field only: the H2 far field is pnl_h2.hip, the GEMV / SpMV / CG kernels are in pnl_solver.hip.  pnl_hip.hip, pnl_sparse.hip,
+// pnl_pwnear.hip and pnl_selftest.hip include this file: every kernel here is a template, a unit holds the instantiations it launches
+// (the kernels that are no templates stand next to their one launcher: the work-list sort in pnl_hip.hip, k_mp_stats in pnl_sparse.hip).
 //
 // Reference routines restated per kernel are cited at each kernel (paths under
 // /root/reference/nl/PyNucleus_nl; NO = nonlocalOperator_{SCALAR}.pxi, NA = nonlocalAssembly_{SCALAR}.pxi,
@@ -385,12 +386,7 @@ __host__ __device__ constexpr bool wl_lane_blocked(int dpe, int kt) { return dpe
 // CSR or SSS target with the reference's addToEntry semantics (CSR_LinearOperator_{SCALAR}.pxi:150-170,
 // SSS_LinearOperator_{SCALAR}.pxi:104-130): binary search in the row, entries that are not in the pattern are dropped;
 // SSS (diag != nullptr) keeps I > J in data and the diagonal in its own vector.
-struct SparseOut {
-    const int *indptr, *indices;
-    double *data, *diag;
-    const int *pairs;                    // [np][2] cell pairs, c1 <= c2
-    const unsigned long long *masks;     // [np][4] requested entries of the symmetric local matrix (256-bit MASK_t)
-};
+// struct SparseOut: pnl_device.h
 
 __device__ __forceinline__ void sparse_add(const SparseOut &S, int I, int J, double v) {
     if (I < 0 || J < 0) return;
@@ -2069,85 +2065,8 @@ k_fh_pairs(const DevProblem P, const int2 *__restrict__ tiles, int T, int2 *__re
 // ---- work list of the orders the tile kernel does not unroll -------------------------------------------------------
 // entry = (c1, c2, rule offset, n | order << 16).  The list is counting-sorted by order so that a workgroup integrates
 // pairs of ONE order at a time: the rule is staged in LDS once and all 16 pairs of a chunk run the same trip count.
+// (the sort: pnl_wl_sort and its kernels, pnl_hip.hip)
 #define PNL_WL_BINS 128
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_wl_hist(const int4 *__restrict__ wl, const unsigned *__restrict__ wl_count, unsigned wl_cap, unsigned *__restrict__ hist) {
-    __shared__ unsigned h[PNL_WL_BINS];
-    if (threadIdx.x < PNL_WL_BINS) h[threadIdx.x] = 0;
-    __syncthreads();
-    const unsigned count = min(*wl_count, wl_cap);
-    for (unsigned i = blockIdx.x*PNL_NTHREADS+threadIdx.x; i < count; i += gridDim.x*PNL_NTHREADS)
-        atomicAdd(&h[(wl[i].w >> 16) & (PNL_WL_BINS-1)], 1u);
-    __syncthreads();
-    if (threadIdx.x < PNL_WL_BINS && h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
-}
-
-// offs[q] = first sorted position of order q, chunk_off[q] = first 16-pair chunk of order q; both have PNL_WL_BINS+1 entries
-__global__ void k_wl_scan(const unsigned *__restrict__ hist, unsigned *__restrict__ offs, unsigned *__restrict__ chunk_off,
-                          unsigned *__restrict__ cursor) {
-    if (threadIdx.x == 0) {
-        unsigned run = 0, crun = 0;
-        for (int q = 0; q < PNL_WL_BINS; q++) {
-            offs[q] = run; chunk_off[q] = crun; cursor[q] = 0;
-            run += hist[q]; crun += (hist[q]+15)/16;
-        }
-        offs[PNL_WL_BINS] = run; chunk_off[PNL_WL_BINS] = crun;
-    }
-}
-
-// Stable within a wave's slice: every wave owns a contiguous part of its workgroup's input range and hands out positions in
-// input order (ballot ranks), so runs of consecutive entries with one key stay consecutive.  The producers append whole
-// waves of neighbouring pairs (k_fh_pairs: 64 consecutive cells c1 against one c2), and the consumers run 64 consecutive
-// sorted entries per wave: coalesced cell data, neighbouring pattern rows, shared cells that can be summed over the wave.
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_wl_scatter(const int4 *__restrict__ wl, const unsigned *__restrict__ wl_count, unsigned wl_cap, const unsigned *__restrict__ offs,
-             unsigned *__restrict__ cursor, int4 *__restrict__ sorted) {
-    constexpr int NW = PNL_NTHREADS/64;
-    __shared__ unsigned h[NW][PNL_WL_BINS], base[NW][PNL_WL_BINS];
-    const unsigned count = min(*wl_count, wl_cap);
-    const unsigned per = (count+gridDim.x-1)/gridDim.x;
-    const unsigned b0 = blockIdx.x*per, b1 = min(count, b0+per);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned perw = ((b1 > b0 ? b1-b0 : 0u)+NW-1)/NW;
-    const unsigned i0 = min(b1, b0+wave*perw), i1 = min(b1, i0+perw);
-    const unsigned long long lt = (1ull << lane)-1ull;
-    for (int t = threadIdx.x; t < NW*PNL_WL_BINS; t += PNL_NTHREADS) (&h[0][0])[t] = 0;
-    __syncthreads();
-    // pass 1: keys per wave slice; pass 2 hands out positions with the same loop
-    auto sweep = [&](bool place) {
-        for (unsigned i = i0; i < i1; i += 64) {
-            const bool act = i+lane < i1;
-            int4 e = make_int4(0, 0, 0, 0);
-            if (act) e = wl[i+lane];
-            const int q = act ? ((e.w >> 16) & (PNL_WL_BINS-1)) : -1;
-            unsigned long long todo = __ballot(act);
-            while (todo) {
-                const int leader = __ffsll((long long)todo)-1;
-                const int qL = __builtin_amdgcn_readlane(q, leader);
-                const unsigned long long same = __ballot(q == qL);
-                if (place) {
-                    const unsigned start = base[wave][qL]+h[wave][qL];          // the wave is the only writer of its row
-                    if (q == qL) sorted[start+__popcll(same & lt)] = e;
-                }
-                __builtin_amdgcn_wave_barrier();
-                if (lane == leader) h[wave][qL] += (unsigned)__popcll(same);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                todo &= ~same;
-            }
-        }
-    };
-    sweep(false);
-    __syncthreads();
-    if (threadIdx.x < PNL_WL_BINS) {
-        unsigned tot = 0;
-        for (int w = 0; w < NW; w++) tot += h[w][threadIdx.x];
-        unsigned run = tot ? offs[threadIdx.x]+atomicAdd(&cursor[threadIdx.x], tot) : 0u;
-        for (int w = 0; w < NW; w++) { base[w][threadIdx.x] = run; run += h[w][threadIdx.x]; h[w][threadIdx.x] = 0; }
-    }
-    __syncthreads();
-    sweep(true);
-}
 
 // Distant pairs of the high orders from the sorted work list (NO:722-789; few pairs, thousands of point pairs each): a
 // workgroup takes chunks of 16 pairs of one order, one DPP row (16 lanes) per pair; the lanes split the rows of the tensor
@@ -3035,57 +2954,6 @@ k_scatter_diag(const DevProblem P, const double *__restrict__ Dglob, double *__r
     const double v = Dglob[(size_t)c*ND+DPE*lo-(lo*(lo+1) >> 1)+hi];
     const int I = P.cdof[(size_t)a*P.ncp+c], J = P.cdof[(size_t)b*P.ncp+c];
     if (v != 0. && I >= 0 && J >= 0) atomic_add_f64(&A[(long long)I*ldA+J], v);
-}
-
-// A <- A + A^T on the strict off-diagonal (cross contributions were written on one side only)
-__global__ void __launch_bounds__(PNL_NTHREADS)
-k_mirror(double *__restrict__ A, long long ldA, int N) {
-    __shared__ double t1[32][33], t2[32][33];
-    const int nb = (N+31)/32;
-    // linear block id over the upper block triangle
-    int bid = blockIdx.x;
-    int bi = 0;
-    {
-        // solve bi from bid = bi*nb - bi(bi-1)/2 + (bj-bi)
-        double fb = ((2.*nb+1.)-sqrt((2.*nb+1.)*(2.*nb+1.)-8.*bid))*0.5;
-        bi = (int)fb;
-        while (bi > 0 && (long long)bi*nb-(long long)bi*(bi-1)/2 > bid) bi--;
-        while ((long long)(bi+1)*nb-(long long)(bi+1)*bi/2 <= bid) bi++;
-    }
-    const int bj = bi+(bid-(int)((long long)bi*nb-(long long)bi*(bi-1)/2));
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
-    for (int r = ty; r < 32; r += 8) {
-        const int I = bi*32+r, J = bj*32+tx;
-        t1[r][tx] = (I < N && J < N) ? A[(long long)I*ldA+J] : 0.;
-        const int I2 = bj*32+r, J2 = bi*32+tx;
-        t2[r][tx] = (I2 < N && J2 < N) ? A[(long long)I2*ldA+J2] : 0.;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const int I = bi*32+r, J = bj*32+tx;
-        if (I < N && J < N) {
-            if (bi != bj) A[(long long)I*ldA+J] = t1[r][tx]+t2[tx][r];
-            else if (r != tx) A[(long long)I*ldA+J] = t1[r][tx]+t1[tx][r];
-        }
-        const int I2 = bj*32+r, J2 = bi*32+tx;
-        if (bi != bj && I2 < N && J2 < N) A[(long long)I2*ldA+J2] = t2[r][tx]+t1[tx][r];
-    }
-}
-
-// ---- masked pair assembly (assembleClusters, NA:1663-1964): statistics of the sorted pair list ---------------------
-// hist[q] pairs of order q: numAssembledCellPairs, kernel evaluations n(q)^2 each and the order histogram (the touching
-// pairs in bins 121.. are counted by k_singular_pairs itself)
-__global__ void k_mp_stats(const DevProblem P, const unsigned *__restrict__ hist) {
-    const int q = threadIdx.x;
-    if (q < 2 || q > P.qmax || q > PNL_MAXQ) return;
-    const unsigned long long c = hist[q];
-    // pairs cut by a finite horizon sit in bin q + PNL_CUT_SHIFT; their kernel evaluations are counted by the kernel
-    const unsigned long long ccut = (P.k.horizon2 < 1e300 && q+PNL_CUT_SHIFT < PNL_WL_BINS && q <= PNL_CUT_SHIFT) ? hist[q+PNL_CUT_SHIFT] : 0ull;
-    if (!c && !ccut) return;
-    const unsigned long long n = (unsigned long long)(P.off[q+1]-P.off[q]);
-    atomicAdd(&P.counters[8+q], c+ccut);
-    atomicAdd(&P.counters[1], c+ccut);
-    if (c) atomicAdd(&P.counters[2], c*n*n);
 }
 
 // Gauss-theorem boundary term over explicit (cell, facet) items with entry masks: the cluster-local term

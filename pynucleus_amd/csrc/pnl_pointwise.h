@@ -164,18 +164,6 @@ k_pw_classify(const DevProblem P, const PwDev W, const int2 *__restrict__ tiles,
     (void)visited; (void)assembled; (void)evals; // the host knows the number of visited pairs, k_pw_stats counts the rest
 }
 
-// statistics from the histogram of the sorted list: pairs per order, both orientations' kernel evaluations
-__global__ void k_pw_stats(const DevProblem P, const unsigned *__restrict__ hist) {
-    const int q = threadIdx.x;
-    if (q < 2 || q > P.qmax || q > PNL_MAXQ) return;
-    const unsigned long long c = hist[q];
-    if (!c) return;
-    const unsigned long long n = (unsigned long long)(P.off[q+1]-P.off[q]);
-    atomicAdd(&P.counters[8+q], c);
-    atomicAdd(&P.counters[1], c);
-    atomicAdd(&P.counters[2], 2ull*c*n*n);
-}
-
 // ---- distant pairs from the sorted list, rules with more than PNL_PW_LANE_MAXPTS points: 16 lanes per pair split the rows
 // per point pair: L = ln d2 once, K1 = w_i w_j C(s(x_i)) exp(e(x_i) L), K2 = w_i w_j C(s(y_j)) exp(e(y_j) L);
 // order and scaling of the points of the second cell are computed once per pair and kept in LDS.
@@ -1500,18 +1488,6 @@ k_pw_classify_near(const DevProblem P, const PwDev W, const int *__restrict__ pa
             if (pos < wl_cap) wl[pos] = make_int4(c1, c2, item, n | (q << 16));
         }
     }
-}
-
-// statistics of the near-field work list: pairs per order, kernel evaluations of ONE orientation per item
-__global__ void k_pw_stats_near(const DevProblem P, const unsigned *__restrict__ hist) {
-    const int q = threadIdx.x;
-    if (q < 2 || q > P.qmax || q > PNL_MAXQ) return;
-    const unsigned long long c = hist[q];
-    if (!c) return;
-    const unsigned long long n = (unsigned long long)(P.off[q+1]-P.off[q]);
-    atomicAdd(&P.counters[8+q], c);
-    atomicAdd(&P.counters[1], c);
-    atomicAdd(&P.counters[2], c*n*n);
 }
 
 // Gauss-theorem term over explicit (cell, facet) items with the pointwise boundary kernel C(s(x))/s(x) |x-y|^(1-d-2 s(x)), x in the

@@ -68,10 +68,15 @@ def build(d, tmp):
 
 
 def by_symbol(units):
+    """keyed by the demangled name without any `(anonymous namespace)::`, in the kernel's name and in its parameter types: a kernel
+    that moves into or out of an unnamed namespace stays the same kernel"""
+    syms = sorted({k for ks, _ in units.values() for k in ks})
+    names = subprocess.run(['c++filt'], input='\n'.join(syms), capture_output=True, text=True).stdout.split('\n')
+    plain = {k: d.replace('(anonymous namespace)::', '') for k, d in zip(syms, names)}
     sym = {}
     for u, (ks, _) in units.items():
         for k, v in ks.items():
-            sym.setdefault(k, {})[u] = v
+            sym.setdefault(plain[k], {})[u] = v
     return sym
 
 
@@ -85,8 +90,7 @@ def main():
         a, b = old.get(u, ({}, '-')), new.get(u, ({}, '-'))
         print('{:14s} {:4d} -> {:4d} kernels   {} -> {}   {}'.format(u, len(a[0]), len(b[0]), a[1], b[1], 'identical' if a[1] == b[1] else 'CHANGED'))
     so, sn = by_symbol(old), by_symbol(new)
-    names = subprocess.run(['c++filt'], input='\n'.join(sorted(set(so) | set(sn))), capture_output=True, text=True).stdout.split('\n')
-    short = {k: re.sub(r'^void ', '', d)[:110] for k, d in zip(sorted(set(so) | set(sn)), names)}
+    short = {k: re.sub(r'^void ', '', k)[:110] for k in set(so) | set(sn)}
     count = {'same': 0, 'moved': 0, 'copies dropped': 0, 'vanished': 0, 'new': 0, 'pc-relative': 0, 'differs': 0}
     print('== kernels (symbol: units old -> units new)')
     for k in sorted(set(so) | set(sn), key=lambda k: short[k]):
