@@ -26,7 +26,7 @@ class FakePLogger:
 
 
 def tile_cells(dpe, dim=2):
-    """cells per block of the GPU tile kernel (mirrors TILE_P1 / TILE_P2 in csrc/pnl_hip.hip)"""
+    """cells per block of the GPU tile kernel (mirrors TILE_P1 / TILE_P2 in csrc/pnl_context.h)"""
     return 32 if (dpe == 6 or (dim == 1 and dpe == 3)) else 64
 
 
@@ -144,7 +144,7 @@ def label_blocks(dm, labels, max_dofs=None):
     cells carry one label each; a block that straddles an interface makes ALL its tiles multi-class.  Here every straddling block
     is split into one block per label: the fragments of consecutive straddling blocks are merged while they fit (T cells and the
     DoF count of the largest ordinary block, so that the LDS sub-blocks keep their size), and every new block is filled up to T
-    cells with zero-volume copies of its own first cell (in-mesh padding: csrc/pnl_hip.hip finalize()).  Returns a shallow copy
+    cells with zero-volume copies of its own first cell (in-mesh padding: csrc/pnl_setup.hip finalize()).  Returns a shallow copy
     of dm whose mesh has the renumbered + padded cells (DoF numbers unchanged; dofs = -1 and volume 0 for the copies), or dm
     itself when no block straddles."""
     import copy

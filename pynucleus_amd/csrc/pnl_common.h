@@ -120,9 +120,8 @@ __device__ __forceinline__ double pnl_exp_ranged(double y) { return y >= -708. ?
 //   scale x^e = (scale c_j^e) 2^(e k) (1 + u)^e = T[128 + j] T[256 + k + 96] (1 + u)^e,
 // the last factor by its binomial series to u^6 (coefficients C(e, i) of the kernel class in DevKernel::pb; the next term is
 // below 1e-16 for |e| <= 2).  18 operations and three LDS gathers against 36 operations and three L1 gathers of
-// exp(e ln x) above; the tables (PNL_POW_TAB_DOUBLES doubles per exponent, built in long double by pow_table in
-// pnl_hip.hip) are copied to LDS by the kernel.  Exponents of x outside 2^-96 ... 2^31 are clamped (|x - y| < 1e-14).
-#define PNL_POW_TAB_DOUBLES 384
+// exp(e ln x) above; the tables (PNL_POW_TAB_DOUBLES doubles per exponent, pnl_device.h, built in long double by
+// pow_table_values in pnl_setup.hip) are copied to LDS by the kernel.  Exponents of x outside 2^-96 ... 2^31 are clamped (|x - y| < 1e-14).
 __device__ __forceinline__ void pnl_pow_tab_fill(double *dst, const double *__restrict__ src, int tid, int nthreads) {
     if (src) for (int t = tid; t < PNL_POW_TAB_DOUBLES; t += nthreads) dst[t] = src[t];
 }

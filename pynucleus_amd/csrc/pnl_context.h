@@ -11,7 +11,6 @@
 #include "pnl_hip.h"
 #include "pnl_device.h"
 
-
 constexpr int TILE_P1 = 64;     // cells per block for dpe <= 3
 constexpr int TILE_P2 = 32;     // cells per block for dpe == 6 (bigger LDS sub-block per cell)
 
@@ -21,7 +20,6 @@ struct DevBuf {
     ~DevBuf() { release(); }
     void release() { if (p) { (void)hipFree(p); p = nullptr; bytes = 0; } }
 };
-
 
 struct pnl_context {
     int device = 0;
@@ -158,7 +156,6 @@ struct pnl_context {
     bool wl_lane = true;            // debug: PNL_WL_LANE=0 sends every work-list order to the 16-lanes-per-pair kernel
 };
 
-
 inline int fail(pnl_context *ctx, int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
@@ -231,9 +228,11 @@ inline DevKernel to_dev_bkn(pnl_kernel kn, int dim) {
     return d;
 }
 
-// values of the pnl_pow_tab tables of k (PNL_POW_TAB_DOUBLES doubles, scale folded in; pnl_hip.hip); false where the kernel
+// values of the pnl_pow_tab tables of k (PNL_POW_TAB_DOUBLES doubles, scale folded in; pnl_setup.hip); false where the kernel
 // has none (not fractional, or fast without also_fast, or the option PNL_NO_POWTAB)
 bool pow_table_values(const DevKernel &k, bool also_fast, std::vector<double> &tab);
+// pnl_setup.hip: the same tables on the device, one copy per (exponent, scale) of the context; nullptr where there are none
+const double *pnl_pow_table(pnl_context *ctx, const DevKernel &k, bool also_fast = false);
 
 // the order function's part of PwDev (the rest is per mesh: pnl_set_order_function); false: a bad Chebyshev series of the scaling
 inline bool pw_set_function(PwDev &W, const pnl_order_function &f) {
@@ -303,31 +302,37 @@ inline DevProblem with_mixed_rules(const pnl_context *ctx, DevProblem Pt) {
     return Pt;
 }
 
-
 inline void kt_begin(pnl_context *ctx, int slot) { (void)hipEventRecord(ctx->kev[slot][0], ctx->stream); }
 inline void kt_end(pnl_context *ctx, int slot) { (void)hipEventRecord(ctx->kev[slot][1], ctx->stream); ctx->kev_set[slot] = true; }
 
-// pnl_hip.hip: joins the vertex-order search finalize() started and uploads the permuted cell tables (sets have_tile_order)
+// pnl_setup.hip: joins the vertex-order search finalize() started and uploads the permuted cell tables (sets have_tile_order)
 int pnl_tile_order_ready(pnl_context *ctx);
 
-// pnl_hip.hip: what pnl_h2_setup (pnl_h2.hip) shares with the assemblies of a constant or piecewise constant order -- kernels, order
+// pnl_setup.hip: what pnl_h2_setup (pnl_h2.hip) shares with the assemblies of a constant or piecewise constant order -- kernels, order
 // formulas and rules are set, the tables derived from mesh and DoF map exist (finalize), the problem description holds the current class
 int pnl_assembly_prepare(pnl_context *ctx);
 // its two halves: the checks with finalize; the problem description of the class / orientation ctx->cur / ctx->orient (launches nothing)
 int pnl_assembly_ready(pnl_context *ctx);
 void pnl_refresh_tables(pnl_context *ctx);
+// pnl_setup.hip, the tile plan of a dense assembly: the tiles (block a, block b >= a) of a cell range, heavy ones first; which of
+// the caller's tiles are of one order, the lists per class / of the single-launch P2 layout in b_tiles (kept while nothing changes)
+int pnl_make_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin, int cell_end);
+int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin, int cell_end);
+// pnl_hip.hip, for pnl_upload_tiles: k_tile_order_range<ctx->tile> over the ncand tiles in b_candtiles, one order (or 0) each into
+// host_out through b_candq; synchronises the stream
+int pnl_tile_order_range(pnl_context *ctx, const DevFormula &qo, int ncand, signed char *host_out);
 // pnl_hip.hip: counting sort of a work list by order (k_wl_hist / _scan / _scatter): histogram, offsets, 16-pair chunk offsets and cursors
 // of the bins, PNL_WL_BINS + 1 words each, carved out of aux_base
 struct WlBins { unsigned *hist, *offs, *coff, *cursor; };
 int pnl_wl_sort(pnl_context *ctx, const int4 *wl, const unsigned *count, unsigned cap, unsigned *aux_base, int4 *sorted, WlBins &B);
 // pnl_hip.hip: the per-cell diagonal blocks D into the dense matrix (k_scatter_diag<ctx->dpe>, dpe 2, 3 or 6)
 void pnl_scatter_diag(pnl_context *ctx, const DevProblem &P, const double *D, double *A, int64_t ldA);
-// pnl_hip.hip, host only: the one order <= qlimit of all cell pairs of the tile (block ta, block tb), 0 where that cannot be proved
+// pnl_setup.hip: the one order <= qlimit of all cell pairs of the tile (block ta, block tb), 0 where that cannot be proved
 int pnl_tile_uniform_order(const pnl_context *ctx, const pnl_order_formula &F, int ta, int tb, int qlimit);
 // pnl_sparse.hip: pnl_assembly_ready, the uploaded pattern and the output checked, pnl_refresh_tables, S filled in -- in that order
 int pnl_sparse_ready(pnl_context *ctx, double *data, double *diag, SparseOut &S);
 
-// pnl_hip.hip / pnl_pwnear.hip: kernels with an order per quadrature point
+// pnl_setup.hip / pnl_pwnear.hip: kernels with an order per quadrature point
 int pnl_pw_prepare(pnl_context *ctx, int need_boundary);
 int pnl_pw_h2_interp(pnl_context *ctx);
 

@@ -7,6 +7,10 @@
 #define PNL_MAXQ 120            // nonlocalOperator.pyx:107 MAX_PANEL
 #define PNL_NCOUNTERS 134
 #define PNL_WL_SLOTS 256          // work-list fill counters: one per order class / class pass of an assembly
+#define PNL_WL_BINS 128           // bins of the counting sort of a work list by order (pnl_wl_sort)
+#define PNL_POW_TAB_DOUBLES 384   // doubles of the tables of pnl_pow_tab (pnl_common.h) per exponent
+#define PNL_TT_MAXPTS 96          // points of the rules the tile kernel keeps in LDS (DevProblem::tt_tab)
+#define PNL_GEN_MAXPTS 16         // other orders with at most this many points are integrated in the tile kernel too (list C)
 
 struct DevKernel {
     int ktype;                  // 0 fractional, 1 indicator, 2 peridynamic

@@ -446,8 +446,8 @@ __device__ __forceinline__ bool pair_has(const ClusterTiles &CT, int k, int I, i
 // ---------------------------------------------------------------------------------------------
 // Tile kernel: classification (NO:280-378 vertex test, NO:493-540 + FL2:622-642 order) and distant
 // evaluation for one TILE x TILE block of cell pairs.
-#define PNL_TT_MAXPTS 96
-#define PNL_GEN_MAXPTS 16      // other orders with at most this many points are integrated in the tile kernel too (list C)
+// PNL_TT_MAXPTS points of the packed rules in LDS, orders with at most PNL_GEN_MAXPTS points through the generic loop:
+// both constants are in pnl_device.h (the host packs the rules by them)
 #define PNL_GEN_MAXCHUNKS 128
 // Pairs whose order is not one of the two unrolled point counts but has at most PNL_GEN_MAXPTS points (orders 5-8 on
 // triangles, 92 % of the remaining pairs) stay in the tile as list C: it is counting-sorted by order in LDS so that a wave
@@ -1186,7 +1186,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
 
 // ---------------------------------------------------------------------------------------------
 // Uniform tiles: every one of the 64 x 64 cell pairs of the tile is a distant pair of the lowest order (host-side
-// conservative bound on the order formula over the two blocks, see classify_tiles in pnl_hip.hip) -- two thirds of all
+// conservative bound on the order formula over the two blocks, see pnl_tile_uniform_order in pnl_setup.hip) -- two thirds of all
 // pairs at noRef 6, more on finer meshes.  No classification, no lists: lane = cell i of block a, the four waves split the
 // cells j of block b, so everything that depends on j alone (its quadrature points, volume, DoF slots) is a broadcast LDS
 // read, the points of cell i and the row sums that feed its diagonal block stay in registers for the whole tile, and the
@@ -2065,8 +2065,8 @@ k_fh_pairs(const DevProblem P, const int2 *__restrict__ tiles, int T, int2 *__re
 // ---- work list of the orders the tile kernel does not unroll -------------------------------------------------------
 // entry = (c1, c2, rule offset, n | order << 16).  The list is counting-sorted by order so that a workgroup integrates
 // pairs of ONE order at a time: the rule is staged in LDS once and all 16 pairs of a chunk run the same trip count.
-// (the sort: pnl_wl_sort and its kernels, pnl_hip.hip)
-#define PNL_WL_BINS 128
+// (the sort: pnl_wl_sort and its kernels, pnl_hip.hip; its PNL_WL_BINS bins: pnl_device.h)
+
 
 // Distant pairs of the high orders from the sorted work list (NO:722-789; few pairs, thousands of point pairs each): a
 // workgroup takes chunks of 16 pairs of one order, one DPP row (16 lanes) per pair; the lanes split the rows of the tensor

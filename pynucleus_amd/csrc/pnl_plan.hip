@@ -24,7 +24,7 @@
 #include <cstdlib>
 #include "pnl_hip.h"
 
-extern "C++" const char *pnl_tune(const char *name);     // pnl_hip.hip: options set through pnl_set_option
+extern "C++" const char *pnl_tune(const char *name);     // pnl_setup.hip: options set through pnl_set_option
 
 #include "pnl_plan.h"
 

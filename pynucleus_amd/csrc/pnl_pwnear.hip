@@ -2,7 +2,7 @@
 // over all pairs (pnl_assemble_dense_pointwise).  Near field and far field: the part of assembleClusters / getH2
 // (nonlocalAssembly_{SCALAR}.pxi:1663-2156, 3094-3219) these kernels take -- ordered element pairs with masks over the (2 dpe)^2 local
 // entries, the cluster exterior with the pointwise boundary kernel, the kernel interpolants of the admissible pairs with the order at
-// the nodes of the row cluster.  Kernels: pnl_pointwise.h; the state setters and pnl_pw_prepare launch nothing and stay in pnl_hip.hip.
+// the nodes of the row cluster.  Kernels: pnl_pointwise.h; the state setters and pnl_pw_prepare launch nothing and are in pnl_setup.hip.
 #include "pnl_context.h"
 // the kernel templates this unit instantiates stay in an unnamed namespace: nothing collides with pnl_hip.o or pnl_sparse.o at link time
 namespace {

@@ -86,7 +86,7 @@ int pnl_selftest(int op, int path, int dim, int boundary, const void *param, int
     std::vector<double> hin;
     if (op != PNL_SELFTEST_QORDER) hin.assign(in, in+n);
     else {
-        // cell data as finalize stages it (ln h, |ln(h / H0)| per cell, pnl_hip.hip)
+        // cell data as finalize stages it (ln h, |ln(h / H0)| per cell, pnl_setup.hip)
         hin.assign((size_t)7*n, 0.);
         for (int i = 0; i < n; i++) {
             const double h1 = in[4*i], h2 = in[4*i+1], d2 = in[4*i+2], H0 = in[4*i+3];

@@ -2,7 +2,7 @@
 // nonlocalAssembly_{SCALAR}.pxi:1663-1964) and getSparse for a finite horizon without a host pair list -- block tiles the horizon can
 // reach, k_tile_distant<.., FH> for the pairs inside it, the sorted sparse pipeline (classification, work list, touching pairs) for the
 // rest.  Kernels: the SPARSE instantiations of pnl_kernels.h, which nothing else launches; they stay in an unnamed namespace, so
-// nothing collides with pnl_hip.o at link time.  What this unit needs from pnl_hip.hip are host functions of pnl_context.h.
+// nothing collides with pnl_hip.o at link time.  What this unit needs from pnl_hip.hip and pnl_setup.hip are host functions of pnl_context.h.
 #include <climits>
 #include "pnl_context.h"
 namespace {

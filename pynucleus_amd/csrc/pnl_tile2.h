@@ -1,7 +1,7 @@
 // Second generation of the dense tile kernels (gfx950 only, 2D):
 //
 //   k_tile_uniform<DPE, NP, KT>  tiles whose cell pairs are ALL distant pairs of ONE quadrature order (host-side
-//                                conservative bounds on the order formula, tile_uniform_order in pnl_hip.hip): no
+//                                conservative bounds on the order formula, pnl_tile_uniform_order in pnl_setup.hip): no
 //                                classification, no lists.  P2 (32-cell blocks): lane = (cell i of block a, half h), the two
 //                                halves of a wave take two cells j of block b at a time; P1 (64-cell blocks): lane = cell i.
 //                                NP = 3 (order 2) or 6 (orders 3 and 4) points per triangle.
