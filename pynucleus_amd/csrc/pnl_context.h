@@ -32,6 +32,9 @@ struct pnl_context {
     // recorded behind the fold + mirror pass of a block-slot assembly: from here on A only receives atomic adds, so the touching
     // pairs and the boundary term run on side streams next to the work-list kernels (one order class)
     hipEvent_t ev_fold = nullptr;
+    // staged fold (pnl_hip.hip: launch_tiles): ev_stage[s] behind the last tile kernel of stage s on the caller's stream
+    static constexpr int MAX_STAGES = 16;    // far bands of a staged fold (stage 0 + bands)
+    hipEvent_t ev_stage[MAX_STAGES+1] = {};
     hipEvent_t ev_bnd = nullptr;             // zero fill of the diagonal-block buffer + class tables of the boundary term are in the stream
     bool fold_event_set = false;
     std::string err;
@@ -80,6 +83,22 @@ struct pnl_context {
     // the tiles that several order classes visit, the storage itself (allocated by the first assembly that uses it)
     DevBuf b_scolbase, b_srowoff, b_cpoff, b_cpslot, b_cprow, b_foldtab, b_bkcls, b_bfcls, b_bdefer, b_multitiles, b_slotA, b_candtiles, b_candq;
     int slot_S = 0, n_multitiles = 0;
+    // staged fold of the 2D P1 one-class path (pnl_setup.hip: stage_plan): blocks that hold a copy of a DoF of every range of 32 DoFs
+    // (CSR, from upload_slot_tables), per stage the packed images (range i << 16 | range j) in b_foldimg, per order and stage the offsets
+    // into the uniform lists; stg_K = 0: no stages (one fold of the whole matrix behind all tiles)
+    std::vector<int32_t> rng_blk_off, rng_blk;
+    DevBuf b_foldimg, b_unictr;
+    int stg_K = 0, stg_want = -1;                 // bands of the resident plan; PNL_FOLD_STAGES the plan was made for
+    std::vector<int> stg_img_off;                 // [stg_K + 2] offsets of the stages in b_foldimg
+    std::vector<int> stg_uni_off[3];              // [stg_K + 2] offsets of the stages in the uniform list of order 2, 3, 4
+    std::vector<unsigned> stg_img;                // host copy of b_foldimg (pnl_get_fold_plan)
+    std::vector<signed char> stg_tile_stage;      // [nblocks][nblocks] stage of tile (a, b), -1 below the diagonal
+    std::vector<unsigned char> stg_tile_q;        // [nblocks][nblocks] order 2 .. 4 of a uniform tile, else 0
+    // ticket counters of the uniform-tile launches (b_unictr, UNI_CTRS words): an assembly zeroes all of them at its start and hands
+    // them out in turn (uni_ctr_fresh left); launches beyond that zero their counter in the stream themselves
+    static constexpr int UNI_CTRS = 64;
+    int uni_ctr_next = 0, uni_ctr_fresh = 0;
+    bool stg_active = false;                      // the current assembly runs the staged sequence
     long long slot_total = 0;         // doubles
     // row slab of a rank (pnl_set_row_slab, pnl_slab.hip)
     DevBuf b_rowmap, b_rowdof, b_colmap, b_coldof;
@@ -143,8 +162,11 @@ struct pnl_context {
     double xform[4] = {1., 0., 0., 1.};
     std::vector<BlockAgg> blocks;
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t kev[PNL_NUM_KERNEL_SLOTS][2] = {};   // event pair around every tile-kernel launch (pnl_get_kernel_ms)
-    bool kev_set[PNL_NUM_KERNEL_SLOTS] = {};
+    // event pair around every tile-kernel launch (pnl_get_kernel_ms); a slot that is launched several times per assembly (the
+    // stages of a staged fold) takes one more pair per launch, created on first use and kept; kev_n: launches of the current assembly
+    std::vector<hipEvent_t> kev[PNL_NUM_KERNEL_SLOTS];
+    int kev_n[PNL_NUM_KERNEL_SLOTS] = {};
+    bool kev_open[PNL_NUM_KERNEL_SLOTS] = {};
     bool pure_launched = false;
     bool symflush = false;          // PNL_FLAG_SYMMETRIC_FLUSH of the current assembly
     bool ev_valid = false;
@@ -302,8 +324,22 @@ inline DevProblem with_mixed_rules(const pnl_context *ctx, DevProblem Pt) {
     return Pt;
 }
 
-inline void kt_begin(pnl_context *ctx, int slot) { (void)hipEventRecord(ctx->kev[slot][0], ctx->stream); }
-inline void kt_end(pnl_context *ctx, int slot) { (void)hipEventRecord(ctx->kev[slot][1], ctx->stream); ctx->kev_set[slot] = true; }
+inline void kt_begin(pnl_context *ctx, int slot) {
+    std::vector<hipEvent_t> &v = ctx->kev[slot];
+    const size_t k = 2*(size_t)ctx->kev_n[slot];
+    ctx->kev_open[slot] = false;
+    while (v.size() < k+2) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return; }      // no timer for this launch
+        v.push_back(e);
+    }
+    ctx->kev_open[slot] = hipEventRecord(v[k], ctx->stream) == hipSuccess;
+}
+inline void kt_end(pnl_context *ctx, int slot) {
+    if (!ctx->kev_open[slot]) return;
+    ctx->kev_open[slot] = false;
+    if (hipEventRecord(ctx->kev[slot][2*(size_t)ctx->kev_n[slot]+1], ctx->stream) == hipSuccess) ctx->kev_n[slot]++;
+}
 
 // pnl_setup.hip: joins the vertex-order search finalize() started and uploads the permuted cell tables (sets have_tile_order)
 int pnl_tile_order_ready(pnl_context *ctx);
@@ -344,11 +380,11 @@ int pnl_launch_slab_two_sided(pnl_context *ctx, const double *slab, long long ld
 
 // pnl_tile2.hip
 int pnl2_launch_uniform(pnl_context *ctx, int kt, const DevProblem &Pt, const int2 *tiles, const int *tile_cls, int ntiles, int q,
-                        double *A, int64_t ldA, double *Dglob, const SlotOut &SO);
+                        double *A, int64_t ldA, double *Dglob, const SlotOut &SO, int spare = 0);
 int pnl2_launch_p2(pnl_context *ctx, int kt, const int2 *tiles, const int *tile_cls, int ntiles, double *A, int64_t ldA,
                    int cell_begin, int cell_end, unsigned wl_cap_each, const SlotOut &SO);
 int pnl2_zero_slot_tiles(pnl_context *ctx, const SlotOut &SO);
-int pnl2_fold_mirror(pnl_context *ctx, const SlotOut &SO, double *A, int64_t ldA);
+int pnl2_fold_mirror(pnl_context *ctx, const SlotOut &SO, double *A, int64_t ldA, const unsigned *images = nullptr, int nimages = 0);
 inline SlotOut slot_out(const pnl_context *ctx) {
     SlotOut SO;
     SO.A2 = (double*)ctx->b_slotA.p; SO.rowoff = (const long long*)ctx->b_srowoff.p; SO.colbase = (const int*)ctx->b_scolbase.p;

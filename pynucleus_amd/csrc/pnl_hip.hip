@@ -170,11 +170,117 @@ int ensure_worklist(pnl_context *ctx, double pairs, int regions) {
     return PNL_OK;
 }
 
+// the mixed tiles of the current class (k_tile_distant): one region of the work list, reused by every class / orientation pass; the
+// fill counter wlc of pass p stays in slot p (check_overflow)
+template <int DIM, int DPE, int TILE, int KT>
+int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, int cell_begin, int cell_end, const SlotOut &SO) {
+    using S = TileSmem<DIM, DPE, TILE, KT == 0>;
+    const int ntiles = ctx->n_mixed;
+    const int acc_stride = acc_stride_of(ctx->nU, S::fixed_bytes);
+    const size_t lds = S::fixed_bytes+sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
+    if (lds > 160*1024)
+        return fail(ctx, PNL_ERR_UNSUPPORTED, "a block of %d cells touches %d DoFs: LDS sub-block of %zu bytes exceeds 160 KiB "
+                    "(cells must be numbered with spatial locality)", TILE, ctx->nU, lds);
+    HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
+    auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false>;
+    const int grid_mult = pnl_tune("PNL_GRID_MULT") ? atoi(pnl_tune("PNL_GRID_MULT")) : 1;
+    const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT), lds, ntiles, 2, grid_mult);
+    if (g.rc) return g.rc;
+    if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] tiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", ntiles, ctx->nU, lds, g.per_cu);
+    SlotOut SOk = SO;
+    SOk.nU = ctx->nU;                                       // rows of the LDS sub-block (also without the block-slot storage)
+    kt_begin(ctx, PNL_K_TILE_GENERAL);
+    if (g.grid > 0)
+        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)), (const int2*)ctx->b_tiles.p+ctx->tile_off, A,
+                           (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), cell_begin, cell_end, acc_stride, (int4*)ctx->b_wl.p,
+                           wlc, ctx->wl_cap_each, ctx->ablate | (ctx->symflush ? 256 : 0), ntiles, ClusterTiles{},
+                           (unsigned*)ctx->b_tilectr.p, SOk);
+    kt_end(ctx, PNL_K_TILE_GENERAL);
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+
+// spare workgroup slots per CU of the uniform-tile launches of the stages >= 1 (option PNL_UNI_SPARE)
+#ifndef PNL_UNI_SPARE_DEFAULT
+#define PNL_UNI_SPARE_DEFAULT 1
+#endif
 template <int DIM, int DPE, int TILE, int KT>
 int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell_begin, int cell_end, const SlotOut &SO = SlotOut{}) {
-    using S = TileSmem<DIM, DPE, TILE, KT == 0>;
     HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     ctx->pure_launched = false;
+    // Staged fold (option PNL_FOLD_STAGES > 0; 2D P1, one order class, block-slot storage; the plan: stage_plan in pnl_setup.hip).
+    // Measured at 98,304 cells, s = 1/2 (docs/CHANGELOG_kernels.md, round 6): no gain over the single fold for any number of bands --
+    // what the side kernels do beside the tile kernels, the tile kernels lose -- so the default is 0.  Caller's stream: the uniform
+    // tiles of stage 0, the mixed tiles, event; then per stage s >= 1 its uniform tiles on a grid that leaves `spare` workgroup
+    // slots per CU free, event.  The fold's side stream (aux[2]) folds stage s behind the event of stage s; behind the fold of stage 0
+    // (ev_fold) the work list (aux[3]) and the touching pairs (aux[0], assemble_impl) start on their side streams.  Every image of A that
+    // these add to belongs to stage 0, and the folds of the later stages write other images.  Side streams wait on events only;
+    // the ticket counters of the tile loops hand out work, no workgroup waits for another.  PNL_NO_OVERLAP: the same sequence on the
+    // caller's stream.
+    const bool staged = DIM == 2 && DPE == 3 && SO.A2 && ctx->stg_K > 0 && ctx->cls.size() == 1 && !ctx->nonsym;
+    ctx->stg_active = staged;
+    if (staged) {
+        int rc;
+        const int K = ctx->stg_K;
+        const int spare = pnl_tune("PNL_UNI_SPARE") ? atoi(pnl_tune("PNL_UNI_SPARE")) : PNL_UNI_SPARE_DEFAULT;
+        const bool side = !pnl_tune("PNL_NO_OVERLAP");
+        hipStream_t const caller = ctx->stream;
+        hipStream_t const folds = side ? ctx->aux[2] : caller;
+        // the work list on a side stream of its own (aux[3]) behind the fold of stage 0, not on the folds' stream in front of the later
+        // folds.  (Where the runtime maps five streams onto four hardware queues it may still share the queue of the folds' stream;
+        // measured with the work list on the other side streams as well, docs/CHANGELOG_kernels.md round 6: no gain either way)
+        constexpr int wl_aux = 3;
+        hipStream_t const wls = side ? ctx->aux[wl_aux] : caller;
+        struct StreamGuard { pnl_context *c; hipStream_t s; ~StreamGuard() { c->stream = s; } } stream_guard{ctx, caller};
+        const int2 *tiles = (const int2*)ctx->b_tiles.p+ctx->tile_off;
+        double *Dt = (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p);
+        unsigned *wlc = (unsigned*)ctx->b_wlcount.p+wl_slot;
+        auto uniform_stage = [&](int s, int spare_s) -> int {
+            int off = ctx->n_mixed;
+            for (int q = 2; q <= 4; q++) {
+                const std::vector<int> &so = ctx->stg_uni_off[q-2];
+                const int n = so[s+1]-so[s];
+                int rcu = pnl2_launch_uniform(ctx, KT, tile_problem(ctx), tiles+off+so[s], nullptr, n, q, A, ldA, Dt, SO, spare_s);
+                if (rcu) return rcu;
+                ctx->pure_launched = ctx->pure_launched || n > 0;
+                off += so[K+1];
+            }
+            return PNL_OK;
+        };
+        auto fold_stage = [&](int s) -> int {
+            if (side) HIPCHK(ctx, hipStreamWaitEvent(folds, ctx->ev_stage[s], 0));
+            ctx->stream = folds;
+            const int rcf = pnl2_fold_mirror(ctx, SO, A, ldA, (const unsigned*)ctx->b_foldimg.p+ctx->stg_img_off[s], ctx->stg_img_off[s+1]-ctx->stg_img_off[s]);
+            ctx->stream = caller;
+            return rcf;
+        };
+        if ((rc = uniform_stage(0, 0))) return rc;
+        HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+        if ((rc = launch_mixed_tiles<DIM, DPE, TILE, KT>(ctx, wlc, A, ldA, cell_begin, cell_end, SO))) return rc;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_stage[0], caller));
+        if ((rc = fold_stage(0))) return rc;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_fold, folds));
+        ctx->fold_event_set = true;
+        if (side && wls != folds) HIPCHK(ctx, hipStreamWaitEvent(wls, ctx->ev_fold, 0));
+        ctx->stream = wls;
+        rc = run_worklist<DIM, DPE, KT>(ctx, (const int4*)ctx->b_wl.p, wlc, ctx->wl_cap_each, A, ldA, true);
+        ctx->stream = caller;
+        if (rc) return rc;
+        if (side && wls != folds) HIPCHK(ctx, hipEventRecord(ctx->ev_join[wl_aux], wls));
+        for (int s = 1; s <= K; s++) {
+            if ((rc = uniform_stage(s, spare))) return rc;
+            HIPCHK(ctx, hipEventRecord(ctx->ev_stage[s], caller));
+            if ((rc = fold_stage(s))) return rc;
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->ev[6], caller));                        // the last tile kernel is done
+        if (side) {
+            // what is left of the folds and the work list behind the last tile kernel: phase [1]
+            HIPCHK(ctx, hipEventRecord(ctx->ev_join[2], folds));
+            HIPCHK(ctx, hipStreamWaitEvent(caller, ctx->ev_join[2], 0));
+            if (wls != folds) HIPCHK(ctx, hipStreamWaitEvent(caller, ctx->ev_join[wl_aux], 0));
+        }
+        return PNL_OK;
+    }
     if (TILE == 64 && DPE <= 3) {
         int rc;
         // order-2 uniform tiles: 2D P1 the pipelined k_tile_uniform<3, 3> (with three or four workgroups per CU it beats k_tile_pure:
@@ -198,30 +304,11 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
         }
         HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     }
-    const int ntiles = ctx->n_mixed;
-    const int acc_stride = acc_stride_of(ctx->nU, S::fixed_bytes);
-    const size_t lds = S::fixed_bytes+sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
-    if (lds > 160*1024)
-        return fail(ctx, PNL_ERR_UNSUPPORTED, "a block of %d cells touches %d DoFs: LDS sub-block of %zu bytes exceeds 160 KiB "
-                    "(cells must be numbered with spatial locality)", TILE, ctx->nU, lds);
-    // one region, reused by every class / orientation pass; the fill counter of pass p stays in slot p (check_overflow)
     unsigned *wlc = (unsigned*)ctx->b_wlcount.p+wl_slot;
-    HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
-    auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false>;
-    const int grid_mult = pnl_tune("PNL_GRID_MULT") ? atoi(pnl_tune("PNL_GRID_MULT")) : 1;
-    const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT), lds, ntiles, 2, grid_mult);
-    if (g.rc) return g.rc;
-    if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] tiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", ntiles, ctx->nU, lds, g.per_cu);
-    SlotOut SOk = SO;
-    SOk.nU = ctx->nU;                                       // rows of the LDS sub-block (also without the block-slot storage)
-    kt_begin(ctx, PNL_K_TILE_GENERAL);
-    if (g.grid > 0)
-        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)), (const int2*)ctx->b_tiles.p+ctx->tile_off, A,
-                           (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), cell_begin, cell_end, acc_stride, (int4*)ctx->b_wl.p,
-                           wlc, ctx->wl_cap_each, ctx->ablate | (ctx->symflush ? 256 : 0), ntiles, ClusterTiles{},
-                           (unsigned*)ctx->b_tilectr.p, SOk);
-    kt_end(ctx, PNL_K_TILE_GENERAL);
-    HIPCHK(ctx, hipGetLastError());
+    {
+        int rc = launch_mixed_tiles<DIM, DPE, TILE, KT>(ctx, wlc, A, ldA, cell_begin, cell_end, SO);
+        if (rc) return rc;
+    }
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     // block-slot storage: A = A' + A'^T is formed now (it overwrites A); the work-list kernels then write both images
     if (SO.A2) {
@@ -442,13 +529,20 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
     int rc;
     const int ncls = (int)ctx->cls.size();
     ctx->symflush = (flags & PNL_FLAG_SYMMETRIC_FLUSH) != 0;
-    for (bool &b : ctx->kev_set) b = false;
+    for (int &k : ctx->kev_n) k = 0;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->b_D.p, 0, sizeof(double)*(size_t)ctx->ncp*(DPE*(DPE+1)/2), ctx->stream));
     if (ctx->have_tile_order) HIPCHK(ctx, hipMemsetAsync(ctx->b_Dt.p, 0, sizeof(double)*(size_t)ctx->ncp*(DPE*(DPE+1)/2), ctx->stream));
+    if (DIM == 2 && DPE == 3) {
+        // ticket counters of the uniform-tile launches (pnl_tile2.hip): one fill for all launches of this assembly
+        if ((rc = ensure(ctx, ctx->b_unictr, sizeof(unsigned)*pnl_context::UNI_CTRS))) return rc;
+        HIPCHK(ctx, hipMemsetAsync(ctx->b_unictr.p, 0, sizeof(unsigned)*pnl_context::UNI_CTRS, ctx->stream));
+        ctx->uni_ctr_next = 0; ctx->uni_ctr_fresh = pnl_context::UNI_CTRS;
+    }
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     ctx->tiles_launched = ntiles > 0;
     ctx->fold_event_set = false;
+    ctx->stg_active = false;
     // variable order, zero exterior: the distant (cell, facet) pairs of ALL classes run in one launch with per-class kernel /
     // order-formula tables; the tables go up now, ahead of the tile kernels, so that the launch needs nothing from the
     // caller's stream later than the fold
@@ -603,9 +697,12 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
         HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
         ctx->stream = main_stream;
     } else HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    if (bnd_mode == 3 && ctx->fold_event_set) rc = boundary_side(ctx->ev[6]);          // next to the fold pass (ev[6]: tile kernels done)
-    else if (bnd_mode == 1 || ((bnd_mode == 0 || bnd_mode == 3) && overlap)) rc = boundary_side(bnd_mode == 1 ? ctx->ev_bnd : ctx->ev_fold);
-    else if (bnd_mode == 0 || bnd_mode == 3) rc = boundary_term(chain);
+    // 4: as 3, but with a staged fold behind the tile kernels of stage 0, next to the uniform tiles of the later stages (which leave
+    // it a workgroup slot per CU)
+    if ((bnd_mode == 3 || bnd_mode == 4) && ctx->fold_event_set)              // next to the fold pass (ev[6]: tile kernels done)
+        rc = boundary_side(bnd_mode == 4 && ctx->stg_active && !pnl_tune("PNL_NO_OVERLAP") ? ctx->ev_stage[0] : ctx->ev[6]);
+    else if (bnd_mode == 1 || ((bnd_mode == 0 || bnd_mode >= 3) && overlap)) rc = boundary_side(bnd_mode == 1 ? ctx->ev_bnd : ctx->ev_fold);
+    else if (bnd_mode == 0 || bnd_mode >= 3) rc = boundary_term(chain);
     if (rc) return rc;
     ctx->cur = 0;
     if (overlap) {

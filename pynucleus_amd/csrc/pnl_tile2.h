@@ -49,27 +49,35 @@ __host__ __device__ constexpr int uni_rule_size(int dpe, int np) { return 3*np+n
 template <bool NT>
 __global__ void __launch_bounds__(256)
 k_fold_mirror(const double *__restrict__ A2, const FoldEntry *__restrict__ tab, const int *__restrict__ cpoff, const int2 *__restrict__ cp,
-              const long long *__restrict__ cprow, double *__restrict__ A, long long ldA, int N) {
+              const long long *__restrict__ cprow, double *__restrict__ A, long long ldA, int N, const unsigned *__restrict__ images) {
     __shared__ double t1[32][33], t2[32][33];
     __shared__ FoldEntry s_tab[2][PNL_FOLD_TAB+1];
     const unsigned nb = (unsigned)(N+31)/32;
     // 8 x 8 super-blocks of the upper block triangle, 64 consecutive workgroups each: the workgroups in flight share the
     // storage rows of 8 row ranges and 8 column ranges (pages, DRAM rows, L2 lines of the XCD) instead of sweeping one block
     // row against thousands of unrelated column ranges
-    const unsigned nbs = (nb+7)/8;
-    const unsigned sbid = blockIdx.x >> 6, inner = blockIdx.x & 63;
-    // sbid = I nbs - I (I-1)/2 + (J - I); the grid has less than 2^31 blocks, so 32-bit arithmetic is exact
-    unsigned I;
-    {
-        const float t = 2.f*(float)nbs+1.f;
-        const float fb = (t-sqrtf(fmaxf(t*t-8.f*(float)sbid, 0.f)))*0.5f;
-        I = (unsigned)fmaxf(fb, 0.f);
-        if (I >= nbs) I = nbs-1;
-        while (I > 0 && I*nbs-I*(I-1)/2 > sbid) I--;
-        while (I+1 < nbs && (I+1)*nbs-(I+1)*I/2 <= sbid) I++;
+    // images: the workgroups take the packed images (bi << 16 | bj) of a list in that order (a stage of a staged fold: the host made
+    // the list in the same traversal order); nullptr: the whole upper block triangle, decoded from the block index
+    unsigned bi, bj;
+    if (images) {
+        const unsigned im = images[blockIdx.x];
+        bi = im >> 16; bj = im & 0xffffu;
+    } else {
+        const unsigned nbs = (nb+7)/8;
+        const unsigned sbid = blockIdx.x >> 6, inner = blockIdx.x & 63;
+        // sbid = I nbs - I (I-1)/2 + (J - I); the grid has less than 2^31 blocks, so 32-bit arithmetic is exact
+        unsigned I;
+        {
+            const float t = 2.f*(float)nbs+1.f;
+            const float fb = (t-sqrtf(fmaxf(t*t-8.f*(float)sbid, 0.f)))*0.5f;
+            I = (unsigned)fmaxf(fb, 0.f);
+            if (I >= nbs) I = nbs-1;
+            while (I > 0 && I*nbs-I*(I-1)/2 > sbid) I--;
+            while (I+1 < nbs && (I+1)*nbs-(I+1)*I/2 <= sbid) I++;
+        }
+        const unsigned J = I+(sbid-(I*nbs-I*(I-1)/2));
+        bi = 8*I+(inner >> 3); bj = 8*J+(inner & 7);
     }
-    const unsigned J = I+(sbid-(I*nbs-I*(I-1)/2));
-    const unsigned bi = 8*I+(inner >> 3), bj = 8*J+(inner & 7);
     if (bi > bj || bj >= nb) return;                     // lower part of a diagonal super-block, padding of the last one
     const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;     // 32 x 8
     if (tid < 2*(PNL_FOLD_TAB+1)) {
@@ -192,7 +200,7 @@ __host__ __device__ constexpr size_t uniform_fixed_lds(int dpe, int np, int tile
     // per-cell rows have odd strides (in doubles / ints): the lanes of a wave read the rows of 64 different cells
     // (P1; the P2 kernels, two workgroups of just under 80 KB per CU, keep compact rows and the vertices of the a-cells)
     return dpe == 3 ? sizeof(double)*(size_t)(2*tile*(np*2+1)+2*tile+2*tile*(np|1)+(dpe*(dpe+1)/2)*np)
-                      +sizeof(int)*(size_t)(2*tile*(dpe|1)+2*tile+(dof_lists ? 4*nUe : 0))
+                      +sizeof(int)*(size_t)(2*tile*(dpe|1)+2*tile+2+(dof_lists ? 4*nUe : 0))
                     : sizeof(double)*(size_t)(tile*np*2+tile*6+2*tile+2*tile*np+(dpe*(dpe+1)/2)*np)
                       +sizeof(int)*(size_t)(2*tile*dpe+2*tile+(dof_lists ? 4*nUe : 0));
 }
@@ -220,7 +228,7 @@ template <int DPE, int NP, int KT, bool STRUCT = false>
 __global__ void __launch_bounds__(256, (DPE == 3 && NP == 3) ? (KT == 0 ? PNL_U33K0_WAVES : (KT == 2 ? 4 : 2)) : ((DPE == 3 && NP == 6) ? 3 : 2))
 k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__restrict__ tile_cls, const DevKernel *__restrict__ kcls,
                int ntiles, double *__restrict__ A, long long ldA, double *__restrict__ Dglob, int acc_stride, int q_uniform,
-               int flags, const double *__restrict__ rule_g, int nUe, const SlotOut SO) {
+               int flags, const double *__restrict__ rule_g, int nUe, const SlotOut SO, unsigned *__restrict__ tile_ctr) {
     const int flags_in = flags;
     constexpr int DIM = 2, NV = 3, NC = 6, ND = DPE*(DPE+1)/2, NT = 256, NW = NT/64;
     constexpr int TILE = DPE == 6 ? 32 : 64, HALVES = 64/TILE, JW = TILE/NW, ITER = JW/HALVES;
@@ -248,7 +256,8 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
     int *s_sa = s_slotb+TILE*SS;                         // [TILE][SS] row offset in the sub-block (trash row nUe)
     int *s_ha = s_sa+TILE*SS;                            // [TILE] has-a-DoF flags
     int *s_hb = s_ha+TILE;
-    int *s_dof = s_hb+TILE;                              // [2][2][nUe] global DoFs of both blocks (ping-pong over tiles);
+    int *s_next = s_hb+TILE;                             // [2] P1: the next tile of this workgroup (ticket), padding
+    int *s_dof = s_next+(DPE == 3 ? 2 : 0);              // [2][2][nUe] global DoFs of both blocks (ping-pong over tiles);
     const bool dof_lists = SO.A2 == nullptr;             // not with the block-slot storage (uniform_fixed_lds)
     double *s_acc = (double*)(s_dof+(dof_lists ? 4*nUe : 0));    // [nUe+1][acc_stride]; nUe even
     // tables of the general power (KT == 0) behind the sub-block, if the launcher made room for them (bit 8 of flags: they
@@ -323,6 +332,13 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
     if (have_pow && !tile_cls) { cur_ptab = P.k.ptab; pnl_pow_tab_fill(s_pow, cur_ptab, tid, NT); }
     for (int t = tid; t < (nUe+1)*acc_stride; t += NT) s_acc[t] = 0.;
     for (int t = tid; t < 2*TILE*RS; t += NT) s_Ra[t] = 0.;        // s_Ra and s_Rb
+    // P1: the tiles behind the first come from a ticket counter (one per launch, zeroed in the stream), so that a workgroup that
+    // starts late or shares its CU takes fewer tiles instead of leaving its share of a static stride for the end.  Thread 0 holds
+    // the ticket one tile ahead (the atomic is issued before the flush, its latency passes behind a whole tile) and publishes it
+    // through LDS at the barrier behind the pair loop.  P2 keeps the stride of the grid (tile_ctr is not read).
+    constexpr bool TICKET = DPE == 3;
+    unsigned pending = 0;
+    if (TICKET && tid == 0) pending = atomicAdd(tile_ctr, 1u);
     stage(tile_idx, 0);
     lds_barrier();
 #pragma unroll 1
@@ -525,9 +541,14 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
             for (int ip = 0; ip < (NP == 3 ? 3 : 1); ip++) lds_add_f64(&Ra[li*RS+ip], racc[ip]);
         }
         });
+        if (TICKET && tid == 0) {
+            // tickets beyond the list stay beyond it (the counter only grows by one per workgroup from there on)
+            s_next[0] = (int)min(gridDim.x+pending, (unsigned)ntiles);
+            if (gridDim.x+pending < (unsigned)ntiles) pending = atomicAdd(tile_ctr, 1u);
+        }
         lds_barrier();
         // ---- the next tile's inputs, then the flush of this one ----
-        const int nxt = tile_idx+(int)gridDim.x;
+        const int nxt = TICKET ? __builtin_amdgcn_readfirstlane(s_next[0]) : tile_idx+(int)gridDim.x;
         const bool more = nxt < ntiles;
         if (more) stage(nxt, buf^1);
         const int *__restrict__ dA = s_dof+(buf*2+0)*nUe, *__restrict__ dB = s_dof+(buf*2+1)*nUe;

@@ -7,7 +7,7 @@ namespace {
 
 template <int DPE, int NP, int KT, bool STRUCT = false>
 int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, const int *tile_cls, int ntiles, int q, double *A,
-                     int64_t ldA, double *Dglob, const SlotOut &SO) {
+                     int64_t ldA, double *Dglob, const SlotOut &SO, int spare) {
     constexpr int TILE = DPE == 6 ? 32 : 64;
     const int nUe = (ctx->nU+1) & ~1;                     // even: the sub-block follows the int arrays at an 8-byte boundary
     const size_t fixed = uniform_fixed_lds(DPE, NP, TILE, nUe, SO.A2 == nullptr);
@@ -51,7 +51,21 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
     }
     HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int per_cu = resident(lds);
-    const int grid = pnl_grid_cap(std::min(ntiles, 256*per_cu));
+    // spare: workgroup slots per CU this launch leaves to kernels of other streams (P1: the ticketed tile loop does not care how
+    // many workgroups share the tiles)
+    const int grid = pnl_grid_cap(std::min(ntiles, 256*std::max(1, per_cu-(DPE == 3 ? std::max(spare, 0) : 0))));
+    // P1: the ticket counter of this launch, one of those the assembly zeroed at its start (assemble_impl), else zeroed in the stream
+    // here; every launch has its own, so that no launch depends on more than the order of its own stream
+    unsigned *ctr = nullptr;
+    if (DPE == 3) {
+        constexpr int NCTR = pnl_context::UNI_CTRS;
+        int rc = ensure(ctx, ctx->b_unictr, sizeof(unsigned)*NCTR);
+        if (rc) return rc;
+        ctr = (unsigned*)ctx->b_unictr.p+ctx->uni_ctr_next;
+        ctx->uni_ctr_next = (ctx->uni_ctr_next+1)%NCTR;
+        if (ctx->uni_ctr_fresh > 0) ctx->uni_ctr_fresh--;
+        else HIPCHK(ctx, hipMemsetAsync(ctr, 0, sizeof(unsigned), ctx->stream));
+    }
     if (pnl_tune("PNL_VERBOSE"))
         fprintf(stderr, "[pnl] uniform tiles of order %d: %d, dpe=%d np=%d kt=%d struct=%d lds=%zu bytes (%d per CU), acc_stride=%d\n", q, ntiles, DPE,
                 NP, KT, (int)STRUCT, lds, per_cu, acc_stride);
@@ -62,7 +76,7 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
     kt_begin(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     hipLaunchKernelGGL(kfun, dim3(grid), dim3(256), lds, ctx->stream, Pt, tiles, tile_cls, (const DevKernel*)ctx->b_kcls.p, ntiles, A,
                        (long long)ldA, Dglob, acc_stride, q, (ctx->symflush ? 1 : 0) | uni_abl | pow_flag, (const double*)ctx->b_uni.p+ctx->uni_off[q],
-                       nUe, SO);
+                       nUe, SO, ctr);
     kt_end(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
@@ -70,17 +84,17 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
 
 template <int DPE, int NP>
 int launch_uniform_kt(pnl_context *ctx, int kt, const DevProblem &Pt, const int2 *tiles, const int *tile_cls, int ntiles, int q,
-                      double *A, int64_t ldA, double *Dglob, const SlotOut &SO) {
+                      double *A, int64_t ldA, double *Dglob, const SlotOut &SO, int spare) {
     if constexpr (DPE == 3) {
         if (ctx->uni_struct[q] && !pnl_tune("PNL_UNI_GENERIC")) {
-            if (kt == 2) return launch_uniform_t<DPE, NP, 2, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
-            if (kt == 1) return launch_uniform_t<DPE, NP, 1, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
-            return launch_uniform_t<DPE, NP, 0, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+            if (kt == 2) return launch_uniform_t<DPE, NP, 2, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+            if (kt == 1) return launch_uniform_t<DPE, NP, 1, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+            return launch_uniform_t<DPE, NP, 0, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
         }
     }
-    if (kt == 2) return launch_uniform_t<DPE, NP, 2>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
-    if (kt == 1) return launch_uniform_t<DPE, NP, 1>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
-    return launch_uniform_t<DPE, NP, 0>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+    if (kt == 2) return launch_uniform_t<DPE, NP, 2>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+    if (kt == 1) return launch_uniform_t<DPE, NP, 1>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+    return launch_uniform_t<DPE, NP, 0>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
 }
 
 template <int KT>
@@ -115,14 +129,14 @@ int launch_p2_t(pnl_context *ctx, const int2 *tiles, const int *tile_cls, int nt
 
 // uniform tiles of one order; Pt / Dglob: the cell tables (and diagonal-block buffer) the tile kernels use
 int pnl2_launch_uniform(pnl_context *ctx, int kt, const DevProblem &Pt, const int2 *tiles, const int *tile_cls, int ntiles, int q,
-                        double *A, int64_t ldA, double *Dglob, const SlotOut &SO) {
+                        double *A, int64_t ldA, double *Dglob, const SlotOut &SO, int spare) {
     if (ntiles <= 0) return PNL_OK;
     if (q < 2 || q > 4 || ctx->uni_off[q] < 0) return fail(ctx, PNL_ERR_STATE, "no uniform-tile rule for order %d", q);
     const int np = ctx->uni_np[q];
-    if (ctx->dpe == 6 && np == 3) return launch_uniform_kt<6, 3>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
-    if (ctx->dpe == 6 && np == 6) return launch_uniform_kt<6, 6>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
-    if (ctx->dpe == 3 && np == 6) return launch_uniform_kt<3, 6>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
-    if (ctx->dpe == 3 && np == 3) return launch_uniform_kt<3, 3>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+    if (ctx->dpe == 6 && np == 3) return launch_uniform_kt<6, 3>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+    if (ctx->dpe == 6 && np == 6) return launch_uniform_kt<6, 6>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+    if (ctx->dpe == 3 && np == 6) return launch_uniform_kt<3, 6>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+    if (ctx->dpe == 3 && np == 3) return launch_uniform_kt<3, 3>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
     return fail(ctx, PNL_ERR_UNSUPPORTED, "uniform tiles: dpe=%d with %d points", ctx->dpe, np);
 }
 
@@ -142,14 +156,17 @@ int pnl2_zero_slot_tiles(pnl_context *ctx, const SlotOut &SO) {
     return PNL_OK;
 }
 
-int pnl2_fold_mirror(pnl_context *ctx, const SlotOut &SO, double *A, int64_t ldA) {
+// images / nimages: the packed images of one stage (device), nullptr: the whole upper block triangle
+int pnl2_fold_mirror(pnl_context *ctx, const SlotOut &SO, double *A, int64_t ldA, const unsigned *images, int nimages) {
     const long long nb = (ctx->N+31)/32, nbs = (nb+7)/8;
     if (nbs*(nbs+1)/2*64 >= (1ll << 31)) return fail(ctx, PNL_ERR_UNSUPPORTED, "fold pass: %d DoFs exceed the grid size", ctx->N);
+    if (images && nimages <= 0) return PNL_OK;
+    const unsigned grid = images ? (unsigned)nimages : (unsigned)(nbs*(nbs+1)/2*64);
     kt_begin(ctx, PNL_K_FOLD_MIRROR);
     // the matrix is written once and not read again by this pass: non-temporal stores (10.9 -> 10.4 ms at 48,769 DoFs; non-temporal
     // LOADS of the storage cost 50 %: the 8-byte gathers of neighbouring threads share lines)
-    hipLaunchKernelGGL(k_fold_mirror<true>, dim3((unsigned)(nbs*(nbs+1)/2*64)), dim3(256), 0, ctx->stream, (const double*)SO.A2, (const FoldEntry*)ctx->b_foldtab.p, (const int*)ctx->b_cpoff.p,
-                       (const int2*)ctx->b_cpslot.p, (const long long*)ctx->b_cprow.p, A, (long long)ldA, ctx->N);
+    hipLaunchKernelGGL(k_fold_mirror<true>, dim3(grid), dim3(256), 0, ctx->stream, (const double*)SO.A2, (const FoldEntry*)ctx->b_foldtab.p, (const int*)ctx->b_cpoff.p,
+                       (const int2*)ctx->b_cpslot.p, (const long long*)ctx->b_cprow.p, A, (long long)ldA, ctx->N, images);
     kt_end(ctx, PNL_K_FOLD_MIRROR);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
