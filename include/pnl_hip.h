@@ -86,9 +86,12 @@ enum pnl_counter {
     PNL_C_UNIFORM_TILE_PAIRS,          /* pairs integrated by the uniform-tile kernel (subset of assembled) */
     PNL_C_RESERVED7,
     PNL_C_HIST0 = 8,                   /* [8+q]: distant pairs of order q, q < 120; [128..130]: vertex/edge/face */
-    PNL_C_UNIFORM_Q2 = 131             /* [131..133]: pairs integrated by the uniform-tile kernels of order 2, 3, 4 */
+    PNL_C_UNIFORM_Q2 = 131,            /* [131..133]: pairs integrated by the uniform-tile kernels of order 2, 3, 4 */
+    PNL_C_SETTLED_TILES = 134,         /* mixed tiles the assembly took through the settled instantiation of the tile kernel  */
+    PNL_C_CODE_BUILDS = 135,           /* times the context has computed the pair codes of settled tiles (once per tile plan)  */
+    PNL_C_WORKLIST_LENGTH = 136        /* entries the tile kernels handed to the device work lists, summed over the passes      */
 };
-#define PNL_NUM_COUNTERS 134
+#define PNL_NUM_COUNTERS 137
 
 /* Options (process-wide).  The library reads no environment variable on its assembly path; an option exists once it has been
  * set here (value NULL removes it).  A product build accepts
@@ -102,6 +105,9 @@ enum pnl_counter {
  *                     symmetric 3- and 6-point rules (tests: both evaluators against each other),
  *   "PNL_MIXED_GENERIC" mixed tiles: the evaluators for arbitrary rules also for the pairs whose rule has that orbit structure
  *                     (tests: both evaluators against each other),
+ *   "PNL_MIXED_UNSETTLED" the tile plan settles no mixed tile: every mixed tile is classified pair by pair in every assembly
+ *                     (tests: both paths against each other; read when the plan is made, changing it makes a new plan).  Tiles are
+ *                     settled only where the plan computes exact order ranges: a tuning build's PNL_NO_EXACT_TILES settles nothing too,
  *   "PNL_NO_OVERLAP", "PNL_NO_FORK"   profiling: no side streams, every phase on the caller's stream one after the other,
  *   "PNL_FOLD_STAGES" dense 2D P1 assembly of one order class: number of far bands of the staged fold (pnl_get_fold_stages); 0: one
  *                     fold of the whole matrix behind all tile kernels (the default),
@@ -124,9 +130,12 @@ int pnl_set_option(const char *name, const char *value);
  *                         13, 14, 15, 17); the kernel must suit that path (fast for 1, 2 and >= 10)
  *   PNL_SELFTEST_SCALING  out[i] = pw_scaling<dim>(W, s = in[i], boundary), W from the pnl_order_function *param
  *   PNL_SELFTEST_QORDER   in[4 i ..] = h1, h2, d2, H0 of a cell pair; out[3 i ..] = quad_order_exact, quad_order_try,
- *                         quad_order_fast for the pnl_order_formula *param, ln h and |ln(h / H0)| staged like the tile kernels */
+ *                         quad_order_fast for the pnl_order_formula *param, ln h and |ln(h / H0)| staged like the tile kernels
+ *   PNL_SELFTEST_SETTLED_LAYOUT   host only, no device: in[i] = 8 tid + k names sweep k < 8 of thread tid < 512 of the mixed-tile
+ *                         kernel over a tile of 64 x 64 cell pairs; out[3 i ..] = pair index p, cell i of block a, cell j of block b.
+ *                         The 2-bit code of that pair is in bits 2 k, 2 k + 1 of word tid of a settled tile's codes */
 enum { PNL_SELFTEST_LOG = 0, PNL_SELFTEST_EXP = 1, PNL_SELFTEST_EXP_RANGED = 2, PNL_SELFTEST_KERNEL = 3, PNL_SELFTEST_SCALING = 4,
-       PNL_SELFTEST_QORDER = 5 };
+       PNL_SELFTEST_QORDER = 5, PNL_SELFTEST_SETTLED_LAYOUT = 6 };
 #define PNL_SELFTEST_DISPATCH 100
 int pnl_selftest(int op, int path, int dim, int boundary, const void *param, int n, const double *in, double *out);
 
@@ -394,12 +403,16 @@ int pnl_get_fold_stages(pnl_context *ctx, int64_t *out, int n);
  * (a, b) at a nblocks + b (-1 below the diagonal) and its uniform order 2 .. 4, 0 for the other tiles.  NULL skips an output;
  * PNL_ERR_STATE without stages. */
 int pnl_get_fold_plan(pnl_context *ctx, int32_t *images, int64_t nimages, int8_t *tile_stage, int8_t *tile_order, int64_t ntiles);
+/* The settled tiles of the resident dense tile plan (tests): tiles[i][2] = (block a, block b) of the first ntiles of them, in the order
+ * of the launch (most pairs of a 6-point rule first).  Returns their number (0: the plan settles nothing), or an error. */
+int pnl_get_settled_tiles(pnl_context *ctx, int32_t *tiles, int64_t ntiles);
 /* device time of the tile kernels of the last assemble call, one HIP-event pair around each launch (milliseconds, 0 if the
  * kernel did not run; a slot that was launched several times -- stages of a staged fold, order classes -- holds the sum over
  * its launches): [0] general tile kernel, [1] uniform tiles of
- * order 2, [2] order 3, [3] order 4, [4] fold + mirror of the block-slot storage, [5] work-list kernels */
+ * order 2, [2] order 3, [3] order 4, [4] fold + mirror of the block-slot storage, [5] work-list kernels, [6] the launch of the general
+ * tile kernel over the settled tiles (part of [0]) */
 enum pnl_kernel_slot { PNL_K_TILE_GENERAL = 0, PNL_K_TILE_UNIFORM2, PNL_K_TILE_UNIFORM3, PNL_K_TILE_UNIFORM4, PNL_K_FOLD_MIRROR,
-                       PNL_K_WORKLIST, PNL_NUM_KERNEL_SLOTS };
+                       PNL_K_WORKLIST, PNL_K_TILE_SETTLED, PNL_NUM_KERNEL_SLOTS };
 int pnl_get_kernel_ms(pnl_context *ctx, float *out, int n);
 
 /* ---- host-side planning of the H2 / near-field assembly (no GPU needed): cluster tree + admissibility

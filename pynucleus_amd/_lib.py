@@ -21,13 +21,13 @@ PNL_INTERIOR = 0
 PNL_BOUNDARY = 1
 PNL_FLAG_NO_MIRROR = 1
 PNL_FLAG_SYMMETRIC_FLUSH = 2
-PNL_NUM_COUNTERS = 134
+PNL_NUM_COUNTERS = 137
 
 # every symbol include/pnl_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_set_stream', 'pnl_synchronize',
            'pnl_upload_mesh', 'pnl_upload_dofmap', 'pnl_set_kernel', 'pnl_set_order_formula', 'pnl_upload_distant_rules',
            'pnl_upload_singular_rule', 'pnl_upload_boundary', 'pnl_assemble_dense', 'pnl_dense_overwrites', 'pnl_block_row_costs', 'pnl_tile_cells',
-           'pnl_assemble_dense_tiles', 'pnl_get_counters', 'pnl_get_phase_ms', 'pnl_get_kernel_ms', 'pnl_get_fold_stages', 'pnl_get_fold_plan', 'pnl_tree_build', 'pnl_tree_build_blocks', 'pnl_tree_build_refined', 'pnl_tree_build_horizon', 'pnl_tree_build_device', 'pnl_tree_destroy', 'pnl_tree_sizes', 'pnl_tree_get', 'pnl_tree_node_cells', 'pnl_h2_transfer_matrices', 'pnl_nfplan_build', 'pnl_nfplan_destroy', 'pnl_nfplan_sizes', 'pnl_nfplan_get', 'pnl_horizon_pattern', 'pnl_near_pattern', 'pnl_pattern_set_max_nnz', 'pnl_set_option', 'pnl_set_cell_order', 'pnl_set_interaction_transform', 'pnl_set_order_vertex_values', 'pnl_h2_get', 'pnl_h2_set', 'pnl_pattern_nnz', 'pnl_pattern_get', 'pnl_pattern_destroy', 'pnl_set_row_slab', 'pnl_diag_blocks_size', 'pnl_get_diag_blocks', 'pnl_slab_matvec', 'pnl_slab_diagonal', 'pnl_gemv', 'pnl_cg_jacobi',
+           'pnl_assemble_dense_tiles', 'pnl_get_counters', 'pnl_get_phase_ms', 'pnl_get_kernel_ms', 'pnl_get_fold_stages', 'pnl_get_fold_plan', 'pnl_get_settled_tiles', 'pnl_tree_build', 'pnl_tree_build_blocks', 'pnl_tree_build_refined', 'pnl_tree_build_horizon', 'pnl_tree_build_device', 'pnl_tree_destroy', 'pnl_tree_sizes', 'pnl_tree_get', 'pnl_tree_node_cells', 'pnl_h2_transfer_matrices', 'pnl_nfplan_build', 'pnl_nfplan_destroy', 'pnl_nfplan_sizes', 'pnl_nfplan_get', 'pnl_horizon_pattern', 'pnl_near_pattern', 'pnl_pattern_set_max_nnz', 'pnl_set_option', 'pnl_set_cell_order', 'pnl_set_interaction_transform', 'pnl_set_order_vertex_values', 'pnl_h2_get', 'pnl_h2_set', 'pnl_pattern_nnz', 'pnl_pattern_get', 'pnl_pattern_destroy', 'pnl_set_row_slab', 'pnl_diag_blocks_size', 'pnl_get_diag_blocks', 'pnl_slab_matvec', 'pnl_slab_diagonal', 'pnl_gemv', 'pnl_cg_jacobi',
            'pnl_inv_diagonal', 'pnl_set_classes', 'pnl_select_class', 'pnl_upload_sparsity', 'pnl_upload_sparsity_device', 'pnl_assemble_pairs_masked', 'pnl_assemble_boundary_masked', 'pnl_assemble_clusters_tiled', 'pnl_h2_setup', 'pnl_h2_matvec', 'pnl_h2_upward', 'pnl_h2_interact', 'pnl_h2_downward', 'pnl_h2_sizes', 'pnl_spmv',
            'pnl_assemble_pairs_in_horizon', 'pnl_assemble_pairs_in_horizon_range', 'pnl_set_nonsymmetric', 'pnl_set_order_function', 'pnl_upload_pointwise_rules', 'pnl_assemble_dense_pointwise',
            'pnl_assemble_pairs_masked_pointwise', 'pnl_assemble_boundary_masked_pointwise',
@@ -152,6 +152,7 @@ def load():
     L.pnl_get_kernel_ms.argtypes = [vp, vp, i32]
     L.pnl_get_fold_stages.argtypes = [vp, vp, i32]
     L.pnl_get_fold_plan.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64]
+    L.pnl_get_settled_tiles.argtypes = [vp, vp, C.c_int64]
     L.pnl_set_row_slab.argtypes = [vp, i32, vp, i32, vp]
     L.pnl_tree_build.argtypes = [i32, i32, vp, vp, vp, i32, dbl, i32, i32, i32, C.POINTER(vp)]
     L.pnl_tree_build_blocks.argtypes = [i32, i32, vp, vp, vp, i32, dbl, i32, i32, i32, vp, i32, C.POINTER(vp)]
@@ -246,18 +247,19 @@ def set_option(name, value=None):
         raise PnlError('pnl_set_option({!r}) failed: {} (a product build accepts only the options listed in include/pnl_hip.h)'.format(name, rc))
 
 
-SELFTEST_LOG, SELFTEST_EXP, SELFTEST_EXP_RANGED, SELFTEST_KERNEL, SELFTEST_SCALING, SELFTEST_QORDER = range(6)
+SELFTEST_LOG, SELFTEST_EXP, SELFTEST_EXP_RANGED, SELFTEST_KERNEL, SELFTEST_SCALING, SELFTEST_QORDER, SELFTEST_SETTLED_LAYOUT = range(7)
 SELFTEST_DISPATCH = 100
 
 
 def selftest(op, x, path=0, dim=1, boundary=False, param=None):
     """pnl_selftest (include/pnl_hip.h): the production device function `op` on the current device, one thread per input.
-    x: [n] inputs (SELFTEST_QORDER: [n, 4] rows h1, h2, d2, H0 -> [n, 3] orders exact, try, fast); param: the pnl_kernel,
-    pnl_order_function or pnl_order_formula the op needs"""
+    x: [n] inputs (SELFTEST_QORDER: [n, 4] rows h1, h2, d2, H0 -> [n, 3] orders exact, try, fast; SELFTEST_SETTLED_LAYOUT, on the
+    host: 8 tid + k -> [n, 3] pair index, cell of block a, cell of block b); param: the pnl_kernel, pnl_order_function or
+    pnl_order_formula the op needs"""
     L = load()
     x = np.ascontiguousarray(x, dtype=np.float64)
     n = x.shape[0]
-    out = np.empty((n, 3) if op == SELFTEST_QORDER else n)
+    out = np.empty((n, 3) if op in (SELFTEST_QORDER, SELFTEST_SETTLED_LAYOUT) else n)
     rc = L.pnl_selftest(int(op), int(path), int(dim), int(bool(boundary)), None if param is None else C.addressof(param), n,
                         x.ctypes.data, out.ctypes.data)
     if rc != PNL_OK:
@@ -554,7 +556,8 @@ class Context:
         sing = {-1-k: int(out[128+k]) for k in range(3)}
         return dict(numCellPairs=int(out[0]), numAssembledCellPairs=int(out[1]), numIntegrations=int(out[2]),
                     numBoundaryPairs=int(out[3]), numBoundaryIntegrations=int(out[4]), orders=hist, singular=sing,
-                    uniformTilePairs=int(out[6]), uniformTilePairsByOrder={2+k: int(out[131+k]) for k in range(3)})
+                    uniformTilePairs=int(out[6]), uniformTilePairsByOrder={2+k: int(out[131+k]) for k in range(3)},
+                    settledTiles=int(out[134]), codeBuilds=int(out[135]), workListLength=int(out[136]))
 
     def phase_ms(self):
         out = np.zeros(7, dtype=np.float32)
@@ -584,10 +587,10 @@ class Context:
 
     def kernel_ms(self):
         """device time of each tile-kernel launch of the last assembly (HIP events on the library's stream)"""
-        out = np.zeros(6, dtype=np.float32)
-        self.check(self.L.pnl_get_kernel_ms(self.h, out.ctypes.data, 6))
+        out = np.zeros(7, dtype=np.float32)
+        self.check(self.L.pnl_get_kernel_ms(self.h, out.ctypes.data, 7))
         return dict(tile_general=float(out[0]), tile_uniform2=float(out[1]), tile_uniform3=float(out[2]), tile_uniform4=float(out[3]),
-                    fold_mirror=float(out[4]), worklist=float(out[5]))
+                    fold_mirror=float(out[4]), worklist=float(out[5]), tile_settled=float(out[6]))
 
     def fold_stages(self):
         """stages of the fold of the resident dense tile plan: one dict per stage with the number of images, of uniform tiles per
@@ -596,6 +599,15 @@ class Context:
         n = self.L.pnl_get_fold_stages(self.h, out.ctypes.data, 17)
         self.check(min(n, 0))
         return [dict(images=int(r[0]), uniform={2: int(r[1]), 3: int(r[2]), 4: int(r[3])}, mixed=int(r[4])) for r in out[:n]]
+
+    def settled_tiles(self):
+        """the settled tiles (block a, block b) of the resident dense tile plan, [n, 2]"""
+        n = self.L.pnl_get_settled_tiles(self.h, None, 0)
+        self.check(min(n, 0))
+        tiles = np.zeros((n, 2), dtype=np.int32)
+        if n:
+            self.check(min(self.L.pnl_get_settled_tiles(self.h, tiles.ctypes.data, n), 0))
+        return tiles
 
     def fold_plan(self, nblocks):
         """the staged plan: images[:, 3] = (row range, column range, stage), stage and uniform order (0: none) of tile (a, b) as

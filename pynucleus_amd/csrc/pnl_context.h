@@ -83,6 +83,14 @@ struct pnl_context {
     // the tiles that several order classes visit, the storage itself (allocated by the first assembly that uses it)
     DevBuf b_scolbase, b_srowoff, b_cpoff, b_cpslot, b_cprow, b_foldtab, b_bkcls, b_bfcls, b_bdefer, b_multitiles, b_slotA, b_candtiles, b_candq;
     int slot_S = 0, n_multitiles = 0;
+    // settled tiles of the resident plan (dense 2D P1, one order class; pnl_setup.hip: settle_tiles): the last n_settled mixed tiles of
+    // b_tiles, their pair codes in b_codes (512 16-bit words per tile, allocated with the tile lists and dropped with them).
+    // settled_want: the plan was made without the option PNL_MIXED_UNSETTLED; code_builds: times this context has computed codes;
+    // settled_run: tiles the last assembly took through k_tile_distant<.., SETTLED>
+    DevBuf b_codes;
+    int n_settled = 0, settled_want = -1, settled_run = 0;
+    std::vector<int2> settled_tiles;              // host copy of the settled part of the list (pnl_get_settled_tiles)
+    long long code_builds = 0;
     // staged fold of the 2D P1 one-class path (pnl_setup.hip: stage_plan): blocks that hold a copy of a DoF of every range of 32 DoFs
     // (CSR, from upload_slot_tables), per stage the packed images (range i << 16 | range j) in b_foldimg, per order and stage the offsets
     // into the uniform lists; stg_K = 0: no stages (one fold of the whole matrix behind all tiles)
@@ -357,6 +365,9 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
 // pnl_hip.hip, for pnl_upload_tiles: k_tile_order_range<ctx->tile> over the ncand tiles in b_candtiles, one order (or 0) each into
 // host_out through b_candq; synchronises the stream
 int pnl_tile_order_range(pnl_context *ctx, const DevFormula &qo, int ncand, signed char *host_out);
+// pnl_hip.hip, for pnl_upload_tiles: k_tile_pair_codes over n tiles of 64 cells (device pointer): codes (device, 512 words per tile) and /
+// or host_stat (per tile -1 not settled, else its number of pairs of a 6-point rule) may be nullptr; synchronises the stream
+int pnl_tile_pair_codes(pnl_context *ctx, const DevFormula &qo, const int2 *tiles, int n, unsigned short *codes, int *host_stat);
 // pnl_hip.hip: counting sort of a work list by order (k_wl_hist / _scan / _scatter): histogram, offsets, 16-pair chunk offsets and cursors
 // of the bins, PNL_WL_BINS + 1 words each, carved out of aux_base
 struct WlBins { unsigned *hist, *offs, *coff, *cursor; };

@@ -94,6 +94,16 @@ struct DevProblem {
     int mix_struct = 0;
 };
 
+// How the threads of a tile workgroup (k_tile_distant, k_tile_pair_codes) share the tile x tile cell pairs of a tile: thread tid keeps
+// cell j = tid % tile of block b and visits in its k-th sweep the row r of the wrapped diagonals, pair p = r tile + j, whose cell of
+// block a is i = (r + PNL_DIAG_MULT j) mod tile.  The pair codes of a settled tile (pnl_context::b_codes) follow from it: 2 bits per pair,
+// the pair of sweep k in bits 2 k, 2 k + 1 of the 16-bit word codes[tile index][tid] (64 x 64 pairs, 512 threads: 8 sweeps)
+#ifndef PNL_DIAG_MULT
+#define PNL_DIAG_MULT 21
+#endif
+__host__ __device__ constexpr int tile_sweep_row(int tid, int k, int tile, int nt) { return k*(nt/tile)+tid/tile; }
+__host__ __device__ constexpr int tile_diag_cell(int r, int j, int tile) { return (r+PNL_DIAG_MULT*j)%tile; }
+
 // row of the dense output that global DoF I is stored in (identity without a row slab); -1: not stored by this rank
 __device__ __forceinline__ long long pnl_row(const DevProblem &P, int I) { return P.rowmap ? (long long)P.rowmap[I] : (long long)I; }
 // ... and the column of global DoF J (the columns of a rank's slab are the DoFs of its cells and of all later cells)

@@ -171,32 +171,60 @@ int ensure_worklist(pnl_context *ctx, double pairs, int regions) {
 }
 
 // the mixed tiles of the current class (k_tile_distant): one region of the work list, reused by every class / orientation pass; the
-// fill counter wlc of pass p stays in slot p (check_overflow)
-template <int DIM, int DPE, int TILE, int KT>
+// fill counter wlc of pass p stays in slot p (check_overflow).
+// The plan lists the unsettled tiles first, then the settled ones with their pair codes in b_codes (pnl_setup.hip).  An assembly that
+// writes the block-slot storage of the whole operator (one rank, symmetric, no PNL_FLAG_SYMMETRIC_FLUSH) runs the unsettled tiles
+// -- they fill the work list --, then the settled ones through the SETTLED instantiation with a ticket counter of its own; every
+// other assembly takes the whole list through the classifying kernel.
+template <int DIM, int DPE, int TILE, int KT, bool SETTLED = false>
 int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, int cell_begin, int cell_end, const SlotOut &SO) {
     using S = TileSmem<DIM, DPE, TILE, KT == 0>;
-    const int ntiles = ctx->n_mixed;
+    // the SETTLED instantiations: every KT the dense 2D P1 launcher dispatches
+    constexpr bool can_settle = DIM == 2 && DPE == 3 && TILE == 64;
+    int ntiles = ctx->n_mixed, first = 0, ns = 0;
+    unsigned *ctr = (unsigned*)ctx->b_tilectr.p;
+    if (can_settle && ctx->cls.size() == 1 && SO.A2 && !ctx->symflush && !ctx->nonsym && ctx->b_codes.p && cell_begin <= 0 && cell_end >= ctx->nc)
+        ns = std::min(ctx->n_settled, ntiles);
+    if (SETTLED) {
+        first = ntiles-ns; ntiles = ns;
+        // a ticket counter of the block the assembly zeroed at its start, like the uniform-tile launches (pnl_tile2.hip)
+        ctr = (unsigned*)ctx->b_unictr.p+ctx->uni_ctr_next;
+        ctx->uni_ctr_next = (ctx->uni_ctr_next+1)%pnl_context::UNI_CTRS;
+        if (ctx->uni_ctr_fresh > 0) ctx->uni_ctr_fresh--;
+        else HIPCHK(ctx, hipMemsetAsync(ctr, 0, sizeof(unsigned), ctx->stream));
+    } else {
+        ntiles -= ns;
+        ctx->settled_run = ns;
+        HIPCHK(ctx, hipMemsetAsync(ctr, 0, sizeof(unsigned), ctx->stream));
+    }
     const int acc_stride = acc_stride_of(ctx->nU, S::fixed_bytes);
     const size_t lds = S::fixed_bytes+sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
     if (lds > 160*1024)
         return fail(ctx, PNL_ERR_UNSUPPORTED, "a block of %d cells touches %d DoFs: LDS sub-block of %zu bytes exceeds 160 KiB "
                     "(cells must be numbered with spatial locality)", TILE, ctx->nU, lds);
-    HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
-    auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false>;
+    auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false, false, SETTLED>;
     const int grid_mult = pnl_tune("PNL_GRID_MULT") ? atoi(pnl_tune("PNL_GRID_MULT")) : 1;
     const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT), lds, ntiles, 2, grid_mult);
     if (g.rc) return g.rc;
-    if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] tiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", ntiles, ctx->nU, lds, g.per_cu);
+    if (pnl_tune("PNL_VERBOSE"))
+        fprintf(stderr, "[pnl] %stiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", SETTLED ? "settled " : "", ntiles, ctx->nU, lds, g.per_cu);
     SlotOut SOk = SO;
     SOk.nU = ctx->nU;                                       // rows of the LDS sub-block (also without the block-slot storage)
+    // the time of the settled launch counts for the mixed-tile kernel and is reported on its own as well
     kt_begin(ctx, PNL_K_TILE_GENERAL);
+    if (SETTLED) kt_begin(ctx, PNL_K_TILE_SETTLED);
     if (g.grid > 0)
-        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)), (const int2*)ctx->b_tiles.p+ctx->tile_off, A,
+        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)),
+                           (const int2*)ctx->b_tiles.p+ctx->tile_off+first, A,
                            (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), cell_begin, cell_end, acc_stride, (int4*)ctx->b_wl.p,
                            wlc, ctx->wl_cap_each, ctx->ablate | (ctx->symflush ? 256 : 0), ntiles, ClusterTiles{},
-                           (unsigned*)ctx->b_tilectr.p, SOk);
+                           ctr, SOk, SETTLED ? (const unsigned short*)ctx->b_codes.p : (const unsigned short*)nullptr);
+    if (SETTLED) kt_end(ctx, PNL_K_TILE_SETTLED);
     kt_end(ctx, PNL_K_TILE_GENERAL);
     HIPCHK(ctx, hipGetLastError());
+    if constexpr (can_settle && !SETTLED) {
+        if (ns > 0) return launch_mixed_tiles<DIM, DPE, TILE, KT, true>(ctx, wlc, A, ldA, cell_begin, cell_end, SO);
+    }
     return PNL_OK;
 }
 
@@ -541,6 +569,7 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     ctx->tiles_launched = ntiles > 0;
+    ctx->settled_run = 0;
     ctx->fold_event_set = false;
     ctx->stg_active = false;
     // variable order, zero exterior: the distant (cell, facet) pairs of ALL classes run in one launch with per-class kernel /
@@ -778,7 +807,7 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
                                            pl->chunk_stride, lds, g.per_cu);
         hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, ctx->P), (const int2*)nullptr, (double*)nullptr, 0ll,
                            (double*)nullptr, 0, ctx->nc, acc_stride, (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, ctx->wl_cap, 0,
-                           pl->ntiles, CT, (unsigned*)ctx->b_tilectr.p, SlotOut{});
+                           pl->ntiles, CT, (unsigned*)ctx->b_tilectr.p, SlotOut{}, (const unsigned short*)nullptr);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
@@ -995,6 +1024,26 @@ int pnl_wl_sort(pnl_context *ctx, const int4 *wl, const unsigned *count, unsigne
     hipLaunchKernelGGL(k_wl_hist, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, count, cap, B.hist);
     hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(64), 0, ctx->stream, (const unsigned*)B.hist, B.offs, B.coff, B.cursor);
     hipLaunchKernelGGL(k_wl_scatter, dim3(512), dim3(PNL_NTHREADS), 0, ctx->stream, wl, count, cap, (const unsigned*)B.offs, B.cursor, sorted);
+    return PNL_OK;
+}
+
+// the tile plan (pnl_setup.hip): k_tile_pair_codes over n tiles (device pointer); codes: 512 words per tile or nullptr; host_stat: per tile
+// -1 not settled, else its number of 6-point pairs, through b_candq, or nullptr.  Synchronises the stream.
+int pnl_tile_pair_codes(pnl_context *ctx, const DevFormula &qo, const int2 *tiles, int n, unsigned short *codes, int *host_stat) {
+    if (n <= 0) return PNL_OK;
+    if (ctx->tile != 64) return fail(ctx, PNL_ERR_STATE, "pair codes: tiles of 64 cells");
+    int rc;
+    if (host_stat && (rc = ensure(ctx, ctx->b_candq, sizeof(int)*(size_t)n))) return rc;
+    // the cell tables of finalize and the packed rules; the first plan of a context is made before pnl_refresh_tables has run
+    DevProblem P = ctx->P;
+    P.qmax = ctx->qmax;
+    P.tt_n = (const int*)ctx->b_ttn.p;
+    if (!P.tt_n || !P.cslot) return fail(ctx, PNL_ERR_STATE, "pair codes: rules and DoF map first");
+    hipLaunchKernelGGL(k_tile_pair_codes<64>, dim3(std::min(n, 256*8)), dim3(512), 0, ctx->stream, P, qo, tiles, n, codes,
+                       host_stat ? (int*)ctx->b_candq.p : (int*)nullptr);
+    HIPCHK(ctx, hipGetLastError());
+    if (host_stat) HIPCHK(ctx, hipMemcpyAsync(host_stat, ctx->b_candq.p, sizeof(int)*(size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PNL_OK;
 }
 

@@ -537,6 +537,42 @@ template <int DIM, int DPE>
 __device__ __forceinline__ unsigned eval_distant_cut(const DevProblem &P, const double *__restrict__ tab, int stp, int n, const double *av,
                                                      const double *bv, PairAcc<DIM, DPE> &R);
 
+// The decision of the tile kernels about the cell pair (i of block a, j of block b), on the cell data staged as in TileSmem: does the
+// pair exist (both cells real and `sel`, what the launch adds to that), has it a DoF (NA:138-150), do the cells share a vertex
+// (NO:311-323; the ids are compared only where the centres are within the sum of the two radii), and the order of a distant pair
+// (fp32 formula, fp64 where that cannot decide).  k_tile_distant classifies with it, k_tile_pair_codes records its result for the
+// tile plan: ONE function, so that the two cannot disagree.  between(any_dof, shared) runs in front of the order formula and says
+// whether the order is wanted (finite horizon: REMOTE pairs have none).  Returns the order, 0: no distant pair to integrate.
+template <int DIM, int TILE, class Between>
+__device__ __forceinline__ int tile_pair_order(const DevFormula &qo, bool sel, int2 cfa, int2 cfb, const double *s_cen, const double (&cenb)[DIM],
+                                               const int *s_vid, const float *s_lh, float lhb, float Llb, const double *s_h, const double *s_Ld,
+                                               int i, int j, bool order2, Between &&between) {
+    constexpr int NV = DIM+1;
+    if (!((cfa.x & cfb.x & 1) && sel)) return 0;
+    const bool any_dof = ((cfa.x | cfb.x) & 2) != 0;
+    double d2 = 0.;
+#pragma unroll
+    for (int d = 0; d < DIM; d++) {
+        const double t = s_cen[(0*DIM+d)*TILE+i]-cenb[d];
+        d2 += t*t;
+    }
+    bool shared = false;
+    const float rs = __int_as_float(cfa.y)+__int_as_float(cfb.y);
+    if ((float)d2 <= rs*rs) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            const int va = s_vid[(0*NV+k)*TILE+i];
+#pragma unroll
+            for (int m = 0; m < NV; m++) shared = shared || (va == s_vid[(1*NV+m)*TILE+j]);
+        }
+    }
+    if (!between(any_dof, shared) || !any_dof || shared) return 0;
+    if (order2) return 2;
+    int q = quad_order_try(qo, s_lh[i], lhb, s_lh[TILE+i], Llb, d2);
+    if (q < 0) q = quad_order_exact(qo, s_h[i], s_h[TILE+j], s_Ld[i], s_Ld[TILE+j], sqrt(d2));
+    return q;
+}
+
 // Occupancy of the general tile kernel: its LDS (about 72 KB) lets two workgroups share a CU, so the waves per SIMD come from the
 // workgroup size: 512 threads at <= 128 VGPRs give 4 waves per SIMD (the unrolled 6-point evaluator stays spill-free because
 // its loop-invariant rule constants live in SGPRs); measured at noRef 7: 256 x 2 waves 69.7 ms, 384 x 3 101.6 ms (spills in
@@ -559,12 +595,18 @@ __device__ __forceinline__ unsigned eval_distant_cut(const DevProblem &P, const 
 #endif
 __host__ __device__ constexpr int tile_threads(int dpe, int kt, bool fh = false) { return (dpe > 3 || (kt == 0 && !PNL_KT0_WIDE) || fh) ? 256 : PNL_TILE_THREADS; }
 __host__ __device__ constexpr int tile_waves(int dpe, int kt, bool fh = false) { return dpe > 3 ? 1 : (((kt == 0 && !PNL_KT0_WIDE) || fh) ? 2 : PNL_TILE_WAVES); }
-template <int DIM, int DPE, int TILE, int KT, bool CLUSTER, bool FH = false>
+// SETTLED (dense 2D P1, tiles the plan has settled: pnl_setup.hip, k_tile_pair_codes): every pair of the tile is absent or a distant
+// pair of order 2, 3 or 4 with a packed rule, and the plan has recorded which: the first pass of the classification is a 16-bit load
+// per thread (codes[tile index][thread], layout: pnl_device.h) and the cell data only it reads is not staged.  Lists, chunk queue,
+// evaluation, flush and statistics are the same code, and they see the same lists in the same order.
+template <int DIM, int DPE, int TILE, int KT, bool CLUSTER, bool FH = false, bool SETTLED = false>
 __global__ void __launch_bounds__(tile_threads(DPE, KT, FH), tile_waves(DPE, KT, FH))
 k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__restrict__ A, long long ldA,
                double *__restrict__ Dglob, int cell_begin, int cell_end, int acc_stride, int4 *__restrict__ worklist,
                unsigned *__restrict__ wl_count, unsigned wl_cap, int ablate, int ntiles, const ClusterTiles CT,
-               unsigned *__restrict__ tile_ctr, const SlotOut SO) {
+               unsigned *__restrict__ tile_ctr, const SlotOut SO, const unsigned short *__restrict__ codes) {
+    static_assert(!SETTLED || (!CLUSTER && !FH && DIM == 2 && DPE == 3 && TILE*TILE == 8*tile_threads(DPE, KT, FH)),
+                  "settled tiles: dense 2D P1, eight pairs per thread");
     // debug switches that skip work (evaluation, accumulation, flush) exist only in PNL_DEBUG_ABLATE builds; bit 256 is
     // PNL_FLAG_SYMMETRIC_FLUSH
 #ifdef PNL_DEBUG_ABLATE
@@ -592,6 +634,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     const int tid = threadIdx.x;
     int *s_chunk = s_int+S::o_chunk;
     int *s_dslot = s_int+S::o_dslot, *s_cell = s_int+S::o_cell;     // cluster tiles: D slots and cell ids of both sides
+    unsigned short *s_code = (unsigned short*)s_vid;                // settled tiles: the code words of the threads, in place of the vertex ids
     // statistics of order q = 2 + tid (+256) are kept in registers over all tiles of this workgroup: hot counters
     // see one atomic per workgroup, not one per tile
     unsigned long long st_cnt[(PNL_MAXQ+NT)/NT] = {0}, st_ev[(PNL_MAXQ+NT)/NT] = {0};
@@ -630,21 +673,24 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         }
 #pragma unroll
         for (int k = 0; k < NC; k++) s_v[(side*NC+k)*TILE+l] = P.cellv[(size_t)k*P.ncp+c];
+        s_vol[side*TILE+l] = P.cvol[c];
+        int vid0 = -1;
+        // what only the classification reads (settled tiles: not staged)
+        if (!SETTLED) {
 #pragma unroll
         for (int d = 0; d < DIM; d++) s_cen[(side*DIM+d)*TILE+l] = P.ccen[(size_t)d*P.ncp+c];
-        s_vol[side*TILE+l] = P.cvol[c];
         s_h[side*TILE+l] = P.ch[c];
         // ln h and |ln(h/H0)| per cell are precomputed on the host (finalize)
         const double lh = P.clog[c], Ld = P.clog[(size_t)P.ncp+c];
         s_Ld[side*TILE+l] = Ld;
         s_lh[(side*2+0)*TILE+l] = (float)lh;
         s_lh[(side*2+1)*TILE+l] = (float)Ld;
-        int vid0 = -1;
 #pragma unroll
         for (int k = 0; k < NV; k++) {
             const int v = real ? P.cvid[(size_t)k*P.ncp+c] : -1-k;
             s_vid[(side*NV+k)*TILE+l] = v;
             vid0 = k == 0 ? v : vid0;
+        }
         }
         bool has_dof = false;
 #pragma unroll
@@ -655,8 +701,9 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
             has_dof = has_dof || sl >= 0;
         }
         // what the classification reads per cell: one 8-byte word (padding and volume-zero cells carry negative vertex ids)
-        s_cf[side*TILE+l] = make_int2((vid0 >= 0 ? 1 : 0) | (has_dof ? 2 : 0), __float_as_int((float)P.clog[2*(size_t)P.ncp+c]));
+        if (!SETTLED) s_cf[side*TILE+l] = make_int2((vid0 >= 0 ? 1 : 0) | (has_dof ? 2 : 0), __float_as_int((float)P.clog[2*(size_t)P.ncp+c]));
     }
+    if (SETTLED) s_code[tid] = codes[(size_t)tile_idx*NT+tid];
     };
     // The tiles of a workgroup run as a software pipeline: the cell data of the NEXT tile is staged before the flush of this one is
     // issued (a load issued behind the stores / atomics would wait for all of them), the flush zeroes the accumulators it has
@@ -702,14 +749,21 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     // of one returning LDS atomic per list and 64 pairs), and the second pass writes the entries.  Vertex ids are compared only
     // where the centres are within the sum of the two radii (a handful of pairs per tile away from the diagonal).
     static_assert(NT%TILE == 0 && PAIRS%NT == 0 && PER_THREAD <= 16, "tile workgroup: whole rows of the tile per sweep");
-    constexpr int ROWS = NT/TILE, NG = (PER_THREAD+3)/4;
-    const int j = tid%TILE, row0 = tid/TILE;
-    double cenb[DIM];
+    constexpr int NG = (PER_THREAD+3)/4;
+    const int j = tid%TILE;
+    const unsigned code = SETTLED ? s_code[tid] : 0u;
+    // what the classification reads of cell j (settled tiles: none of it is staged)
+    double cenb[DIM] = {};
+    int2 cfb = make_int2(0, 0);
+    float lhb = 0.f, Llb = 0.f;
+    int labb = 0;
+    if constexpr (!SETTLED) {
 #pragma unroll
-    for (int d = 0; d < DIM; d++) cenb[d] = s_cen[(1*DIM+d)*TILE+j];
-    const int2 cfb = s_cf[TILE+j];
-    const float lhb = s_lh[2*TILE+j], Llb = s_lh[3*TILE+j];
-    const int labb = (!CLUSTER && P.cur_class >= 0) ? P.clabel[tb*TILE+j] : 0;
+        for (int d = 0; d < DIM; d++) cenb[d] = s_cen[(1*DIM+d)*TILE+j];
+        cfb = s_cf[TILE+j];
+        lhb = s_lh[2*TILE+j]; Llb = s_lh[3*TILE+j];
+        labb = (!CLUSTER && P.cur_class >= 0) ? P.clabel[tb*TILE+j] : 0;
+    }
     int nw0 = 0, nw1 = 0, nw2 = 0, nw3 = 0;                // this wave's pairs in list A, list B, the far list, list C
     unsigned long long recs[NG];
 #pragma unroll
@@ -717,44 +771,31 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     recs[g] = 0ull;
 #pragma unroll 2
     for (int it4 = 0; it4 < (PER_THREAD-4*g < 4 ? PER_THREAD-4*g : 4); it4++) {
-        const int r = (4*g+it4)*ROWS+row0;
-        const int i = (r+PNL_DIAG_MULT*j)%TILE;
+        const int r = tile_sweep_row(tid, 4*g+it4, TILE, NT);
+        const int i = tile_diag_cell(r, j, TILE);
         int q = 0, fkey = 0;
-        const int2 cfa = s_cf[i];
+        if constexpr (SETTLED) {
+            // the plan's code of the pair: 0 none, 1 .. 3 order 2 .. 4
+            const int c = (int)(code >> (2*(4*g+it4))) & 3;
+            q = c ? c+1 : 0;
+        } else {
         const int ca = ta*TILE+i;
         // dense: upper triangle of the cell pairs, a-cells of the caller's range.  Cluster tiles: n1 == n2 -> unordered pairs
         // once (chunk pair a <= b); n1 != n2 -> every ordered pair (X in n1.cells, Y in n2.cells); identical cells share all
         // vertices and are left to the touching-pair lists like every other touching pair
-        bool ok = (cfa.x & cfb.x & 1) && !(abl & 8) &&
-                  (CLUSTER ? (!sym || ta < tb || i < j) : ((ta < tb || i < j || (fh && i == j)) && (ca >= cell_begin) && (ca < cell_end)));
+        bool sel = !(abl & 8) &&
+                   (CLUSTER ? (!sym || ta < tb || i < j) : ((ta < tb || i < j || (fh && i == j)) && (ca >= cell_begin) && (ca < cell_end)));
         // variable order: this launch assembles the pairs of one order class only
-        if (!CLUSTER && P.cur_class >= 0 && ok) {
+        if (!CLUSTER && P.cur_class >= 0 && sel) {
             const int la = P.clabel[ca];
-            ok = P.cls_of[P.orient ? labb*P.nlab+la : la*P.nlab+labb] == P.cur_class;
+            sel = P.cls_of[P.orient ? labb*P.nlab+la : la*P.nlab+labb] == P.cur_class;
         }
-        if (ok) {
-            // NA:138-150: skip pairs with boundary DoFs only;  NO:311-323: shared vertices -> singular pair
-            const bool any_dof = ((cfa.x | cfb.x) & 2) != 0;
-            double d2 = 0.;
-#pragma unroll
-            for (int d = 0; d < DIM; d++) {
-                const double t = s_cen[(0*DIM+d)*TILE+i]-cenb[d];
-                d2 += t*t;
-            }
-            bool shared = false;
-            const float rs = __int_as_float(cfa.y)+__int_as_float(cfb.y);
-            if ((float)d2 <= rs*rs) {
-#pragma unroll
-                for (int k = 0; k < NV; k++) {
-                    const int va = s_vid[(0*NV+k)*TILE+i];
-#pragma unroll
-                    for (int m = 0; m < NV; m++) shared = shared || (va == s_vid[(1*NV+m)*TILE+j]);
-                }
-            }
-            // finite horizon (getSparse): REMOTE pairs are dropped, pairs CUT by the horizon and touching pairs go to the
-            // sorted sparse pipeline through the far list (keys order + PNL_CUT_SHIFT / 121 + shared vertices - 1, like
-            // k_fh_pairs), pairs inside the horizon are integrated here
-            int rel = PNL_INTERACT;
+        // finite horizon (getSparse): REMOTE pairs are dropped, pairs CUT by the horizon and touching pairs go to the
+        // sorted sparse pipeline through the far list (keys order + PNL_CUT_SHIFT / 121 + shared vertices - 1, like
+        // k_fh_pairs), pairs inside the horizon are integrated here
+        int rel = PNL_INTERACT;
+        q = tile_pair_order<DIM, TILE>(P.qo, sel, s_cf[i], cfb, s_cen, cenb, s_vid, s_lh, lhb, Llb, s_h, s_Ld, i, j, (abl & 16) != 0,
+                                       [&](bool any_dof, bool shared) {
             if (!CLUSTER && fh && any_dof) {
                 if (shared) {
                     int common = 0;
@@ -770,31 +811,29 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
                     rel = rel_position<DIM>(P.k.horizon2, av, bv);
                 }
             }
-            if (any_dof && !shared && rel != PNL_REMOTE) {
-                if (abl & 16) q = 2;
-                else {
-                    q = quad_order_try(P.qo, s_lh[i], lhb, s_lh[TILE+i], Llb, d2);
-                    if (q < 0) q = quad_order_exact(P.qo, s_h[i], s_h[TILE+j], s_Ld[i], s_Ld[TILE+j], sqrt(d2));
-                }
-                if (q > P.qmax || q > PNL_MAXQ) { overflow++; q = 0; }
-                else if (rel == PNL_CUT) {
-                    if (q > PNL_CUT_SHIFT || P.off[q+1]-P.off[q] > PNL_WL_LANE_MAXPTS) { overflow++; q = 0; }
-                    else fkey = q+PNL_CUT_SHIFT;
-                }
+            return rel != PNL_REMOTE;
+        });
+        if (q) {
+            if (q > P.qmax || q > PNL_MAXQ) { overflow++; q = 0; }
+            else if (rel == PNL_CUT) {
+                if (q > PNL_CUT_SHIFT || P.off[q+1]-P.off[q] > PNL_WL_LANE_MAXPTS) { overflow++; q = 0; }
+                else fkey = q+PNL_CUT_SHIFT;
             }
+        }
         }
         // statistics: the three lowest orders (nearly all pairs) are counted with ballots on the scalar unit and added to the
         // LDS histogram once per tile; the LDS atomics of the hot loop are left to the rare higher orders
-        const int nq = q ? s_ttn[q] : 0;
+        const int nq = SETTLED ? 1 : (q ? s_ttn[q] : 0);    // settled tiles: every order of the tile has a packed rule
         const int key = fkey ? fkey : q;
         const int cls = !key ? 0 : (fkey ? 4 : (q == qA0 ? 1 : (q == qB0 ? 2 : (nq > 0 ? 3 : 4))));
         const int qs = (fh && cls == 4) ? 0 : q;         // finite horizon: the sparse pipeline counts what it is handed
         if (!(abl & 32)) {
         cnt234[0] += __popcll(__ballot(qs == 2)); cnt234[1] += __popcll(__ballot(qs == 3)); cnt234[2] += __popcll(__ballot(qs == 4));
-        wave_bucket_add(s_cnt, qs > 4 ? qs : 0, false);
+        if (!SETTLED) wave_bucket_add(s_cnt, qs > 4 ? qs : 0, false);
         }
         nw0 += __popcll(__ballot(cls == 1)); nw1 += __popcll(__ballot(cls == 2));
-        nw2 += __popcll(__ballot(cls == 4)); nw3 += __popcll(__ballot(cls == 3));
+        if (!SETTLED) nw2 += __popcll(__ballot(cls == 4));
+        nw3 += __popcll(__ballot(cls == 3));
         // finite horizon: cut pairs whose order has a packed rule are integrated in this tile (bit 11 -> bit 20 of the entry)
         const unsigned rec = (unsigned)cls | ((unsigned)key << 3) | ((fh && fkey > PNL_CUT_SHIFT+1 && fkey < 121 && nq > 0) ? (1u << 11) : 0u);
         recs[g] |= (unsigned long long)rec << (16*it4);
@@ -813,7 +852,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
             for (int it4 = 0; it4 < (PER_THREAD-4*g < 4 ? PER_THREAD-4*g : 4); it4++) {
                 const unsigned rec = (unsigned)(recs[g] >> (16*it4)) & 0xffffu;
                 const int cls = rec & 7, key = (rec >> 3) & 255;
-                const int p = ((4*g+it4)*ROWS+row0)*TILE+j;
+                const int p = tile_sweep_row(tid, 4*g+it4, TILE, NT)*TILE+j;
                 if (nw0) {
                     const unsigned long long m = __ballot(cls == 1);
                     if (cls == 1) s_list[bA+__popcll(m & lt)] = (unsigned short)(p | ((qA0-2) << 12));
@@ -829,14 +868,14 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
                     if (cls == 3) s_list[PAIRS-1-(bC+__popcll(m & lt))] = (unsigned short)(p | ((key-2) << 12));
                     bC += __popcll(m);
                 }
-                if (nw2) {
+                if (!SETTLED && nw2) {
                     const unsigned long long m = __ballot(cls == 4);
                     if (cls == 4) s_l32[PAIRS-1-(bF+__popcll(m & lt))] = p | (key << 12) | ((rec & (1u << 11)) ? (1 << 20) : 0);
                     bF += __popcll(m);
                 }
             }
     }
-    if (overflow) atomicAdd(&P.counters[5], (unsigned long long)overflow);
+    if (!SETTLED && overflow) atomicAdd(&P.counters[5], (unsigned long long)overflow);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 3; k++) if (cnt234[k]) atomicAdd(&s_cnt[2+k], cnt234[k]);
@@ -863,7 +902,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     bool published = false;                                // has a barrier followed the chunk table (workgroup-uniform)
     {
         // far pairs: one reservation in the global work list per tile, then a coalesced copy
-        const int nF = s_misc[2];
+        const int nF = SETTLED ? 0 : s_misc[2];                // settled tiles hand nothing to the work list
         if (fh) {
             // entries of the sorted sparse pipeline, one reservation per wave and 64 entries: (pair index, 0, rule offset,
             // n | key << 16) + the pair itself, what k_fh_pairs writes
@@ -3304,7 +3343,8 @@ k_cluster_boundary(const DevProblem P, const double *__restrict__ verts, const i
 // ---------------------------------------------------------------------------------------------
 // Exact order range of a tile (block a, block b), a != b, both blocks full: the order formula (FL2:622-642) of all
 // TILE x TILE cell pairs, evaluated with the SAME function the general tile kernels use (quad_order_fast), and the
-// shared-vertex test of getProtoPanelType (NO:280-378).  out[t] = q if every pair is a distant pair of order q, else 0.
+// shared-vertex test of getProtoPanelType (NO:280-378).  out[t] = q if every pair is a distant pair of order q; -1 if the pairs are
+// distant pairs of several orders, all of them in 2 .. 4: a candidate for a settled tile (k_tile_pair_codes decides); else 0.
 // Run once per tile list on the tiles the host's two-sided bounds (tile_uniform_order) could not settle: the ring where
 // the order steps from q to q+1 is a few cells wide, the bounds over two 64-cell blocks leave a band of several blocks.
 template <int TILE>
@@ -3348,7 +3388,81 @@ k_tile_order_range(const DevProblem P, const DevFormula qo, const int2 *__restri
         }
         atomicMin(&s_red[0], mn); atomicMax(&s_red[1], mx); atomicOr(&s_red[2], bad);
         __syncthreads();
-        if (tid == 0) out[t] = (signed char)((!s_red[2] && s_red[0] == s_red[1] && s_red[0] >= 2 && s_red[0] < 120) ? s_red[0] : 0);
+        if (tid == 0)
+            out[t] = (signed char)((!s_red[2] && s_red[0] == s_red[1] && s_red[0] >= 2 && s_red[0] < 120) ? s_red[0]
+                                   : ((!s_red[2] && s_red[0] >= 2 && s_red[0] < s_red[1] && s_red[1] <= 4) ? -1 : 0));
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Pair codes of the settled tiles (dense 2D P1, tile plan in pnl_setup.hip).  A mixed tile (block a, block b), a != b, both blocks
+// full, is settled if the classification of k_tile_distant finds nothing in it but absent pairs and distant pairs of the orders
+// 2 .. 4 with a packed rule: no touching pair, nothing for the work list.  That depends on the mesh, the DoF map and the order formula
+// alone, so the plan records it once: 2 bits per pair (0: no pair, 1 .. 3: order 2 .. 4), the eight pairs of thread tid of the tile
+// kernel in the 16-bit word codes[t][tid] (pnl_device.h).  The same threads visit the same pairs as in k_tile_distant, on cell data
+// staged like there, and decide with the same function (tile_pair_order).
+// stat[t] (if given): -1 the tile is not settled, else its number of pairs of a 6-point rule; codes (if given) are written for every tile.
+template <int TILE>
+__global__ void __launch_bounds__(512)
+k_tile_pair_codes(const DevProblem P, const DevFormula qo, const int2 *__restrict__ tiles, int ntiles, unsigned short *__restrict__ codes,
+                  int *__restrict__ stat) {
+    constexpr int DIM = 2, NV = 3, DPE = 3, NT = 512, SWEEPS = TILE*TILE/NT;
+    static_assert(SWEEPS == 8, "2 bits per pair, one 16-bit word per thread");
+    __shared__ double s_cen[2*DIM*TILE], s_h[2*TILE], s_Ld[2*TILE];
+    __shared__ float s_lh[4*TILE];
+    __shared__ int s_vid[2*NV*TILE];
+    __shared__ int2 s_cf[2*TILE];
+    __shared__ int s_red[2];
+    const int tid = threadIdx.x;
+#pragma unroll 1
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int2 tl = tiles[t];
+        // as k_tile_distant stages the cells of a dense tile
+        for (int u = tid; u < 2*TILE; u += NT) {
+            const int side = u/TILE, l = u%TILE, c = (side ? tl.y : tl.x)*TILE+l;
+#pragma unroll
+            for (int d = 0; d < DIM; d++) s_cen[(side*DIM+d)*TILE+l] = P.ccen[(size_t)d*P.ncp+c];
+            s_h[side*TILE+l] = P.ch[c];
+            const double lh = P.clog[c], Ld = P.clog[(size_t)P.ncp+c];
+            s_Ld[side*TILE+l] = Ld;
+            s_lh[(side*2+0)*TILE+l] = (float)lh;
+            s_lh[(side*2+1)*TILE+l] = (float)Ld;
+#pragma unroll
+            for (int k = 0; k < NV; k++) s_vid[(side*NV+k)*TILE+l] = P.cvid[(size_t)k*P.ncp+c];
+            bool has_dof = false;
+#pragma unroll
+            for (int k = 0; k < DPE; k++) has_dof = has_dof || P.cslot[(size_t)k*P.ncp+c] >= 0;
+            s_cf[side*TILE+l] = make_int2((P.cvid[c] >= 0 ? 1 : 0) | (has_dof ? 2 : 0), __float_as_int((float)P.clog[2*(size_t)P.ncp+c]));
+        }
+        if (tid < 2) s_red[tid] = 0;
+        __syncthreads();
+        const int j = tid%TILE;
+        double cenb[DIM];
+#pragma unroll
+        for (int d = 0; d < DIM; d++) cenb[d] = s_cen[(1*DIM+d)*TILE+j];
+        const int2 cfb = s_cf[TILE+j];
+        const float lhb = s_lh[2*TILE+j], Llb = s_lh[3*TILE+j];
+        unsigned code = 0u;
+        int bad = 0, n6 = 0;
+#pragma unroll 2
+        for (int k = 0; k < SWEEPS; k++) {
+            const int i = tile_diag_cell(tile_sweep_row(tid, k, TILE, NT), j, TILE);
+            const int q = tile_pair_order<DIM, TILE>(qo, true, s_cf[i], cfb, s_cen, cenb, s_vid, s_lh, lhb, Llb, s_h, s_Ld, i, j, false,
+                                                     [&](bool any_dof, bool shared) { bad |= (any_dof && shared) ? 1 : 0; return true; });
+            if (q) {
+                const int nq = (q <= 4 && q <= P.qmax) ? P.tt_n[q] : 0;
+                if (nq <= 0) bad = 1;
+                else { code |= (unsigned)(q-1) << (2*k); n6 += nq == 6 ? 1 : 0; }
+            }
+        }
+        if (codes) codes[(size_t)t*NT+tid] = (unsigned short)code;
+        if (stat) {
+            if (bad) atomicOr(&s_red[0], 1);
+            if (n6) atomicAdd(&s_red[1], n6);
+            __syncthreads();
+            if (tid == 0) stat[t] = s_red[0] ? -1 : s_red[1];
+        }
         __syncthreads();
     }
 }

@@ -78,7 +78,17 @@ void st_launch_kernel(bool bnd, int grid, const DevKernel &k, const double *tab,
 }  // namespace
 
 int pnl_selftest(int op, int path, int dim, int boundary, const void *param, int n, const double *in, double *out) {
-    if (n < 0 || (n > 0 && (!in || !out)) || op < PNL_SELFTEST_LOG || op > PNL_SELFTEST_QORDER) return PNL_ERR_INVALID;
+    if (n < 0 || (n > 0 && (!in || !out)) || op < PNL_SELFTEST_LOG || op > PNL_SELFTEST_SETTLED_LAYOUT) return PNL_ERR_INVALID;
+    if (op == PNL_SELFTEST_SETTLED_LAYOUT) {
+        // the pairs of the threads of the mixed-tile kernel (pnl_device.h), on the host
+        for (int i = 0; i < n; i++) {
+            const int v = (int)in[i], tid = v >> 3, k = v & 7;
+            if (v < 0 || tid >= 512) return PNL_ERR_INVALID;
+            const int j = tid%64, r = tile_sweep_row(tid, k, 64, 512);
+            out[3*(size_t)i] = r*64+j; out[3*(size_t)i+1] = tile_diag_cell(r, j, 64); out[3*(size_t)i+2] = j;
+        }
+        return PNL_OK;
+    }
     if (op >= PNL_SELFTEST_KERNEL && !param) return PNL_ERR_INVALID;
     if (op >= PNL_SELFTEST_KERNEL && dim != 1 && dim != 2) return PNL_ERR_INVALID;
     if (n == 0) return PNL_OK;

@@ -699,7 +699,7 @@ const char *const k_product_options[] = {"PNL_WL_FRAC", "PNL_FH_NOTILES", "PNL_N
                                          "PNL_NO_OVERLAP", "PNL_NO_FORK",
                                          // tests: at most this many workgroups of a persistent tile kernel (every workgroup then walks
                                          // many tiles at test sizes: the pipelined tile loops against the oracle)
-                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_MIXED_GENERIC",
+                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED",
                                          // staged fold of the dense 2D P1 assembly: far bands (0: one fold behind all tiles), spare workgroup
                                          // slots per CU of the far uniform launches, where the boundary term starts (3 / 4)
                                          "PNL_FOLD_STAGES", "PNL_UNI_SPARE", "PNL_BND_MODE"};
@@ -1155,19 +1155,24 @@ struct TilePlan {
 };
 
 static int fold_stages_wanted();
+// the option PNL_MIXED_UNSETTLED (a product option, read when the plan is made): the plan settles no mixed tile
+static int settled_wanted() { return pnl_tune("PNL_MIXED_UNSETTLED") ? 0 : 1; }
 
 // repeated assemblies of the same work list keep it resident
 static bool tiles_resident(const pnl_context *ctx, const std::vector<int2> &tiles, const TilePlan &R) {
     const std::vector<pnl_order_formula> &forms = R.forms;
     return tiles.size() == ctx->tiles_cached.size() && ctx->b_tiles.p && ctx->tiles_cb == R.cell_begin && ctx->tiles_ce == R.cell_end &&
         forms.size() == ctx->tiles_forms.size() && std::memcmp(forms.data(), ctx->tiles_forms.data(), sizeof(pnl_order_formula)*R.ncls) == 0 &&
-        ctx->tiles_filter == ctx->tile_cell_filter && ctx->stg_want == fold_stages_wanted() &&
+        ctx->tiles_filter == ctx->tile_cell_filter && ctx->stg_want == fold_stages_wanted() && ctx->settled_want == settled_wanted() &&
         (tiles.empty() || std::memcmp(tiles.data(), ctx->tiles_cached.data(), tiles.size()*sizeof(int2)) == 0);
 }
 
 // qof[i] for class k: -1 the class does not visit tile i, 2 .. 4 all its pairs are distant pairs of that order, 0 anything else.
-// The order bounds of the tiles on a few host threads (4.7 million tiles at 97,537 DoFs), then the exact range on the device
-static int tile_orders(pnl_context *ctx, const TilePlan &R, const std::vector<int2> &tiles, int k, std::vector<signed char> &qof) {
+// The order bounds of the tiles on a few host threads (4.7 million tiles at 97,537 DoFs), then the exact range on the device.
+// open_234: the tiles with qof 0 whose pairs are distant pairs of several of the orders 2 .. 4 (candidates of settle_tiles)
+static int tile_orders(pnl_context *ctx, const TilePlan &R, const std::vector<int2> &tiles, int k, std::vector<signed char> &qof,
+                       std::vector<size_t> &open_234) {
+    open_234.clear();
     const int T = R.T, L = R.L, qlimit = R.qlimit, cell_begin = R.cell_begin, cell_end = R.cell_end;
     const bool filter = R.filter, allow = R.allow, q2ok = R.q2ok;
     const std::vector<std::vector<int>> &blk_labels = R.blk_labels;
@@ -1211,10 +1216,48 @@ static int tile_orders(pnl_context *ctx, const TilePlan &R, const std::vector<in
     size_t moved = 0;
     for (size_t c = 0; c < cand.size(); c++) {
         const int q = cq[c];
+        if (q == -1) open_234.push_back(cand_idx[c]);
         if (q < 2 || q > qlimit || (q == 2 && !q2ok)) continue;
         qof[cand_idx[c]] = (signed char)q; moved++;
     }
     if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] exact order range: %zu of %zu open tiles are uniform\n", moved, cand.size());
+    return PNL_OK;
+}
+
+// ---- settled tiles (dense 2D P1, one order class without labels, symmetric, the whole cell range) ---------------------------------------
+// A mixed tile (a, b), a != b, both blocks full, is settled when the classification of k_tile_distant finds nothing in it but absent
+// pairs and distant pairs of the orders 2 .. 4 with a packed rule: most mixed tiles lie in the thin rings where the order steps
+// 2 -> 3 -> 4.  That depends on the mesh, the DoF map and the order formula alone -- what this plan is keyed on -- so the plan keeps
+// the outcome, 2 bits per pair (k_tile_pair_codes), and the SETTLED instantiation of the tile kernel loads it instead of classifying
+// 4096 pairs per tile in every assembly.  k_tile_order_range names the candidates, k_tile_pair_codes decides with the tile kernel's own
+// function.  settled: the settled tiles, those with the most pairs of a 6-point rule first (the tile loop hands out tickets: heavy
+// tiles first); is_settled: per entry of tiles.  No device memory for the codes, or no packed rules / DoF slots on the device: nothing is
+// settled, and that is no error.  The candidates come from the exact order range of tile_orders: where that is skipped (tuning option
+// PNL_NO_EXACT_TILES, uniform tiles switched off) nothing is settled either; a tile of ONE order 2 .. 4 that the uniform kernels do not
+// take (PNL_UNI_QMAX) is no candidate and stays with the classifying kernel.  The code kernel runs twice per plan (statistics of the
+// candidates, then the codes of the sorted list): a few milliseconds once per plan against an index array in the hot kernel.
+static int settle_tiles(pnl_context *ctx, const TilePlan &R, const std::vector<int2> &tiles, const std::vector<size_t> &open_234,
+                        std::vector<int2> &settled, std::vector<char> &is_settled) {
+    settled.clear();
+    is_settled.assign(tiles.size(), 0);
+    if (!settled_wanted() || open_234.empty() || !(R.p1 && ctx->dim == 2 && ctx->dpe == 3 && R.T == 64) || R.ncls != 1 || R.L > 0 ||
+        ctx->nonsym || !ctx->b_ttn.p || !ctx->b_cslot.p || R.cell_begin > 0 || R.cell_end < ctx->nc || open_234.size() > (size_t)0x7fffffff/512) return PNL_OK;
+    std::vector<int2> cand(open_234.size());
+    for (size_t c = 0; c < cand.size(); c++) cand[c] = tiles[open_234[c]];
+    int rc;
+    if ((rc = upload(ctx, ctx->b_candtiles, cand.data(), cand.size()))) return rc;
+    std::vector<int> stat(cand.size());
+    if ((rc = pnl_tile_pair_codes(ctx, to_dev(R.forms[0]), (const int2*)ctx->b_candtiles.p, (int)cand.size(), nullptr, stat.data()))) return rc;
+    std::vector<size_t> keep;
+    for (size_t c = 0; c < cand.size(); c++) if (stat[c] >= 0) keep.push_back(c);
+    if (keep.empty()) return PNL_OK;
+    if (ensure(ctx, ctx->b_codes, keep.size()*512*sizeof(unsigned short)) != PNL_OK) {
+        (void)hipGetLastError();
+        ctx->err.clear();
+        return PNL_OK;
+    }
+    std::stable_sort(keep.begin(), keep.end(), [&](size_t x, size_t y) { return stat[x] > stat[y]; });
+    for (size_t c : keep) { settled.push_back(cand[c]); is_settled[open_234[c]] = 1; }
     return PNL_OK;
 }
 
@@ -1468,15 +1511,24 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
     for (int u = 0; u < 3; u++) uni[u].resize(ncls);
     // the lists in tile order
     std::vector<signed char> qof(tiles.size());
+    std::vector<size_t> open_234;
+    std::vector<int2> settled;
+    std::vector<char> is_settled;
     int rc;
+    ctx->n_settled = 0;
     for (int k = 0; k < ncls; k++) {
-        if ((rc = tile_orders(ctx, R, tiles, k, qof))) return rc;
+        if ((rc = tile_orders(ctx, R, tiles, k, qof, open_234))) return rc;
+        if ((rc = settle_tiles(ctx, R, tiles, open_234, settled, is_settled))) return rc;
         for (size_t i = 0; i < tiles.size(); i++) {
             const int q = qof[i];
-            if (q < 0) continue;
+            if (q < 0 || is_settled[i]) continue;
             (q ? uni[q-2][k] : mixed[k]).push_back(tiles[i]);
         }
+        // the mixed list: its unsettled part in tile order (heavy first), then the settled tiles
+        mixed[k].insert(mixed[k].end(), settled.begin(), settled.end());
     }
+    if (settled.empty()) ctx->b_codes.release();
+    ctx->settled_tiles.clear();
     std::vector<int2> all;
     ctx->single_launch = R.p2;
     const int stages_wanted = fold_stages_wanted();
@@ -1486,9 +1538,20 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
     if (pnl_tune("PNL_VERBOSE")) {
         size_t nm = 0, nu[3] = {0, 0, 0};
         for (int k = 0; k < ncls; k++) { nm += mixed[k].size(); for (int u = 0; u < 3; u++) nu[u] += uni[u][k].size(); }
-        fprintf(stderr, "[pnl] tiles: %zu mixed, uniform order 2/3/4: %zu / %zu / %zu (qlimit %d)\n", nm, nu[0], nu[1], nu[2], qlimit);
+        fprintf(stderr, "[pnl] tiles: %zu mixed (%zu of them settled), uniform order 2/3/4: %zu / %zu / %zu (qlimit %d)\n", nm, settled.size(),
+                nu[0], nu[1], nu[2], qlimit);
     }
     if ((rc = upload(ctx, ctx->b_tiles, all.data(), all.size()))) return rc;
+    if (!settled.empty()) {
+        // the pair codes in the order of the list (settled implies one class: its mixed tiles are the first entries of b_tiles)
+        const int first = ctx->cls_tile_off[0]+ctx->cls_n_mixed[0]-(int)settled.size();
+        if ((rc = pnl_tile_pair_codes(ctx, to_dev(R.forms[0]), (const int2*)ctx->b_tiles.p+first, (int)settled.size(),
+                                      (unsigned short*)ctx->b_codes.p, nullptr))) return rc;
+        ctx->n_settled = (int)settled.size();
+        ctx->settled_tiles = settled;
+        ctx->code_builds++;
+    }
+    ctx->settled_want = settled_wanted();
     ctx->tile_off = 0; ctx->n_mixed = ctx->cls_n_mixed[0]; ctx->n_pure = ctx->cls_n_pure[0];
     ctx->tiles_cached = tiles; ctx->tiles_cb = cell_begin; ctx->tiles_ce = cell_end; ctx->tiles_forms = R.forms;
     ctx->tiles_filter = ctx->tile_cell_filter;
@@ -1651,6 +1714,18 @@ int pnl_get_counters(pnl_context *ctx, int64_t *out, int n) {
     HIPCHK(ctx, hipMemcpy(tmp, ctx->b_counters.p, sizeof(tmp), hipMemcpyDeviceToHost));
     tmp[0] = ctx->visited_is_assembled ? tmp[1] : ctx->visited_pairs;
     for (int i = 0; i < n && i < PNL_NCOUNTERS; i++) out[i] = (int64_t)tmp[i];
+    if (n > PNL_C_SETTLED_TILES) out[PNL_C_SETTLED_TILES] = ctx->settled_run;
+    if (n > PNL_C_CODE_BUILDS) out[PNL_C_CODE_BUILDS] = ctx->code_builds;
+    if (n > PNL_C_WORKLIST_LENGTH) {
+        // entries the tile kernels handed to the work lists, over the passes of the assembly (the fill counters check_overflow reads)
+        unsigned wl[PNL_WL_SLOTS];
+        const int ns = std::max(1, std::min(ctx->wl_slots, PNL_WL_SLOTS));
+        out[PNL_C_WORKLIST_LENGTH] = 0;
+        if (ctx->b_wlcount.p && ctx->wl_cap_each > 0) {
+            HIPCHK(ctx, hipMemcpy(wl, ctx->b_wlcount.p, sizeof(unsigned)*ns, hipMemcpyDeviceToHost));
+            for (int i = 0; i < ns; i++) out[PNL_C_WORKLIST_LENGTH] += wl[i];
+        }
+    }
     return check_overflow(ctx);
 }
 
@@ -1696,6 +1771,15 @@ int pnl_get_fold_stages(pnl_context *ctx, int64_t *out, int n) {
         if (s == 0) for (int k : ctx->cls_n_mixed) o[4] += k;
     }
     return K+1;
+}
+
+int pnl_get_settled_tiles(pnl_context *ctx, int32_t *tiles, int64_t ntiles) {
+    if (!ctx || ntiles < 0 || (ntiles && !tiles)) return PNL_ERR_INVALID;
+    if (!ctx->b_tiles.p || ctx->cls_n_mixed.empty()) return fail(ctx, PNL_ERR_STATE, "no tile plan yet");
+    const std::vector<int2> &st = ctx->settled_tiles;
+    if ((int)st.size() != ctx->n_settled) return fail(ctx, PNL_ERR_STATE, "the resident tile list is not that of a dense assembly");
+    for (size_t i = 0; i < st.size() && (int64_t)i < ntiles; i++) { tiles[2*i] = st[i].x; tiles[2*i+1] = st[i].y; }
+    return (int)st.size();
 }
 
 int pnl_get_fold_plan(pnl_context *ctx, int32_t *images, int64_t nimages, int8_t *tile_stage, int8_t *tile_order, int64_t ntiles) {
