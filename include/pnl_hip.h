@@ -664,6 +664,24 @@ int pnl_getrf(pnl_context *ctx, double *A_dev, int64_t ldA, int n, int32_t *piv_
  * right-hand sides gives the bits of the one-by-one solves.  Asynchronous on the context's stream. */
 int pnl_getrs(pnl_context *ctx, const double *LU_dev, int64_t ldLU, int n, const int32_t *piv_dev, double *B_dev, int64_t ldb, int nrhs);
 
+/* ---- linear combinations of dense blocks (csrc/pnl_interp.hip): the operators interpolated in the fractional order,
+ *      interpolationOperator (base/PyNucleus_base/linear_operators.pyx:1261-1391): A(s) = sum_k w_k(s) A(s_k) over the operators at the
+ *      Chebyshev nodes of an interval. ---------------------------------------------------------------------------------------------
+ * A_dev: HOST array of m device pointers to row-major nrows x ncols blocks with the common leading dimension ldA >= ncols;
+ * coeffs_host[m].  Pointers and coefficients travel in the kernel arguments: no upload, no allocation, no synchronisation per call;
+ * both calls are asynchronous on the context's stream.  The combined entry is t = c_0 a_0, then t = fma(c_k, a_k, t) in ascending k; the
+ * product then accumulates fma(t, x[c], acc).  All reductions have a fixed shape and use no floating-point atomics: the same input
+ * gives the same bits, whatever the alignment (16-byte loads and stores where the pointers and leading dimensions allow them, scalar
+ * ones otherwise).  PNL_ERR_INVALID, before any launch, for m < 1, m > PNL_INTERP_MAX_OPS, a null pointer (an entry of A_dev included),
+ * nrows or ncols < 1, a leading dimension below ncols, B_dev equal to an A_dev[k], x_dev equal to y_dev. */
+#define PNL_INTERP_MAX_OPS 21     /* M_max + 1 of the node selection */
+/* B[r][c] = sum_k coeffs[k] A_k[r][c] for r < nrows, c < ncols; the columns ncols .. ldB - 1 of B are not written */
+int pnl_lincomb(pnl_context *ctx, int m, const double *const *A_dev, int64_t ldA, int nrows, int ncols, const double *coeffs_host,
+                double *B_dev, int64_t ldB);
+/* y = alpha (sum_k coeffs[k] A_k) x + beta b with the conventions of pnl_gemv_axpby (b_dev may be y_dev; it is not read when beta == 0) */
+int pnl_gemv_multi(pnl_context *ctx, int m, const double *const *A_dev, int64_t ldA, int nrows, int ncols, const double *coeffs_host,
+                   const double *x_dev, double alpha, double beta, const double *b_dev, double *y_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,3 +17,5 @@ from .fractionalOrders import (variableConstFractionalOrder, leftRightFractional
                                smoothedInnerOuterFractionalOrder, feFractionalOrder, innerOuterFractionalOrder,
                                islandsFractionalOrder, sumFractionalOrder)
 from .builder import nonlocalBuilder, assembleNonlocalOperator  # noqa: F401
+from .operatorInterpolation import admissibleSet, getChebyIntervalsAndNodes  # noqa: F401
+from .kernels import RangedFractionalKernel  # noqa: F401

@@ -34,11 +34,12 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest',
            'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs',
            'pnl_csr_cg_jacobi', 'pnl_fe_space_create', 'pnl_fe_space_destroy', 'pnl_assemble_nonlinearity', 'pnl_imex_create',
-           'pnl_imex_destroy', 'pnl_imex_sweep']
+           'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi']
 
 PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
 PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
 PNL_IMEX_MAX_STAGES, PNL_IMEX_MAX_COMP = 4, 2
+PNL_INTERP_MAX_OPS = 21
 
 
 def source_sha16():
@@ -208,6 +209,8 @@ def load():
     L.pnl_imex_create.argtypes = [vp, C.POINTER(pnl_imex_desc), C.POINTER(vp)]
     L.pnl_imex_destroy.argtypes = [vp]
     L.pnl_imex_sweep.argtypes = [vp, vp, vp, vp, vp]
+    L.pnl_lincomb.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, i64]
+    L.pnl_gemv_multi.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, dbl, dbl, vp, vp]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
     L.pnl_upload_sparsity_device.argtypes = [vp, i32, vp, vp]
     L.pnl_set_classes.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -632,6 +635,25 @@ class Context:
     # -- solver side (multigrid, theta stepping) --------------------------------------------------
     def gemv_axpby(self, A_ptr, ldA, nrows, ncols, x_ptr, alpha, beta, b_ptr, y_ptr):
         self.check(self.L.pnl_gemv_axpby(self.h, C.c_void_p(A_ptr), int(ldA), int(nrows), int(ncols), C.c_void_p(x_ptr), float(alpha),
+                                         float(beta), C.c_void_p(b_ptr) if b_ptr else None, C.c_void_p(y_ptr)))
+
+    # -- linear combinations of dense blocks (pnl_interp.hip): the interpolated operators ------------
+    @staticmethod
+    def _block_list(A_ptrs, coeffs):
+        c = np.ascontiguousarray(coeffs, dtype=np.float64)
+        assert c.ndim == 1 and c.shape[0] == len(A_ptrs)
+        return (C.c_void_p*max(len(A_ptrs), 1))(*[int(p) if p else None for p in A_ptrs]), c
+
+    def lincomb(self, A_ptrs, ldA, nrows, ncols, coeffs, B_ptr, ldB):
+        """B = sum_k coeffs[k] A_k (A_ptrs: device pointers of the blocks, common leading dimension ldA)"""
+        arr, c = self._block_list(A_ptrs, coeffs)
+        self.check(self.L.pnl_lincomb(self.h, len(A_ptrs), arr, int(ldA), int(nrows), int(ncols), c.ctypes.data, C.c_void_p(B_ptr) if B_ptr else None,
+                                      int(ldB)))
+
+    def gemv_multi(self, A_ptrs, ldA, nrows, ncols, coeffs, x_ptr, alpha, beta, b_ptr, y_ptr):
+        """y = alpha (sum_k coeffs[k] A_k) x + beta b without forming the sum"""
+        arr, c = self._block_list(A_ptrs, coeffs)
+        self.check(self.L.pnl_gemv_multi(self.h, len(A_ptrs), arr, int(ldA), int(nrows), int(ncols), c.ctypes.data, C.c_void_p(x_ptr), float(alpha),
                                          float(beta), C.c_void_p(b_ptr) if b_ptr else None, C.c_void_p(y_ptr)))
 
     def csr_matvec(self, nrows, indptr_ptr, indices_ptr, data_ptr, x_ptr, alpha, beta, y_ptr):

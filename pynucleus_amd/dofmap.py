@@ -227,6 +227,21 @@ class DoFMap:
     def assembleNonlocal(self, kernel, matrixFormat='DENSE', **kwargs):
         """DoFMaps.pyx:808-900"""
         from .builder import nonlocalBuilder
+        from .kernels import RangedFractionalKernel
+        if isinstance(kernel, RangedFractionalKernel):
+            # DoFMaps.pyx:838-863: one operator per Chebyshev node of the order range, built when its interval is first selected
+            from .linear_operators import multiIntervalInterpolationOperator
+            from .operatorInterpolation import getChebyIntervalsAndNodes
+            s_left, s_right = kernel.admissibleOrders.ranges[0]
+            errorBound = kernel.errorBound if kernel.errorBound > 0. else 0.1*self.mesh.h**0.5
+            intervals, nodes = getChebyIntervalsAndNodes(float(s_left), float(s_right), min(self.mesh.diam, kernel.horizon.value), 1/2, errorBound,
+                                                         M_min=kernel.M_min, M_max=kernel.M_max, fixedXi=kernel.xi, variableOrder=True)
+
+            def delayed(s):
+                return lambda: self.assembleNonlocal(kernel.getFrozenKernel(s), matrixFormat, **dict(kwargs))
+            dm2 = kwargs.get('dm2')
+            shape = (self.num_dofs, self.num_dofs if dm2 is None else dm2.num_dofs)
+            return multiIntervalInterpolationOperator(intervals, nodes, [[delayed(float(s)) for s in n] for n in nodes], shape=shape)
         params = kwargs.pop('params', {})
         builder = nonlocalBuilder(self, kernel, params, **kwargs)
         fmt = matrixFormat.upper()

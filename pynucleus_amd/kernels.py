@@ -407,9 +407,48 @@ class FractionalKernel(Kernel):
         return 'kernel(fractional{}, {}, {}, {})'.format('-boundary' if self.boundary else '', self.s, self.interaction, self.scalingValue)
 
 
+class RangedFractionalKernel(FractionalKernel):
+    """kernelsCy.pyx:2096-2155: a fractional kernel whose constant order may be anywhere in ``admissibleOrders`` (one range).  It
+    behaves as the constant-order kernel of its current order (``setOrder``; the lower bound at first); DoFMap.assembleNonlocal
+    turns it into an operator interpolated in s from the operators of ``getFrozenKernel(s_k)`` at Chebyshev nodes s_k.
+    errorBound (<= 0: 0.1 h^0.5), M_min, M_max and xi steer operatorInterpolation.getChebyIntervalsAndNodes."""
+
+    def __init__(self, dim, admissibleOrders, horizon, normalized=True, tempered=0., errorBound=-1., M_min=1, M_max=20, xi=0.):
+        assert admissibleOrders.numParams == 1, 'Cannot handle {} params'.format(admissibleOrders.numParams)
+        if tempered != 0.:
+            raise NotImplementedError('tempered fractional kernels')
+        self.admissibleOrders = admissibleOrders
+        self._ranged = (int(dim), _getHorizon(horizon), bool(normalized))
+        self.tempered = tempered
+        self.errorBound = float(errorBound)
+        self.M_min, self.M_max = int(M_min), int(M_max)
+        self.xi = float(xi)
+        self.setOrder(admissibleOrders.getLowerBounds()[0])
+
+    def _constant_order_args(self, s):
+        assert self.admissibleOrders.isAdmissible(s), (s, self.admissibleOrders)
+        dim, horizon, normalized = self._ranged
+        # kernelsCy.pyx:2111-2114: the full space for an infinite horizon, the Euclidean ball otherwise
+        interaction = fullSpace() if horizon.value == np.inf else ball2_retriangulation(horizon.value)
+        return dim, float(s), horizon, interaction, None, normalized
+
+    def setOrder(self, s):
+        dim, s, horizon, interaction, _, normalized = self._constant_order_args(s)
+        scaling = constantFractionalLaplacianScaling(dim, s, horizon.value, 0.) if normalized else constantTwoPoint(0.5)
+        FractionalKernel.__init__(self, dim, constFractionalOrder(s), horizon, interaction, scaling, normalized=normalized)
+
+    def getFrozenKernel(self, s):
+        """the plain constant-order kernel of order s (what the node operators are assembled with)"""
+        return getFractionalKernel(*self._constant_order_args(s))
+
+    def __repr__(self):
+        return 'ranged '+FractionalKernel.__repr__(self)
+
+
 def _getFractionalOrder(s):
     from .fractionalOrders import variableFractionalOrder, singleVariableUnsymmetricFractionalOrder
-    if isinstance(s, (constFractionalOrder, variableFractionalOrder, singleVariableUnsymmetricFractionalOrder)):
+    from .operatorInterpolation import admissibleSet
+    if isinstance(s, (constFractionalOrder, variableFractionalOrder, singleVariableUnsymmetricFractionalOrder, admissibleSet)):
         return s
     if isinstance(s, (float, int, np.floating)):
         return constFractionalOrder(float(s))
@@ -477,6 +516,10 @@ def getFractionalKernel(dim, s, horizon=None, interaction=None, scaling=None, no
     horizonFun = _getHorizon(horizon)
     interaction = _getInteraction(interaction, horizonFun)
     from .fractionalOrders import variableFractionalOrder, singleVariableUnsymmetricFractionalOrder
+    from .operatorInterpolation import admissibleSet
+    if isinstance(sFun, admissibleSet):
+        # kernels.py:127-128 of the reference: a range of orders gives the ranged kernel
+        return RangedFractionalKernel(dim, sFun, horizonFun, normalized=normalized, tempered=tempered)
     if isinstance(sFun, (variableFractionalOrder, singleVariableUnsymmetricFractionalOrder)):
         # variableFractionalLaplacianScaling (kernelNormalization.pyx:329-364) is evaluated per element pair in evalParams
         return FractionalKernel(dim, sFun, horizonFun, interaction, None, None, piecewise, boundary, derivative, tempered,

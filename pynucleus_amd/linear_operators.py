@@ -509,3 +509,282 @@ class DistributedSparse_LinearOperator:
         A = torch.from_numpy(self.local.toarray())
         dist.all_reduce(A, group=self.group)
         return A.numpy()
+
+
+def lagrangeWeights(nodes, val, derivative=0):
+    """values (derivative = 0), first or second derivatives at ``val`` of the Lagrange basis on ``nodes``, in float64 on the host.
+
+    Neville's scheme on the unit vectors, as interpolationOperator.set of the reference (linear_operators.pyx:1287-1358): row j of
+    W holds the coefficients of the polynomial through the nodes j .. j + k after step k,
+        W_j <- W_a + (W_b - W_a) (val - x_a) / (x_b - x_a),
+    and the derivative rows follow by differentiating that line.  Of the two ends (a, b) = (j, j + k) or (j + k, j) the anchor a is
+    the node closer to val: the same polynomial, but the factor is at most 1/2 in magnitude and is exactly 0 at val = x_a, so at a node
+    the weights are exactly one-hot."""
+    x = np.ascontiguousarray(nodes, dtype=np.float64)
+    n = x.shape[0]
+    if derivative not in (0, 1, 2):
+        raise NotImplementedError('derivative {} not implemented'.format(derivative))
+    val = float(val)
+    W, W1, W2 = np.eye(n), np.zeros((n, n)), np.zeros((n, n))
+    for k in range(1, n):
+        m = n-k
+        lo, hi = x[:m], x[k:]
+        low = np.abs(val-lo) <= np.abs(val-hi)                   # anchor at the lower end of the node range
+        xa, xb = np.where(low, lo, hi), np.where(low, hi, lo)
+        inv = (1./(xb-xa))[:, None]
+        f = ((val-xa)/(xb-xa))[:, None]
+        sel = low[:, None]
+        if derivative == 2:
+            a, b = np.where(sel, W2[:m], W2[1:m+1]), np.where(sel, W2[1:m+1], W2[:m])
+            a1, b1 = np.where(sel, W1[:m], W1[1:m+1]), np.where(sel, W1[1:m+1], W1[:m])
+            W2[:m] = a+(b-a)*f+2.*(b1-a1)*inv
+        if derivative >= 1:
+            a, b = np.where(sel, W1[:m], W1[1:m+1]), np.where(sel, W1[1:m+1], W1[:m])
+            a0, b0 = np.where(sel, W[:m], W[1:m+1]), np.where(sel, W[1:m+1], W[:m])
+            W1[:m] = a+(b-a)*f+(b0-a0)*inv
+        a, b = np.where(sel, W[:m], W[1:m+1]), np.where(sel, W[1:m+1], W[:m])
+        W[:m] = a+(b-a)*f
+    return (W, W1, W2)[derivative][0].copy()
+
+
+def _is_pending(op):
+    """an entry of ``ops`` that still has to be built: a callable returning the operator (the reference's delayedNonlocalOp)"""
+    return callable(op) and not hasattr(op, 'matvec')
+
+
+class interpolationOperator:
+    """A(val) = sum_k c_k(val) A_k for operators A_k at the interpolation nodes of one interval [left, right]
+    (base/PyNucleus_base/linear_operators.pyx:1261-1391).  ``set(val, derivative)`` computes the weights c = the Lagrange basis on
+    ``nodes`` (or its first / second derivative) at val on the host; nothing is assembled or combined by it.
+
+    Entries of ``ops`` may be callables that return the operator; they are called when the operators are first needed.  Dense node
+    operators of one shape, leading dimension and device are applied and combined by the fused kernels of csrc/pnl_interp.hip
+    (``matvec`` streams the m blocks once, ``materialize`` forms the sum once); any other operators through their own matvec, summed
+    on the device."""
+
+    def __init__(self, ops, nodes, left, right, shape=None):
+        self.ops = list(ops)
+        self.nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+        assert self.nodes.ndim == 1 and len(self.ops) == self.nodes.shape[0] >= 1
+        assert np.all(self.nodes[:-1] < self.nodes[1:]), 'interpolation nodes must be strictly increasing'
+        self.left, self.right = float(left), float(right)
+        self.coeffs = np.full(self.nodes.shape[0], np.nan)
+        self.val = np.nan
+        self.derivative = -1
+        self._shape = None if shape is None else (int(shape[0]), int(shape[1]))
+
+    # -- weights -------------------------------------------------------------
+    def set(self, val, derivative=0):
+        derivative = int(derivative)
+        if derivative not in (0, 1, 2):
+            raise NotImplementedError('derivative {} not implemented'.format(derivative))
+        assert self.left <= val <= self.right, (val, self.left, self.right)
+        self.coeffs = lagrangeWeights(self.nodes, val, derivative)
+        self.val, self.derivative = float(val), derivative
+
+    @property
+    def numInterpolationNodes(self):
+        return self.nodes.shape[0]
+
+    def getNumInterpolationNodes(self):
+        return self.numInterpolationNodes
+
+    # -- the node operators ----------------------------------------------------
+    def assure_constructed(self):
+        for k, op in enumerate(self.ops):
+            if _is_pending(op):
+                self.ops[k] = op = op()
+                if hasattr(op, 'ctx'):
+                    op.ctx.synchronize()                   # every node operator is assembled on a context of its own: finished here, once
+        for op in self.ops:
+            if isinstance(op, (DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator)):
+                raise NotImplementedError('interpolation of distributed operators')
+        assert all(tuple(op.shape) == tuple(self.ops[0].shape) for op in self.ops), 'the node operators differ in shape'
+
+    @property
+    def constructed(self):
+        return not any(_is_pending(op) for op in self.ops)
+
+    @property
+    def shape(self):
+        if self._shape is None:
+            self.assure_constructed()
+            self._shape = tuple(int(v) for v in self.ops[0].shape)
+        return self._shape
+
+    num_rows = property(lambda self: self.shape[0])
+    num_columns = property(lambda self: self.shape[1])
+
+    def _ready(self):
+        assert self.derivative != -1, 'interpolationOperator: set(val) first'
+        self.assure_constructed()
+        return self.ops
+
+    def _fused(self):
+        """the node operators as dense blocks the fused kernels can take, or None"""
+        ops = self.ops
+        if len(ops) > 21 or not all(type(op) is Dense_LinearOperator for op in ops):
+            return None
+        A0 = ops[0].A
+        if not all(op.A.shape == A0.shape and op.A.stride(0) == A0.stride(0) and op.A.device == A0.device for op in ops):
+            return None
+        return [op.A for op in ops]
+
+    def _device(self):
+        for op in self.ops:
+            dev = getattr(op, 'device', None) or getattr(getattr(op, 'A', None), 'device', None)
+            if dev is not None:
+                return dev
+        return torch.device('cpu')
+
+    # -- application -------------------------------------------------------------
+    def _apply_dev(self, xd):
+        ops = self._ready()
+        blocks = self._fused()
+        if blocks is not None:
+            ctx, dev = ops[0].ctx, blocks[0].device
+            yd = torch.empty(self.shape[0], dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            ctx.gemv_multi([A.data_ptr() for A in blocks], blocks[0].stride(0), self.shape[0], self.shape[1], self.coeffs, xd.data_ptr(), 1., 0.,
+                           None, yd.data_ptr())
+            ctx.synchronize()
+            return yd
+        yd = None
+        arg = xd if xd.is_cuda else xd.numpy()             # operators on the host (numpy) take the host vector
+        for c, op in zip(self.coeffs, ops):
+            t = op.matvec(arg)
+            t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t, dtype=np.float64)).to(xd.device)
+            yd = float(c)*t if yd is None else yd.add_(t, alpha=float(c))
+        return yd
+
+    def matvec(self, x, y=None):
+        self._ready()
+        xd = _as_dev(x, self._device())
+        assert xd.shape[0] == self.shape[1]
+        yd = self._apply_dev(xd)
+        if isinstance(x, torch.Tensor):
+            if y is not None:
+                y.copy_(yd)
+                return y
+            return yd
+        out = yd.cpu().numpy()
+        if y is not None:
+            y[:] = out
+            return y
+        return out
+
+    def __mul__(self, x):
+        return self.matvec(x)
+
+    dot = matvec
+
+    @property
+    def diagonal(self):
+        ops = self._ready()
+        d = None
+        for c, op in zip(self.coeffs, ops):
+            t = torch.from_numpy(np.ascontiguousarray(op.diagonal, dtype=np.float64))
+            d = float(c)*t if d is None else d.add_(t, alpha=float(c))
+        return d.numpy()
+
+    def materialize(self):
+        """a fresh Dense_LinearOperator holding sum_k c_k A_k (one pass over the m blocks): the existing products, CG, chol / plu and
+        multigrid classes work on it unchanged.  Dense node operators only."""
+        ops = self._ready()
+        blocks = self._fused()
+        if blocks is None:
+            raise NotImplementedError('materialize() needs dense node operators of one shape on one device')
+        ctx, A0 = ops[0].ctx, blocks[0]
+        nrows, ncols = self.shape
+        ld = (ncols+7) & ~7                                # rows on 64-byte lines, as the builder's blocks
+        B = torch.empty((nrows, ld), dtype=torch.float64, device=A0.device)
+        B[:, ncols:].zero_()                               # the kernel leaves the padding columns alone
+        B = B[:, :ncols]
+        torch.cuda.current_stream(A0.device).synchronize()
+        ctx.lincomb([A.data_ptr() for A in blocks], A0.stride(0), nrows, ncols, self.coeffs, B.data_ptr(), B.stride(0))
+        ctx.synchronize()
+        return Dense_LinearOperator(B, ctx, dict(interpolated=dict(val=self.val, derivative=self.derivative)),
+                                    symmetric=all(op.symmetric for op in ops))
+
+    def toarray(self):
+        ops = self._ready()
+        if self._fused() is not None:
+            return self.materialize().A.cpu().numpy()
+        out = None
+        for c, op in zip(self.coeffs, ops):
+            t = torch.from_numpy(np.ascontiguousarray(op.toarray(), dtype=np.float64)).to(self._device())
+            out = float(c)*t if out is None else out.add_(t, alpha=float(c))
+        return out.cpu().numpy()
+
+    def __repr__(self):
+        return '<{}x{} {} with {} interpolation nodes>'.format(self.shape[0], self.shape[1], type(self).__name__, self.numInterpolationNodes)
+
+
+class multiIntervalInterpolationOperator:
+    """interpolation operators on adjacent intervals; ``set(val)`` selects the first interval that contains val and sets its weights,
+    everything else acts on the selected one (base/PyNucleus_base/linear_operators.pyx:1393-1504).  The operators of an interval are
+    built when ``set`` first selects it."""
+
+    def __init__(self, intervals, nodes, ops, shape=None):
+        assert len(intervals) == len(nodes) == len(ops) >= 1
+        self.ops = [interpolationOperator(ops[k], nodes[k], intervals[k][0], intervals[k][1], shape=shape) for k in range(len(intervals))]
+        self.left = min(float(a) for a, _ in intervals)
+        self.right = max(float(b) for _, b in intervals)
+        self.selected = -1
+
+    def get(self):
+        return self.ops[self.selected].val if self.selected != -1 else np.nan
+
+    def set(self, val, derivative=0):
+        assert self.left <= val <= self.right, (val, self.left, self.right)
+        for k, op in enumerate(self.ops):
+            if op.left <= val <= op.right:
+                op.set(val, derivative)
+                op.assure_constructed()
+                self.selected = k
+                return
+        assert False, val
+
+    def getSelectedOp(self):
+        assert self.selected != -1, 'multiIntervalInterpolationOperator: set(val) first'
+        return self.ops[self.selected]
+
+    def assure_constructed(self):
+        for op in self.ops:
+            op.assure_constructed()
+
+    @property
+    def shape(self):
+        return (self.ops[self.selected] if self.selected != -1 else self.ops[0]).shape
+
+    num_rows = property(lambda self: self.shape[0])
+    num_columns = property(lambda self: self.shape[1])
+
+    def matvec(self, x, y=None):
+        return self.getSelectedOp().matvec(x, y)
+
+    def __mul__(self, x):
+        return self.matvec(x)
+
+    dot = matvec
+
+    @property
+    def diagonal(self):
+        return self.getSelectedOp().diagonal
+
+    def toarray(self):
+        return self.getSelectedOp().toarray()
+
+    def materialize(self):
+        return self.getSelectedOp().materialize()
+
+    @property
+    def numInterpolationNodes(self):
+        return sum(op.numInterpolationNodes for op in self.ops)
+
+    def getNumInterpolationNodes(self):
+        return self.numInterpolationNodes
+
+    def __repr__(self):
+        return '<{}x{} {} with {} intervals and {} interpolation nodes>'.format(self.shape[0], self.shape[1], type(self).__name__, len(self.ops),
+                                                                                 self.numInterpolationNodes)
