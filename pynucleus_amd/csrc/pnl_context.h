@@ -21,6 +21,43 @@ struct DevBuf {
     void release() { if (p) { (void)hipFree(p); p = nullptr; bytes = 0; } }
 };
 
+// The phase events of an assembly (pnl_context::ev).  Every assembly path records all of them on the caller's stream, in the order
+// START, TILES_UNIFORM_DONE, TILES_DONE, WORKLIST_DONE, MIRROR_DONE, SINGULAR_DONE, BOUNDARY_DONE, END; a path without a phase records
+// its event right behind the one before.  pnl_get_phase_ms reads the differences.  EV_TILES_DONE and EV_TILES_UNIFORM_DONE are also
+// events that side streams wait for (the boundary term beside the fold pass).  The values are the slots of the array.
+enum PhaseEvent {
+    EV_START = 0,               // counters and diagonal-block buffer zeroed, nothing launched yet
+    EV_WORKLIST_DONE = 1,       // work-list kernels (behind the fold + mirror pass of a block-slot assembly)
+    EV_MIRROR_DONE = 2,         // k_mirror of an assembly without block-slot storage
+    EV_SINGULAR_DONE = 3,       // touching pairs (joined, where they ran on a side stream)
+    EV_BOUNDARY_DONE = 4,       // boundary term joined
+    EV_END = 5,                 // diagonal blocks scattered
+    EV_TILES_DONE = 6,          // last tile kernel (of the last class pass)
+    EV_TILES_UNIFORM_DONE = 7,  // uniform tiles (those of stage 0 with a staged fold)
+    EV_COUNT = 8
+};
+
+// What one assembly leaves for its own later phases and for pnl_get_counters / pnl_get_phase_ms / pnl_get_kernel_ms, and what means
+// nothing for the next assembly.  pnl_begin_assembly starts every C-ABI assembly call with a fresh record; each path then sets only
+// what it knows.  Plan state that survives assemblies (tile lists, n_settled, stg_K, wl_cap ...) stays in the context.
+struct AssemblyRun {
+    bool ev_valid = false;          // the phase events are all recorded: false until the assembly has succeeded
+    bool tiles_launched = false, pure_launched = false;     // phases "tiles" / "tiles_uniform" of pnl_get_phase_ms exist
+    bool symflush = false;          // PNL_FLAG_SYMMETRIC_FLUSH
+    bool tile_cell_filter = true;   // apply [cell_begin, cell_end) to the a-cells of the tiles too (not for a caller's tile list)
+    bool full_tile_list = false;    // the tile list is the whole upper block triangle of the cell range (pnl_assemble_dense)
+    // the tile kernels wrote the block-slot storage; ev_fold is recorded behind a fold + mirror pass; the staged sequence runs
+    bool slot_used = false, fold_event_set = false, stg_active = false;
+    int settled_run = 0;            // tiles taken through k_tile_distant<.., SETTLED>
+    int tile_off = 0, n_mixed = 0, n_pure = 0;      // slice of b_tiles of the class pass being launched (dense P1 / 1D)
+    // fill counters of b_wlcount in use (one per class / pass; 0: the path keeps none): pnl_get_counters sums them, check_overflow
+    int wl_slots = 0;               // holds them against wl_cap_each
+    int uni_ctr_next = 0, uni_ctr_fresh = 0;        // ticket counters of b_unictr: next to hand out, how many are still zeroed
+    int kev_n[PNL_NUM_KERNEL_SLOTS] = {}; bool kev_open[PNL_NUM_KERNEL_SLOTS] = {};    // timed launches per kernel slot (pairs of pnl_context::kev in use)
+    unsigned long long visited_pairs = 0;   // numCellPairs of pnl_get_counters, unless
+    bool visited_is_assembled = false;      // (finite-horizon tiles) every visited (non-REMOTE) pair is an assembled one
+};
+
 struct pnl_context {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -36,7 +73,6 @@ struct pnl_context {
     static constexpr int MAX_STAGES = 16;    // far bands of a staged fold (stage 0 + bands)
     hipEvent_t ev_stage[MAX_STAGES+1] = {};
     hipEvent_t ev_bnd = nullptr;             // zero fill of the diagonal-block buffer + class tables of the boundary term are in the stream
-    bool fold_event_set = false;
     std::string err;
     // host copies
     int dim = 0, nv = 0, nc = 0, dpe = 0, dpv = 0, dped = 0, N = 0, nb = 0, qmax = -1;
@@ -85,10 +121,9 @@ struct pnl_context {
     int slot_S = 0, n_multitiles = 0;
     // settled tiles of the resident plan (dense 2D P1, one order class; pnl_setup.hip: settle_tiles): the last n_settled mixed tiles of
     // b_tiles, their pair codes in b_codes (512 16-bit words per tile, allocated with the tile lists and dropped with them).
-    // settled_want: the plan was made without the option PNL_MIXED_UNSETTLED; code_builds: times this context has computed codes;
-    // settled_run: tiles the last assembly took through k_tile_distant<.., SETTLED>
+    // settled_want: the plan was made without the option PNL_MIXED_UNSETTLED; code_builds: times this context has computed codes
     DevBuf b_codes;
-    int n_settled = 0, settled_want = -1, settled_run = 0;
+    int n_settled = 0, settled_want = -1;
     std::vector<int2> settled_tiles;              // host copy of the settled part of the list (pnl_get_settled_tiles)
     long long code_builds = 0;
     // staged fold of the 2D P1 one-class path (pnl_setup.hip: stage_plan): blocks that hold a copy of a DoF of every range of 32 DoFs
@@ -103,10 +138,8 @@ struct pnl_context {
     std::vector<signed char> stg_tile_stage;      // [nblocks][nblocks] stage of tile (a, b), -1 below the diagonal
     std::vector<unsigned char> stg_tile_q;        // [nblocks][nblocks] order 2 .. 4 of a uniform tile, else 0
     // ticket counters of the uniform-tile launches (b_unictr, UNI_CTRS words): an assembly zeroes all of them at its start and hands
-    // them out in turn (uni_ctr_fresh left); launches beyond that zero their counter in the stream themselves
+    // them out in turn (AssemblyRun::uni_ctr_fresh left); launches beyond that zero their counter in the stream themselves
     static constexpr int UNI_CTRS = 64;
-    int uni_ctr_next = 0, uni_ctr_fresh = 0;
-    bool stg_active = false;                      // the current assembly runs the staged sequence
     long long slot_total = 0;         // doubles
     // row slab of a rank (pnl_set_row_slab, pnl_slab.hip)
     DevBuf b_rowmap, b_rowdof, b_colmap, b_coldof;
@@ -114,8 +147,6 @@ struct pnl_context {
     DevBuf b_luwork, b_lutmp;         // pnl_getrf (pnl_direct.hip): info word, ticket, pivot rows, partial maxima; pnl_getrs: the permuted right-hand sides
     std::vector<int32_t> slab_rowdofs, slab_coldofs;
     int slab_rows = 0, slab_cols = 0;
-    bool slot_full_list = false;      // the current tile list is the whole upper block triangle (pnl_assemble_dense)
-    bool slot_used = false;           // the tile kernels of the current assembly wrote the block-slot storage
     std::vector<DevKernel> kcls_host;
     std::vector<DevKernel> bkcls_host;
     std::vector<DevFormula> bfcls_host;
@@ -148,14 +179,13 @@ struct pnl_context {
     std::vector<int2> tiles_cached;   // tile list (as given by the caller) currently resident in b_tiles
     size_t tiles_cap = 0;
     // b_tiles holds the mixed tiles first, then the uniform ones (all pairs distant with the lowest order)
-    int n_mixed = 0, n_pure = 0, tile_off = 0, tiles_cb = -1, tiles_ce = -1;
+    int tiles_cb = -1, tiles_ce = -1;
     std::vector<int> cls_tile_off, cls_n_mixed, cls_n_pure;     // per order class: its slice of b_tiles (mixed tiles, then uniform)
     std::vector<int> cls_n_uni[3];    // uniform tiles of order 2, 3, 4 per class (cls_n_pure = cls_n_uni[0]); they follow the mixed ones
     // dim 2, dpe 6 (one launch over all classes): b_tiles = [mixed tiles of all classes][order 2][order 3][order 4], b_tilecls alike
     bool single_launch = false;
     int sl_off[4] = {0, 0, 0, 0}, sl_n[4] = {0, 0, 0, 0};
     unsigned wl_cap_each = 0;         // capacity of one work-list region (one region per class in a single-launch assembly)
-    int wl_slots = 1;                 // work-list counters in use by the current assembly (one per class / pass)
     std::vector<pnl_order_formula> tiles_forms;
     pnl_order_formula tiles_form;
     bool tiles_filter = true;
@@ -169,22 +199,17 @@ struct pnl_context {
     bool have_xform = false;
     double xform[4] = {1., 0., 0., 1.};
     std::vector<BlockAgg> blocks;
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[EV_COUNT] = {};     // the phase events, by PhaseEvent
     // event pair around every tile-kernel launch (pnl_get_kernel_ms); a slot that is launched several times per assembly (the
-    // stages of a staged fold) takes one more pair per launch, created on first use and kept; kev_n: launches of the current assembly
+    // stages of a staged fold) takes one more pair per launch, created on first use and kept; AssemblyRun::kev_n counts the launches
     std::vector<hipEvent_t> kev[PNL_NUM_KERNEL_SLOTS];
-    int kev_n[PNL_NUM_KERNEL_SLOTS] = {};
-    bool kev_open[PNL_NUM_KERNEL_SLOTS] = {};
-    bool pure_launched = false;
-    bool symflush = false;          // PNL_FLAG_SYMMETRIC_FLUSH of the current assembly
-    bool ev_valid = false;
-    unsigned long long visited_pairs = 0;
-    bool visited_is_assembled = false;      // finite-horizon tiles: every visited (non-REMOTE) pair is an assembled one
-    bool tiles_launched = false;
+    AssemblyRun run;                // the assembly in progress or, behind it, the last one (pnl_begin_assembly)
     int ablate = 0;                 // debug: PNL_ABLATE env bits (1 no LDS accumulate, 2 no evaluation)
-    bool tile_cell_filter = true;   // apply [cell_begin, cell_end) to the a-cells of the tiles too
     bool wl_lane = true;            // debug: PNL_WL_LANE=0 sends every work-list order to the 16-lanes-per-pair kernel
 };
+
+// once per C-ABI assembly call, where its arguments have been checked and before anything of the run is set
+inline void pnl_begin_assembly(pnl_context *ctx) { ctx->run = AssemblyRun{}; }
 
 inline int fail(pnl_context *ctx, int code, const char *fmt, ...) {
     char buf[512];
@@ -334,19 +359,19 @@ inline DevProblem with_mixed_rules(const pnl_context *ctx, DevProblem Pt) {
 
 inline void kt_begin(pnl_context *ctx, int slot) {
     std::vector<hipEvent_t> &v = ctx->kev[slot];
-    const size_t k = 2*(size_t)ctx->kev_n[slot];
-    ctx->kev_open[slot] = false;
+    const size_t k = 2*(size_t)ctx->run.kev_n[slot];
+    ctx->run.kev_open[slot] = false;
     while (v.size() < k+2) {
         hipEvent_t e = nullptr;
         if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return; }      // no timer for this launch
         v.push_back(e);
     }
-    ctx->kev_open[slot] = hipEventRecord(v[k], ctx->stream) == hipSuccess;
+    ctx->run.kev_open[slot] = hipEventRecord(v[k], ctx->stream) == hipSuccess;
 }
 inline void kt_end(pnl_context *ctx, int slot) {
-    if (!ctx->kev_open[slot]) return;
-    ctx->kev_open[slot] = false;
-    if (hipEventRecord(ctx->kev[slot][2*(size_t)ctx->kev_n[slot]+1], ctx->stream) == hipSuccess) ctx->kev_n[slot]++;
+    if (!ctx->run.kev_open[slot]) return;
+    ctx->run.kev_open[slot] = false;
+    if (hipEventRecord(ctx->kev[slot][2*(size_t)ctx->run.kev_n[slot]+1], ctx->stream) == hipSuccess) ctx->run.kev_n[slot]++;
 }
 
 // pnl_setup.hip: joins the vertex-order search finalize() started and uploads the permuted cell tables (sets have_tile_order)
@@ -358,6 +383,30 @@ int pnl_assembly_prepare(pnl_context *ctx);
 // its two halves: the checks with finalize; the problem description of the class / orientation ctx->cur / ctx->orient (launches nothing)
 int pnl_assembly_ready(pnl_context *ctx);
 void pnl_refresh_tables(pnl_context *ctx);
+
+// ctx->stream, ctx->cur and ctx->orient are implicit arguments of every launcher.  They change through these two scopes only, which put
+// them back on every way out of the region.
+// The launchers inside the scope go to `stream` (to() switches again); afterwards ctx->stream is what it was before
+struct StreamScope {
+    pnl_context *ctx;
+    hipStream_t prev;
+    StreamScope(pnl_context *c, hipStream_t stream) : ctx(c), prev(c->stream) { ctx->stream = stream; }
+    StreamScope(const StreamScope&) = delete; StreamScope &operator=(const StreamScope&) = delete;
+    void to(hipStream_t stream) { ctx->stream = stream; }
+    ~StreamScope() { ctx->stream = prev; }
+};
+// select(k, orient): setters and launchers act on order class k in that orientation, ctx->P describes it.  Afterwards the class is
+// leave_at and the orientation 0: the dense and the cluster assemblies leave class 0, the CSR pair assemblies the class they were
+// entered with (the caller's pnl_select_class holds).  refresh_after: ctx->P describes that class again
+struct ClassScope {
+    pnl_context *ctx;
+    int leave_at;
+    bool refresh_after;
+    ClassScope(pnl_context *c, int leave_at_, bool refresh_after_ = false) : ctx(c), leave_at(leave_at_), refresh_after(refresh_after_) {}
+    ClassScope(const ClassScope&) = delete; ClassScope &operator=(const ClassScope&) = delete;
+    void select(int k, int orient) { ctx->cur = k; ctx->orient = orient; pnl_refresh_tables(ctx); }
+    ~ClassScope() { ctx->cur = leave_at; ctx->orient = 0; if (refresh_after) pnl_refresh_tables(ctx); }
+};
 // pnl_setup.hip, the tile plan of a dense assembly: the tiles (block a, block b >= a) of a cell range, heavy ones first; which of
 // the caller's tiles are of one order, the lists per class / of the single-launch P2 layout in b_tiles (kept while nothing changes)
 int pnl_make_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin, int cell_end);

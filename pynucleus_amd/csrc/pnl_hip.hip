@@ -4,17 +4,9 @@
 // field; next to them the kernels that are no templates (k_mirror, the work-list sort) and the launch of k_tile_order_range
 // for the tile plan.  Launches on the caller's stream and the side streams of the context.  Context, uploads, finalize() and the
 // tile plan are host code of pnl_setup.hip; what the two units ask of each other is declared in pnl_context.h.
-#include <hip/hip_runtime.h>
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-#include "pnl_hip.h"
+#include "pnl_context.h"
 #include "pnl_kernels.h"
 #include "pnl_bndtile.h"
-#include "pnl_context.h"
 #include "pnl_launch.h"
 
 namespace {
@@ -64,41 +56,41 @@ void scatter_diag(pnl_context *ctx, const DevProblem &P, const double *D, double
 
 template <int DIM, int DPE, int KT>
 int launch_pure(pnl_context *ctx, double *A, int64_t ldA, const SlotOut &SO) {
-    if (ctx->n_pure == 0) return PNL_OK;
+    if (ctx->run.n_pure == 0) return PNL_OK;
     constexpr int NP = DIM == 2 ? 3 : 2, ND = DPE*(DPE+1)/2;
     const int acc_stride = acc_stride_of(ctx->nU);
     const size_t lds = sizeof(double)*(64*NP*DIM+64+2*64*ND+NP*(4+DPE)+(KT == 0 ? PNL_POW_TAB_DOUBLES : 0))+sizeof(int)*(64*DPE+64)
                        +sizeof(double)*(size_t)(ctx->nU+1)*acc_stride;
     auto kfun = k_tile_pure<DIM, DPE, KT>;
-    const PersistentGrid g = persistent_grid(ctx, kfun, PNL_NTHREADS, lds, ctx->n_pure, 2);
+    const PersistentGrid g = persistent_grid(ctx, kfun, PNL_NTHREADS, lds, ctx->run.n_pure, 2);
     if (g.rc) return g.rc;
-    if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] uniform tiles=%d of %d, lds=%zu bytes, occupancy API: %d blocks/CU\n", ctx->n_pure,
-                                       ctx->n_pure+ctx->n_mixed, lds, g.per_cu);
+    if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] uniform tiles=%d of %d, lds=%zu bytes, occupancy API: %d blocks/CU\n", ctx->run.n_pure,
+                                       ctx->run.n_pure+ctx->run.n_mixed, lds, g.per_cu);
     int pure_abl = 0;
 #ifdef PNL_DEBUG_ABLATE
     pure_abl = pnl_tune("PNL_PURE_ABL") ? atoi(pnl_tune("PNL_PURE_ABL")) : 0;
 #endif
     kt_begin(ctx, PNL_K_TILE_UNIFORM2);
-    hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->tile_off+ctx->n_mixed,
-                       ctx->n_pure, A, (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), acc_stride, 2,
-                       (ctx->symflush ? 1 : 0) | pure_abl, SO);
+    hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->run.tile_off+ctx->run.n_mixed,
+                       ctx->run.n_pure, A, (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), acc_stride, 2,
+                       (ctx->run.symflush ? 1 : 0) | pure_abl, SO);
     kt_end(ctx, PNL_K_TILE_UNIFORM2);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
 
 // The per-class passes of a variable order run on side streams (pnl_context::aux): fork from the caller's stream, class k on
-// stream k mod NAUX (ctx->stream is redirected while a class is being launched), join back.  One class: nothing happens.
+// stream k mod NAUX (ctx->stream is redirected through `scope` while a class is being launched), join back.  One class: nothing happens.
 struct ClassFork {
     pnl_context *ctx;
-    hipStream_t main;
+    StreamScope scope;                  // scope.prev: the stream the fork was made on
     bool on, used[pnl_context::NAUX] = {};
     hipEvent_t start;
     // from: an event recorded earlier on the caller's stream (the fold pass) -- the side streams start there instead of behind
     // everything the caller's stream holds, so consecutive forked phases run back to back on every side stream
     ClassFork(pnl_context *c, int nclasses, hipEvent_t from = nullptr)
-        : ctx(c), main(c->stream), on(nclasses > 1 && !pnl_tune("PNL_NO_FORK")), start(from ? from : c->ev_fork) {
-        if (on && !from) (void)hipEventRecord(ctx->ev_fork, main);
+        : ctx(c), scope(c, c->stream), on(nclasses > 1 && !pnl_tune("PNL_NO_FORK")), start(from ? from : c->ev_fork) {
+        if (on && !from) (void)hipEventRecord(ctx->ev_fork, scope.prev);
     }
     // classes of very different weight (three layers: the pairs inside a layer against the few across an interface): heaviest first
     // onto the least loaded stream, so that two heavy classes do not queue behind each other while a stream of light ones runs dry
@@ -120,15 +112,15 @@ struct ClassFork {
         if (!on) return;
         const int j = k < (int)slot.size() ? slot[k] : k % pnl_context::NAUX;
         if (!used[j]) { (void)hipStreamWaitEvent(ctx->aux[j], start, 0); used[j] = true; }
-        ctx->stream = ctx->aux[j];
+        scope.to(ctx->aux[j]);
     }
     void join() {
         if (!on) return;
-        ctx->stream = main;
+        scope.to(scope.prev);
         for (int j = 0; j < pnl_context::NAUX; j++)
             if (used[j]) {
                 (void)hipEventRecord(ctx->ev_join[j], ctx->aux[j]);
-                (void)hipStreamWaitEvent(main, ctx->ev_join[j], 0);
+                (void)hipStreamWaitEvent(scope.prev, ctx->ev_join[j], 0);
                 used[j] = false;
             }
         on = false;
@@ -181,20 +173,20 @@ int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, 
     using S = TileSmem<DIM, DPE, TILE, KT == 0>;
     // the SETTLED instantiations: every KT the dense 2D P1 launcher dispatches
     constexpr bool can_settle = DIM == 2 && DPE == 3 && TILE == 64;
-    int ntiles = ctx->n_mixed, first = 0, ns = 0;
+    int ntiles = ctx->run.n_mixed, first = 0, ns = 0;
     unsigned *ctr = (unsigned*)ctx->b_tilectr.p;
-    if (can_settle && ctx->cls.size() == 1 && SO.A2 && !ctx->symflush && !ctx->nonsym && ctx->b_codes.p && cell_begin <= 0 && cell_end >= ctx->nc)
+    if (can_settle && ctx->cls.size() == 1 && SO.A2 && !ctx->run.symflush && !ctx->nonsym && ctx->b_codes.p && cell_begin <= 0 && cell_end >= ctx->nc)
         ns = std::min(ctx->n_settled, ntiles);
     if (SETTLED) {
         first = ntiles-ns; ntiles = ns;
         // a ticket counter of the block the assembly zeroed at its start, like the uniform-tile launches (pnl_tile2.hip)
-        ctr = (unsigned*)ctx->b_unictr.p+ctx->uni_ctr_next;
-        ctx->uni_ctr_next = (ctx->uni_ctr_next+1)%pnl_context::UNI_CTRS;
-        if (ctx->uni_ctr_fresh > 0) ctx->uni_ctr_fresh--;
+        ctr = (unsigned*)ctx->b_unictr.p+ctx->run.uni_ctr_next;
+        ctx->run.uni_ctr_next = (ctx->run.uni_ctr_next+1)%pnl_context::UNI_CTRS;
+        if (ctx->run.uni_ctr_fresh > 0) ctx->run.uni_ctr_fresh--;
         else HIPCHK(ctx, hipMemsetAsync(ctr, 0, sizeof(unsigned), ctx->stream));
     } else {
         ntiles -= ns;
-        ctx->settled_run = ns;
+        ctx->run.settled_run = ns;
         HIPCHK(ctx, hipMemsetAsync(ctr, 0, sizeof(unsigned), ctx->stream));
     }
     const int acc_stride = acc_stride_of(ctx->nU, S::fixed_bytes);
@@ -215,9 +207,9 @@ int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, 
     if (SETTLED) kt_begin(ctx, PNL_K_TILE_SETTLED);
     if (g.grid > 0)
         hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)),
-                           (const int2*)ctx->b_tiles.p+ctx->tile_off+first, A,
+                           (const int2*)ctx->b_tiles.p+ctx->run.tile_off+first, A,
                            (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), cell_begin, cell_end, acc_stride, (int4*)ctx->b_wl.p,
-                           wlc, ctx->wl_cap_each, ctx->ablate | (ctx->symflush ? 256 : 0), ntiles, ClusterTiles{},
+                           wlc, ctx->wl_cap_each, ctx->ablate | (ctx->run.symflush ? 256 : 0), ntiles, ClusterTiles{},
                            ctr, SOk, SETTLED ? (const unsigned short*)ctx->b_codes.p : (const unsigned short*)nullptr);
     if (SETTLED) kt_end(ctx, PNL_K_TILE_SETTLED);
     kt_end(ctx, PNL_K_TILE_GENERAL);
@@ -234,8 +226,8 @@ int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, 
 #endif
 template <int DIM, int DPE, int TILE, int KT>
 int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell_begin, int cell_end, const SlotOut &SO = SlotOut{}) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-    ctx->pure_launched = false;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
+    ctx->run.pure_launched = false;              // of this class pass
     // Staged fold (option PNL_FOLD_STAGES > 0; 2D P1, one order class, block-slot storage; the plan: stage_plan in pnl_setup.hip).
     // Measured at 98,304 cells, s = 1/2 (docs/CHANGELOG_kernels.md, round 6): no gain over the single fold for any number of bands --
     // what the side kernels do beside the tile kernels, the tile kernels lose -- so the default is 0.  Caller's stream: the uniform
@@ -246,7 +238,7 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
     // the ticket counters of the tile loops hand out work, no workgroup waits for another.  PNL_NO_OVERLAP: the same sequence on the
     // caller's stream.
     const bool staged = DIM == 2 && DPE == 3 && SO.A2 && ctx->stg_K > 0 && ctx->cls.size() == 1 && !ctx->nonsym;
-    ctx->stg_active = staged;
+    ctx->run.stg_active = staged;
     if (staged) {
         int rc;
         const int K = ctx->stg_K;
@@ -259,48 +251,45 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
         // measured with the work list on the other side streams as well, docs/CHANGELOG_kernels.md round 6: no gain either way)
         constexpr int wl_aux = 3;
         hipStream_t const wls = side ? ctx->aux[wl_aux] : caller;
-        struct StreamGuard { pnl_context *c; hipStream_t s; ~StreamGuard() { c->stream = s; } } stream_guard{ctx, caller};
-        const int2 *tiles = (const int2*)ctx->b_tiles.p+ctx->tile_off;
+        const int2 *tiles = (const int2*)ctx->b_tiles.p+ctx->run.tile_off;
         double *Dt = (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p);
         unsigned *wlc = (unsigned*)ctx->b_wlcount.p+wl_slot;
         auto uniform_stage = [&](int s, int spare_s) -> int {
-            int off = ctx->n_mixed;
+            int off = ctx->run.n_mixed;
             for (int q = 2; q <= 4; q++) {
                 const std::vector<int> &so = ctx->stg_uni_off[q-2];
                 const int n = so[s+1]-so[s];
                 int rcu = pnl2_launch_uniform(ctx, KT, tile_problem(ctx), tiles+off+so[s], nullptr, n, q, A, ldA, Dt, SO, spare_s);
                 if (rcu) return rcu;
-                ctx->pure_launched = ctx->pure_launched || n > 0;
+                ctx->run.pure_launched = ctx->run.pure_launched || n > 0;
                 off += so[K+1];
             }
             return PNL_OK;
         };
         auto fold_stage = [&](int s) -> int {
             if (side) HIPCHK(ctx, hipStreamWaitEvent(folds, ctx->ev_stage[s], 0));
-            ctx->stream = folds;
-            const int rcf = pnl2_fold_mirror(ctx, SO, A, ldA, (const unsigned*)ctx->b_foldimg.p+ctx->stg_img_off[s], ctx->stg_img_off[s+1]-ctx->stg_img_off[s]);
-            ctx->stream = caller;
-            return rcf;
+            StreamScope on(ctx, folds);
+            return pnl2_fold_mirror(ctx, SO, A, ldA, (const unsigned*)ctx->b_foldimg.p+ctx->stg_img_off[s], ctx->stg_img_off[s+1]-ctx->stg_img_off[s]);
         };
         if ((rc = uniform_stage(0, 0))) return rc;
-        HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
         if ((rc = launch_mixed_tiles<DIM, DPE, TILE, KT>(ctx, wlc, A, ldA, cell_begin, cell_end, SO))) return rc;
         HIPCHK(ctx, hipEventRecord(ctx->ev_stage[0], caller));
         if ((rc = fold_stage(0))) return rc;
         HIPCHK(ctx, hipEventRecord(ctx->ev_fold, folds));
-        ctx->fold_event_set = true;
+        ctx->run.fold_event_set = true;
         if (side && wls != folds) HIPCHK(ctx, hipStreamWaitEvent(wls, ctx->ev_fold, 0));
-        ctx->stream = wls;
-        rc = run_worklist<DIM, DPE, KT>(ctx, (const int4*)ctx->b_wl.p, wlc, ctx->wl_cap_each, A, ldA, true);
-        ctx->stream = caller;
-        if (rc) return rc;
+        {
+            StreamScope on(ctx, wls);
+            if ((rc = run_worklist<DIM, DPE, KT>(ctx, (const int4*)ctx->b_wl.p, wlc, ctx->wl_cap_each, A, ldA, true))) return rc;
+        }
         if (side && wls != folds) HIPCHK(ctx, hipEventRecord(ctx->ev_join[wl_aux], wls));
         for (int s = 1; s <= K; s++) {
             if ((rc = uniform_stage(s, spare))) return rc;
             HIPCHK(ctx, hipEventRecord(ctx->ev_stage[s], caller));
             if ((rc = fold_stage(s))) return rc;
         }
-        HIPCHK(ctx, hipEventRecord(ctx->ev[6], caller));                        // the last tile kernel is done
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_DONE], caller));                        // the last tile kernel is done
         if (side) {
             // what is left of the folds and the work list behind the last tile kernel: phase [1]
             HIPCHK(ctx, hipEventRecord(ctx->ev_join[2], folds));
@@ -314,38 +303,34 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
         // order-2 uniform tiles: 2D P1 the pipelined k_tile_uniform<3, 3> (with three or four workgroups per CU it beats k_tile_pure:
         // 41.3 against 45.5 ms at 98,304 cells, s = 1/2; PNL_PURE_V1=1 keeps k_tile_pure), 1D k_tile_pure
         if (DIM == 2 && DPE == 3 && !pnl_tune("PNL_PURE_V1") && ctx->uni_off[2] >= 0 && ctx->uni_np[2] == 3)
-            rc = pnl2_launch_uniform(ctx, KT, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->tile_off+ctx->n_mixed, nullptr, ctx->n_pure, 2,
+            rc = pnl2_launch_uniform(ctx, KT, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->run.tile_off+ctx->run.n_mixed, nullptr, ctx->run.n_pure, 2,
                                      A, ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), SO);
         else rc = launch_pure<DIM, (DPE <= 3 ? DPE : 3), KT>(ctx, A, ldA, SO);
         if (rc) return rc;
-        ctx->pure_launched = ctx->n_pure > 0;
+        ctx->run.pure_launched = ctx->run.n_pure > 0;
         if (DIM == 2 && DPE == 3) {
             // tiles whose pairs are all of order 3 / all of order 4 (6-point rules): pnl_tile2.h
-            int off = ctx->tile_off+ctx->n_mixed+ctx->n_pure;
+            int off = ctx->run.tile_off+ctx->run.n_mixed+ctx->run.n_pure;
             for (int q = 3; q <= 4; q++) {
                 const int n = ctx->cls_n_uni[q-2][ctx->cur];
                 if ((rc = pnl2_launch_uniform(ctx, KT, tile_problem(ctx), (const int2*)ctx->b_tiles.p+off, nullptr, n, q, A, ldA,
                                               (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), SO))) return rc;
-                ctx->pure_launched = ctx->pure_launched || n > 0;
+                ctx->run.pure_launched = ctx->run.pure_launched || n > 0;
                 off += n;
             }
         }
-        HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
     }
     unsigned *wlc = (unsigned*)ctx->b_wlcount.p+wl_slot;
-    {
-        int rc = launch_mixed_tiles<DIM, DPE, TILE, KT>(ctx, wlc, A, ldA, cell_begin, cell_end, SO);
-        if (rc) return rc;
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    if (int rc = launch_mixed_tiles<DIM, DPE, TILE, KT>(ctx, wlc, A, ldA, cell_begin, cell_end, SO)) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_DONE], ctx->stream));
     // block-slot storage: A = A' + A'^T is formed now (it overwrites A); the work-list kernels then write both images
     if (SO.A2) {
-        int rc = pnl2_fold_mirror(ctx, SO, A, ldA);
-        if (rc) return rc;
+        if (int rc = pnl2_fold_mirror(ctx, SO, A, ldA)) return rc;
         HIPCHK(ctx, hipEventRecord(ctx->ev_fold, ctx->stream));
-        ctx->fold_event_set = true;
+        ctx->run.fold_event_set = true;
     }
-    return run_worklist<DIM, DPE, KT>(ctx, (const int4*)ctx->b_wl.p, wlc, ctx->wl_cap_each, A, ldA, ctx->symflush || SO.A2 != nullptr);
+    return run_worklist<DIM, DPE, KT>(ctx, (const int4*)ctx->b_wl.p, wlc, ctx->wl_cap_each, A, ldA, ctx->run.symflush || SO.A2 != nullptr);
 }
 
 template <int DIM, int DPE, int KT>
@@ -474,9 +459,9 @@ int launch_tiles_single(pnl_context *ctx, double *A, int64_t ldA, int cell_begin
     const bool var = ctx->nlab > 0;
     ctx->kcls_host.resize(ncls); ctx->fcls_host.resize(ncls);
     bool all_fast = true, all_half = true;
+    ClassScope cls(ctx, 0);
     for (int k = 0; k < ncls; k++) {
-        ctx->cur = k; ctx->orient = 0;
-        pnl_refresh_tables(ctx);
+        cls.select(k, 0);
         ctx->kcls_host[k] = ctx->P.k; ctx->fcls_host[k] = ctx->P.qo;
         all_fast = all_fast && ctx->P.k.fast;
         all_half = all_half && ctx->P.k.fast && ctx->P.k.qm == 6;
@@ -490,62 +475,57 @@ int launch_tiles_single(pnl_context *ctx, double *A, int64_t ldA, int cell_begin
     if ((rc = ensure(ctx, ctx->b_fcls, sizeof(DevFormula)*ncls))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->b_kcls.p, ctx->kcls_host.data(), sizeof(DevKernel)*ncls, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->b_fcls.p, ctx->fcls_host.data(), sizeof(DevFormula)*ncls, hipMemcpyHostToDevice, ctx->stream));
-    ctx->cur = 0;
-    pnl_refresh_tables(ctx);
+    cls.select(0, 0);
     const int2 *tiles = (const int2*)ctx->b_tiles.p;
     const int *tcls = var ? (const int*)ctx->b_tilecls.p : nullptr;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
     // block-slot storage when the whole upper block triangle is assembled by this call and mirrored afterwards
     SlotOut SO{};
-    ctx->slot_used = false;
     if (slot_ok && slot_storage_ready(ctx)) {
         SO = slot_out(ctx);
-        ctx->slot_used = true;
+        ctx->run.slot_used = true;
         if (var && (rc = pnl2_zero_slot_tiles(ctx, SO))) return rc;
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-    ctx->pure_launched = false;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
     for (int q = 2; q <= 4; q++) {
         const int n = ctx->sl_n[q-1];
         if ((rc = pnl2_launch_uniform(ctx, kt, ctx->P, tiles+ctx->sl_off[q-1], tcls ? tcls+ctx->sl_off[q-1] : nullptr, n, q, A, ldA,
                                       (double*)ctx->b_D.p, SO))) return rc;
-        ctx->pure_launched = ctx->pure_launched || n > 0;
+        ctx->run.pure_launched = ctx->run.pure_launched || n > 0;
     }
-    if (ctx->pure_launched) HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    if (ctx->run.pure_launched) HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
     if ((rc = pnl2_launch_p2(ctx, kt, tiles+ctx->sl_off[0], tcls ? tcls+ctx->sl_off[0] : nullptr, ctx->sl_n[0], A, ldA, cell_begin, cell_end,
                              ctx->wl_cap_each, SO))) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_DONE], ctx->stream));
     // block-slot storage: A = A' + A'^T is formed now (it overwrites A); the work-list kernels then write both images
-    if (ctx->slot_used) {
+    if (ctx->run.slot_used) {
         if ((rc = pnl2_fold_mirror(ctx, SO, A, ldA))) return rc;
         HIPCHK(ctx, hipEventRecord(ctx->ev_fold, ctx->stream));
-        ctx->fold_event_set = true;
+        ctx->run.fold_event_set = true;
     }
-    const bool sym = ctx->symflush || ctx->slot_used;
+    const bool sym = ctx->run.symflush || ctx->run.slot_used;
     {
         ClassFork fork(ctx, ncls);
         if (ncls > pnl_context::NAUX && (int)ctx->cls_n_mixed.size() == ncls) fork.plan(ctx->cls_n_mixed);     // the work lists come from the mixed tiles
         for (int k = 0; k < ncls; k++) {
-            ctx->cur = k;
-            pnl_refresh_tables(ctx);
+            cls.select(k, 0);
             fork.use(k);
             const int4 *wl = (const int4*)ctx->b_wl.p+(size_t)k*ctx->wl_cap_each;
             const unsigned *wlc = (const unsigned*)ctx->b_wlcount.p+k;
             rc = with_kt(ctx->P.k.fast, [&](auto kt) {
                 return run_worklist<DIM, DPE, decltype(kt)::value>(ctx, wl, wlc, ctx->wl_cap_each, A, ldA, sym, k, ncls);
             });
-            if (rc) { ctx->cur = 0; return rc; }
+            if (rc) return rc;
         }
     }
-    ctx->cur = 0;
     return PNL_OK;
 }
 
-// the whole upper block triangle is assembled by this call and mirrored afterwards
-bool slot_eligible(const pnl_context *ctx, int cell_begin, int cell_end, int flags) {
+// the whole upper block triangle is assembled by this call (full_list: the tile list is that of pnl_assemble_dense) and mirrored afterwards
+bool slot_eligible(const pnl_context *ctx, bool full_list, int cell_begin, int cell_end, int flags) {
     // P2: every tile list (several order classes: multi-visit tiles accumulate); P1: one class, every tile visited by one kernel
     const bool elem = ctx->dpe == 6 || (ctx->dpe == 3 && ctx->cls.size() == 1 && !ctx->nonsym && ctx->use_pure && !pnl_tune("PNL_NO_SLOT_P1"));
-    return ctx->dim == 2 && elem && ctx->slot_full_list && ctx->slab_rows == 0 && cell_begin == 0 && cell_end == ctx->nc &&
+    return ctx->dim == 2 && elem && full_list && ctx->slab_rows == 0 && cell_begin == 0 && cell_end == ctx->nc &&
            !(flags & (PNL_FLAG_NO_MIRROR | PNL_FLAG_SYMMETRIC_FLUSH));
 }
 
@@ -556,8 +536,7 @@ template <int DIM, int DPE, int TILE>
 int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, int ntiles, int cell_begin, int cell_end, int flags) {
     int rc;
     const int ncls = (int)ctx->cls.size();
-    ctx->symflush = (flags & PNL_FLAG_SYMMETRIC_FLUSH) != 0;
-    for (int &k : ctx->kev_n) k = 0;
+    ctx->run.symflush = (flags & PNL_FLAG_SYMMETRIC_FLUSH) != 0;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->b_D.p, 0, sizeof(double)*(size_t)ctx->ncp*(DPE*(DPE+1)/2), ctx->stream));
     if (ctx->have_tile_order) HIPCHK(ctx, hipMemsetAsync(ctx->b_Dt.p, 0, sizeof(double)*(size_t)ctx->ncp*(DPE*(DPE+1)/2), ctx->stream));
@@ -565,13 +544,10 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
         // ticket counters of the uniform-tile launches (pnl_tile2.hip): one fill for all launches of this assembly
         if ((rc = ensure(ctx, ctx->b_unictr, sizeof(unsigned)*pnl_context::UNI_CTRS))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->b_unictr.p, 0, sizeof(unsigned)*pnl_context::UNI_CTRS, ctx->stream));
-        ctx->uni_ctr_next = 0; ctx->uni_ctr_fresh = pnl_context::UNI_CTRS;
+        ctx->run.uni_ctr_next = 0; ctx->run.uni_ctr_fresh = pnl_context::UNI_CTRS;
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    ctx->tiles_launched = ntiles > 0;
-    ctx->settled_run = 0;
-    ctx->fold_event_set = false;
-    ctx->stg_active = false;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
+    ctx->run.tiles_launched = ntiles > 0;
     // variable order, zero exterior: the distant (cell, facet) pairs of ALL classes run in one launch with per-class kernel /
     // order-formula tables; the tables go up now, ahead of the tile kernels, so that the launch needs nothing from the
     // caller's stream later than the fold
@@ -581,13 +557,12 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
         std::vector<DevKernel> &bk = ctx->bkcls_host;
         std::vector<DevFormula> &bf = ctx->bfcls_host;
         bk.resize(ncls); bf.resize(ncls);
+        ClassScope cls(ctx, 0);
         for (int k = 0; k < ncls; k++) {
-            ctx->cur = k;
-            pnl_refresh_tables(ctx);
+            cls.select(k, 0);
             bk[k] = ctx->P.bkn; bf[k] = ctx->P.bqo;
             bnd_all_fast = bnd_all_fast && ctx->P.bkn.fast;
         }
-        ctx->cur = 0;
         if ((rc = ensure(ctx, ctx->b_bkcls, sizeof(DevKernel)*ncls))) return rc;
         if ((rc = ensure(ctx, ctx->b_bfcls, sizeof(DevFormula)*ncls))) return rc;
         HIPCHK(ctx, hipMemcpyAsync(ctx->b_bkcls.p, bk.data(), sizeof(DevKernel)*ncls, hipMemcpyHostToDevice, ctx->stream));
@@ -598,23 +573,20 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
     // event (the order classes' streams after a fold); nullptr: everything on ctx->stream
     auto boundary_term = [&](hipEvent_t chain) -> int {
         int rcb;
+        ClassScope cls(ctx, 0);
         ClassFork fork(ctx, chain ? ncls : 1, chain);
         if (chain && ncls > pnl_context::NAUX && (int)ctx->cls_n_mixed.size() == ncls) fork.plan(ctx->cls_n_mixed);
         for (int k = 0; k < ncls; k++) {
-            ctx->cur = k;
-            pnl_refresh_tables(ctx);
-            if (!ctx->have_boundary || !ctx->C().have_kernel[1] || !ctx->C().have_form[1]) {
-                ctx->cur = 0;
+            cls.select(k, 0);
+            if (!ctx->have_boundary || !ctx->C().have_kernel[1] || !ctx->C().have_form[1])
                 return fail(ctx, PNL_ERR_STATE, "zero_exterior needs boundary facets, boundary kernel and order formula");
-            }
             if (chain) fork.use(k);
             if (bnd_one_pass && k == 0 &&
                 (rcb = launch_boundary<DIM, DPE, 0>(ctx, cell_begin, cell_end, 1, (const DevKernel*)ctx->b_bkcls.p, (const DevFormula*)ctx->b_bfcls.p,
-                                                    bnd_all_fast))) { ctx->cur = 0; return rcb; }
+                                                    bnd_all_fast))) return rcb;
             if (chain) fork.use(k);
-            if ((rcb = launch_boundary<DIM, DPE, 0>(ctx, cell_begin, cell_end, bnd_one_pass ? 2 : 3))) { ctx->cur = 0; return rcb; }
+            if ((rcb = launch_boundary<DIM, DPE, 0>(ctx, cell_begin, cell_end, bnd_one_pass ? 2 : 3))) return rcb;
         }
-        ctx->cur = 0;
         return PNL_OK;
     };
     // The boundary term only adds to the per-cell diagonal blocks (b_D, scattered into A at the very end) and never touches A, so
@@ -631,12 +603,9 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
     const int bnd_mode = !zero_exterior ? -1 : pnl_tune("PNL_BND_MODE") ? atoi(pnl_tune("PNL_BND_MODE")) : PNL_BND_MODE_DEFAULT;
     bool bnd_side = false;
     auto boundary_side = [&](hipEvent_t after) -> int {
-        hipStream_t const caller = ctx->stream;
         hipStream_t const side = ctx->aux[1];
         HIPCHK(ctx, hipStreamWaitEvent(side, after, 0));
-        ctx->stream = side;
-        const int rcb = boundary_term(nullptr);
-        ctx->stream = caller;
+        const int rcb = [&] { StreamScope on(ctx, side); return boundary_term(nullptr); }();
         if (rcb) return rcb;
         HIPCHK(ctx, hipEventRecord(ctx->ev_join[1], side));
         bnd_side = true;
@@ -656,98 +625,89 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
         if ((rc = ensure(ctx, ctx->b_wlcount, sizeof(unsigned)*PNL_WL_SLOTS))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned)*PNL_WL_SLOTS, ctx->stream));
         if ((rc = ensure_worklist(ctx, (double)ntiles*TILE*TILE, single ? ncls : 1))) return rc;
-        ctx->wl_slots = single ? ncls : ncls*norient;
+        ctx->run.wl_slots = single ? ncls : ncls*norient;
         if constexpr (DIM == 2 && DPE == 6) {
             // the block-slot storage needs every tile of the upper block triangle written by this call, then the fold + mirror pass
-            const bool slot_ok = slot_eligible(ctx, cell_begin, cell_end, flags);
-            if ((rc = launch_tiles_single<DIM, DPE>(ctx, A, ldA, ctx->tile_cell_filter ? cell_begin : 0, ctx->tile_cell_filter ? cell_end : ctx->nc, slot_ok)))
-                { ctx->cur = 0; ctx->orient = 0; return rc; }
+            const bool slot_ok = slot_eligible(ctx, ctx->run.full_tile_list, cell_begin, cell_end, flags);
+            if ((rc = launch_tiles_single<DIM, DPE>(ctx, A, ldA, ctx->run.tile_cell_filter ? cell_begin : 0, ctx->run.tile_cell_filter ? cell_end : ctx->nc, slot_ok)))
+                return rc;
         } else {
         // 2D P1, one order class: block-slot storage like the P2 path (plain stores instead of 47 GB of fp64 atomics at 48,769
         // DoFs, fold + mirror instead of zero fill + mirror)
         SlotOut SO{};
-        ctx->slot_used = false;
-        if (slot_eligible(ctx, cell_begin, cell_end, flags) && slot_storage_ready(ctx)) { SO = slot_out(ctx); ctx->slot_used = true; }
+        if (slot_eligible(ctx, ctx->run.full_tile_list, cell_begin, cell_end, flags) && slot_storage_ready(ctx)) { SO = slot_out(ctx); ctx->run.slot_used = true; }
+        ClassScope cls(ctx, 0);
         for (int ko = 0; ko < ncls*norient; ko++) {
             const int k = ko/norient;
-            ctx->cur = k; ctx->orient = ko%norient;
-            pnl_refresh_tables(ctx);
-            ctx->tile_off = ctx->cls_tile_off[k]; ctx->n_mixed = ctx->cls_n_mixed[k]; ctx->n_pure = ctx->cls_n_pure[k];
-            if (ctx->n_mixed+ctx->n_pure+ctx->cls_n_uni[1][k]+ctx->cls_n_uni[2][k] == 0) continue;
-            const int tb0 = ctx->tile_cell_filter ? cell_begin : 0, tb1 = ctx->tile_cell_filter ? cell_end : ctx->nc;
+            cls.select(k, ko%norient);
+            ctx->run.tile_off = ctx->cls_tile_off[k]; ctx->run.n_mixed = ctx->cls_n_mixed[k]; ctx->run.n_pure = ctx->cls_n_pure[k];
+            if (ctx->run.n_mixed+ctx->run.n_pure+ctx->cls_n_uni[1][k]+ctx->cls_n_uni[2][k] == 0) continue;
+            const int tb0 = ctx->run.tile_cell_filter ? cell_begin : 0, tb1 = ctx->run.tile_cell_filter ? cell_end : ctx->nc;
             // s = 1/2 in 2D (exponent -6/4) has its own instantiation: branch-free evaluations
             if (ctx->P.k.fast && ctx->P.k.qm == 6 && DPE == 3 && !pnl_tune("PNL_NO_KT2")) rc = launch_tiles<DIM, DPE, TILE, (DPE == 3 ? 2 : 1)>(ctx, ko, A, ldA, tb0, tb1, SO);
             else rc = with_kt(ctx->P.k.fast, [&](auto kt) { return launch_tiles<DIM, DPE, TILE, decltype(kt)::value>(ctx, ko, A, ldA, tb0, tb1, SO); });
-            if (rc) { ctx->cur = 0; ctx->orient = 0; return rc; }
+            if (rc) return rc;
         }
         }
     }
-    ctx->orient = 0;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    // mirror the cross part before the symmetric contributions are added on both sides
-    if (ntiles > 0 && ctx->slot_used) {
-        // folded and mirrored inside launch_tiles_single
-    } else if (!(flags & (PNL_FLAG_NO_MIRROR | PNL_FLAG_SYMMETRIC_FLUSH))) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_WORKLIST_DONE], ctx->stream));
+    // mirror the cross part before the symmetric contributions are added on both sides (block-slot storage: folded and mirrored behind the tiles)
+    if (!ctx->run.slot_used && !(flags & (PNL_FLAG_NO_MIRROR | PNL_FLAG_SYMMETRIC_FLUSH))) {
         const long long nb = (ctx->N+31)/32;
         hipLaunchKernelGGL(k_mirror, dim3((unsigned)(nb*(nb+1)/2)), dim3(PNL_NTHREADS), 0, ctx->stream, A, (long long)ldA, ctx->N);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_MIRROR_DONE], ctx->stream));
     // one order class behind a fold pass: the touching pairs (side stream 0) and the boundary term (side stream 1) start at the
     // fold, next to the work-list kernels on the caller's stream -- everything after the fold only adds with atomics.  The
     // phase timers then show what is left of them after the work list ("singular"), the boundary phase reads 0
     hipStream_t const main_stream = ctx->stream;
     // without a fold pass (row slabs of a rank, 1D, P0) the same holds from here on: the touching pairs and the boundary term add
     // with atomics and run side by side
-    bool fold_like = ctx->fold_event_set;
+    bool fold_like = ctx->run.fold_event_set;
     if (!fold_like && ncls*norient == 1 && zero_exterior && !pnl_tune("PNL_NO_OVERLAP")) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_fold, ctx->stream));
         fold_like = true;
     }
     const bool overlap = fold_like && ncls*norient == 1 && !pnl_tune("PNL_NO_OVERLAP");
-    struct StreamGuard { pnl_context *c; hipStream_t s; ~StreamGuard() { c->stream = s; } } stream_guard{ctx, main_stream};
-    if (overlap) { HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[0], ctx->ev_fold, 0)); ctx->stream = ctx->aux[0]; }
     // several classes behind a fold pass: the side streams of the touching pairs and of the boundary term start at the fold
     // too, class k follows the work list of class k on its stream, nothing waits for the other classes
-    hipEvent_t const chain = (ctx->fold_event_set && !overlap && !pnl_tune("PNL_NO_OVERLAP")) ? ctx->ev_fold : nullptr;
+    hipEvent_t const chain = (ctx->run.fold_event_set && !overlap && !pnl_tune("PNL_NO_OVERLAP")) ? ctx->ev_fold : nullptr;
+    if (overlap) HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[0], ctx->ev_fold, 0));
     {
+        StreamScope on(ctx, overlap ? ctx->aux[0] : main_stream);
+        ClassScope cls(ctx, 0);
         ClassFork fork(ctx, ncls*norient, chain);
         if (norient == 1 && ncls > pnl_context::NAUX && (int)ctx->cls_n_mixed.size() == ncls) fork.plan(ctx->cls_n_mixed);    // as the work lists
         for (int ko = 0; ko < ncls*norient; ko++) {
-            ctx->cur = ko/norient; ctx->orient = ko%norient;
-            pnl_refresh_tables(ctx);
+            cls.select(ko/norient, ko%norient);
             fork.use(ko);
             rc = with_kt(ctx->P.k.fast, [&](auto kt) { return launch_singular<DIM, DPE, decltype(kt)::value>(ctx, A, ldA, cell_begin, cell_end); });
-            if (rc) { ctx->cur = 0; ctx->orient = 0; return rc; }
+            if (rc) return rc;
         }
     }
-    ctx->orient = 0;
-    if (overlap) {
-        HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
-        ctx->stream = main_stream;
-    } else HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    if (overlap) HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
+    else HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SINGULAR_DONE], ctx->stream));
     // 4: as 3, but with a staged fold behind the tile kernels of stage 0, next to the uniform tiles of the later stages (which leave
     // it a workgroup slot per CU)
-    if ((bnd_mode == 3 || bnd_mode == 4) && ctx->fold_event_set)              // next to the fold pass (ev[6]: tile kernels done)
-        rc = boundary_side(bnd_mode == 4 && ctx->stg_active && !pnl_tune("PNL_NO_OVERLAP") ? ctx->ev_stage[0] : ctx->ev[6]);
+    if ((bnd_mode == 3 || bnd_mode == 4) && ctx->run.fold_event_set)              // next to the fold pass
+        rc = boundary_side(bnd_mode == 4 && ctx->run.stg_active && !pnl_tune("PNL_NO_OVERLAP") ? ctx->ev_stage[0] : ctx->ev[EV_TILES_DONE]);
     else if (bnd_mode == 1 || ((bnd_mode == 0 || bnd_mode >= 3) && overlap)) rc = boundary_side(bnd_mode == 1 ? ctx->ev_bnd : ctx->ev_fold);
     else if (bnd_mode == 0 || bnd_mode >= 3) rc = boundary_term(chain);
     if (rc) return rc;
-    ctx->cur = 0;
     if (overlap) {
         HIPCHK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join[0], 0));
-        ctx->stream = main_stream;
-        HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SINGULAR_DONE], ctx->stream));
     }
     if (bnd_side) HIPCHK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join[1], 0));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_BOUNDARY_DONE], ctx->stream));
     if (ctx->slab_rows == 0) {
         scatter_diag<DPE>(ctx, ctx->P, (const double*)ctx->b_D.p, A, ldA);
         if (ctx->have_tile_order) scatter_diag<DPE>(ctx, tile_problem(ctx), (const double*)ctx->b_Dt.p, A, ldA);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    ctx->ev_valid = true;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_END], ctx->stream));
+    ctx->run.ev_valid = true;
     return PNL_OK;
 }
 
@@ -779,9 +739,8 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
     if (lds > 160*1024) return fail(ctx, PNL_ERR_UNSUPPORTED, "cluster chunk with %d DoFs: LDS sub-block of %zu bytes exceeds 160 KiB", pl->chunk_stride, lds);
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(CT.D, 0, sizeof(double)*(size_t)std::max(pl->num_dslots, 1)*ND, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-    ctx->pure_launched = false;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
     // work list of the orders the tiles do not integrate themselves
     {
         const double pairs = (double)pl->ntiles*TILE*TILE;
@@ -794,7 +753,7 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
         if ((rc = ensure(ctx, ctx->b_wlpair, (size_t)ctx->wl_cap*sizeof(int)))) return rc;
         if ((rc = ensure(ctx, ctx->b_wlcount, sizeof(unsigned)*PNL_WL_SLOTS))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));
-        ctx->wl_slots = 1; ctx->wl_cap_each = ctx->wl_cap;
+        ctx->run.wl_slots = 1; ctx->wl_cap_each = ctx->wl_cap;
         if ((rc = ensure(ctx, ctx->b_tilectr, sizeof(unsigned)))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
         CT.wl_ds = (int2*)ctx->b_wlds.p; CT.wl_pair = (int*)ctx->b_wlpair.p;
@@ -810,13 +769,13 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
                            pl->ntiles, CT, (unsigned*)ctx->b_tilectr.p, SlotOut{}, (const unsigned short*)nullptr);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_DONE], ctx->stream));
     // behind the tile kernel everything only adds (sparse data, diagonal-block buffer) with atomics: the touching pairs run on side
     // stream 0 and the cluster-local boundary term on side stream 1 next to the work-list kernels; joined before the diagonal
     // blocks are scattered.  The phase timers then show what is left of them after the work list
     hipStream_t const main_stream = ctx->stream;
     const bool overlap = !pnl_tune("PNL_NO_OVERLAP");
-    struct StreamGuard { pnl_context *c; hipStream_t s; ~StreamGuard() { c->stream = s; } } stream_guard{ctx, main_stream};
+    StreamScope side(ctx, main_stream);
     if (overlap) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_fold, main_stream));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[0], ctx->ev_fold, 0));
@@ -832,10 +791,10 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
         if ((rc = worklist_eval<DIM, DPE, KT, false>(ctx, "PNL_WL_CL_KB", 18, (const int4*)ctx->b_wlsorted.p, B, nullptr, 0, nullptr, SparseOut{},
                                                      CT, PNL_WL_BINS-1, PNL_WL_LANE_MAXPTS+1, true, 0))) return rc;
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_WORKLIST_DONE], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_MIRROR_DONE], ctx->stream));
     // touching element pairs
-    if (overlap) ctx->stream = ctx->aux[0];
+    if (overlap) side.to(ctx->aux[0]);
     for (int s = 0; s < DIM+1; s++) {
         const int np = pl->n_sing[s];
         if (!np) continue;
@@ -850,8 +809,8 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
     }
     if (overlap) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
-        ctx->stream = ctx->aux[1];
-    } else HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+        side.to(ctx->aux[1]);
+    } else HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SINGULAR_DONE], ctx->stream));
     // cluster-local Gauss-theorem term into the diagonal-block buffer
     if (cluster_boundary && pl->num_dslots > 0 && pl->nfacets > 0) {
         if (!ctx->C().have_kernel[1] || !ctx->C().have_form[1]) return fail(ctx, PNL_ERR_STATE, "boundary kernel and order formula must be set");
@@ -900,21 +859,21 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
     }
     if (overlap) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_join[1], ctx->aux[1]));
-        ctx->stream = main_stream;
+        side.to(main_stream);
         HIPCHK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join[0], 0));
         HIPCHK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join[1], 0));
-        HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SINGULAR_DONE], ctx->stream));
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_BOUNDARY_DONE], ctx->stream));
     if (pl->num_dslots > 0) {
         const long long nt = (long long)pl->num_dslots*DPE*DPE;
         hipLaunchKernelGGL((k_cluster_scatter_diag<DPE>), dim3((unsigned)((nt+PNL_NTHREADS-1)/PNL_NTHREADS)), dim3(PNL_NTHREADS), 0,
                            ctx->stream, ctx->P, CT, d_cell, d_pair, pl->num_dslots);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    ctx->ev_valid = true;
-    ctx->tiles_launched = true;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_END], ctx->stream));
+    ctx->run.ev_valid = true;
+    ctx->run.tiles_launched = true;
     return PNL_OK;
 }
 
@@ -1093,16 +1052,15 @@ int pnl_assemble_dense(pnl_context *ctx, double *A, int64_t ldA, int zero_exteri
     if (!A || ldA < (ctx->slab_rows ? ctx->slab_cols : ctx->N)) return fail(ctx, PNL_ERR_INVALID, "bad output matrix (ldA=%lld, num_dofs=%d)", (long long)ldA, ctx->N);
     if (cell_begin < 0 || cell_end > ctx->nc || cell_begin > cell_end) return fail(ctx, PNL_ERR_INVALID, "bad cell range");
     if ((rc = slab_prepare(ctx, flags, cell_begin, cell_end))) return rc;
+    pnl_begin_assembly(ctx);
+    ctx->run.full_tile_list = true;
     std::vector<int2> tiles;
     if (cell_end > cell_begin) pnl_make_tiles(ctx, tiles, cell_begin, cell_end);
     if ((rc = pnl_upload_tiles(ctx, tiles, cell_begin, cell_end))) return rc;
     // pairs visited by the reference loop: c1 in [begin,end), c2 in [c1, nc)
-    unsigned long long visited = 0;
     for (long long c = cell_begin; c < cell_end; c++)
-        if (ctx->real_from[c] != ctx->real_from[c+1]) visited += (unsigned long long)ctx->real_from[c];      // zero-volume padding cells do not count
-    ctx->visited_pairs = visited; ctx->visited_is_assembled = false;
+        if (ctx->real_from[c] != ctx->real_from[c+1]) ctx->run.visited_pairs += (unsigned long long)ctx->real_from[c];      // zero-volume padding cells do not count
     if (pnl_tune("PNL_FORCE_SYMFLUSH")) flags |= PNL_FLAG_SYMMETRIC_FLUSH;     // debug: both sides written by the flush, no mirror pass
-    ctx->slot_full_list = true;
     return dispatch(ctx, A, ldA, zero_exterior, (int)tiles.size(), cell_begin, cell_end, flags);
 }
 
@@ -1111,11 +1069,7 @@ int pnl_dense_overwrites(pnl_context *ctx, int cell_begin, int cell_end, int fla
     int rc;
     if ((rc = pnl_assembly_ready(ctx))) return rc;
     if (pnl_tune("PNL_FORCE_SYMFLUSH")) return 0;
-    const bool full = ctx->slot_full_list;
-    ctx->slot_full_list = true;                          // what pnl_assemble_dense sets
-    const bool ok = slot_eligible(ctx, cell_begin, cell_end, flags) && slot_storage_ready(ctx);
-    ctx->slot_full_list = full;
-    return ok ? 1 : 0;
+    return slot_eligible(ctx, true, cell_begin, cell_end, flags) && slot_storage_ready(ctx) ? 1 : 0;      // true: what pnl_assemble_dense sets
 }
 
 int pnl_assemble_dense_tiles(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, int ntiles, const int32_t *tiles_host,
@@ -1132,13 +1086,10 @@ int pnl_assemble_dense_tiles(pnl_context *ctx, double *A, int64_t ldA, int zero_
         tiles[i] = make_int2(tiles_host[2*i], tiles_host[2*i+1]);
         if (tiles[i].x < 0 || tiles[i].y >= ctx->nblocks || tiles[i].x > tiles[i].y) return fail(ctx, PNL_ERR_INVALID, "bad tile %d", i);
     }
-    ctx->tile_cell_filter = false;
-    ctx->slot_full_list = false;
-    if ((rc = pnl_upload_tiles(ctx, tiles, cell_begin, cell_end))) { ctx->tile_cell_filter = true; return rc; }
-    ctx->visited_pairs = 0; ctx->visited_is_assembled = false;
-    rc = dispatch(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
-    ctx->tile_cell_filter = true;
-    return rc;
+    pnl_begin_assembly(ctx);
+    ctx->run.tile_cell_filter = false;          // the caller's tiles, whole
+    if ((rc = pnl_upload_tiles(ctx, tiles, cell_begin, cell_end))) return rc;
+    return dispatch(ctx, A, ldA, zero_exterior, ntiles, cell_begin, cell_end, flags);
 }
 
 int pnl_assemble_boundary_masked(pnl_context *ctx, int ni, const int32_t *cells, const int32_t *facets, const uint32_t *masks,
@@ -1265,7 +1216,7 @@ int pnl_assemble_clusters_tiled(pnl_context *ctx, const pnl_cluster_plan *pl, in
 #undef UP
     if ((rc = ensure(ctx, ctx->b_cpD, sizeof(double)*(size_t)std::max(pl->num_dslots, 1)*(dpe*(dpe+1)/2)))) return rc;
     CT.D = (double*)ctx->b_cpD.p;
-    ctx->visited_pairs = 0; ctx->visited_is_assembled = false;
+    pnl_begin_assembly(ctx);
     return with_shape(ctx, [&](auto D, auto E) {
         constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;
         return with_kt(ctx->P.k.fast, [&](auto kt) {

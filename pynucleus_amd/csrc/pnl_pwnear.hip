@@ -47,7 +47,7 @@ int reserve_worklist(pnl_context *ctx, size_t want) {
     if ((rc = ensure(ctx, ctx->b_wlcount, sizeof(unsigned)*PNL_WL_SLOTS))) return rc;
     if ((rc = ensure(ctx, ctx->b_wlaux, sizeof(unsigned)*(4*(PNL_WL_BINS+1))))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));
-    ctx->wl_slots = 1; ctx->wl_cap_each = ctx->wl_cap;
+    ctx->run.wl_slots = 1; ctx->wl_cap_each = ctx->wl_cap;
     return PNL_OK;
 }
 
@@ -66,8 +66,8 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
     const PwDev &W = ctx->pw;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->b_D.p, 0, sizeof(double)*(size_t)ctx->ncp*ND, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    ctx->tiles_launched = true; ctx->pure_launched = false;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
+    ctx->run.tiles_launched = true;
     const int nbk = (ctx->nc+63)/64;
     {
         // work list: only the pairs whose rule has more than 16 points arrive there when the tiles evaluate the others
@@ -125,9 +125,9 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
         hipLaunchKernelGGL(tfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, P, W, (const int2*)ctx->b_tiles.p+mixed.size(),
                            (int)uniform.size(), A, (long long)ldA, (double*)ctx->b_D.p, acc_stride);
         HIPCHK(ctx, hipGetLastError());
-        ctx->pure_launched = true;
+        ctx->run.pure_launched = true;
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
     // the other tiles: classification, in-tile evaluation of the rules with at most 16 points (LDS sub-blocks), work list for the rest
     const bool in_tile = P1 && ctx->tile == 64 && !pnl_tune("PNL_PW_NOMIXED");
     if constexpr (P1el) if (!mixed.empty() && in_tile) {
@@ -148,7 +148,7 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
         hipLaunchKernelGGL((k_pw_classify<DIM, DPE>), dim3((unsigned)mixed.size()), dim3(PNL_NTHREADS), 0, ctx->stream, P, W,
                            (const int2*)ctx->b_tiles.p, (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, ctx->wl_cap, cell_begin, cell_end);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_DONE], ctx->stream));
     {
         WlBins B;
         if ((rc = pnl_wl_sort(ctx, (const int4*)ctx->b_wl.p, (const unsigned*)ctx->b_wlcount.p, ctx->wl_cap, (unsigned*)ctx->b_wlaux.p,
@@ -167,8 +167,8 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
                            (const unsigned*)B.offs, A, (long long)ldA, (double*)ctx->b_D.p, tab_max, lane_kernel ? PNL_PW_LANE_MAXPTS+1 : 0, PwNear{});
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_WORKLIST_DONE], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_MIRROR_DONE], ctx->stream));
     if (npairs > 0) {
         const unsigned grid = (unsigned)((2ll*npairs*64+PNL_NTHREADS-1)/PNL_NTHREADS);
         const int4 *pp = (const int4*)ctx->b_pw_pairs.p;
@@ -178,7 +178,7 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
             hipLaunchKernelGGL((k_pw_singular<DIM, DPE, (DIM == 2 ? 2 : 1)>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, pp, npairs, A, (long long)ldA, cell_begin, cell_end, PwNear{}, (const int*)nullptr);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SINGULAR_DONE], ctx->stream));
     if (zero_exterior && cell_end > cell_begin) {
         const int ncell = cell_end-cell_begin, gx = (ncell+PNL_NTHREADS-1)/PNL_NTHREADS;
         int per = 16;
@@ -194,11 +194,11 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
         }
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_BOUNDARY_DONE], ctx->stream));
     pnl_scatter_diag(ctx, P, (const double*)ctx->b_D.p, A, ldA);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    ctx->ev_valid = true;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_END], ctx->stream));
+    ctx->run.ev_valid = true;
     return PNL_OK;
 }
 
@@ -218,12 +218,11 @@ int pairs_near_impl(pnl_context *ctx, int np, int nt, int nd, const PwNear &NR) 
     const DevProblem &P = ctx->P;
     const PwDev &W = ctx->pw;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    ctx->tiles_launched = false; ctx->pure_launched = false;
-    for (int e : {7, 6}) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
+    for (int e : {EV_TILES_UNIFORM_DONE, EV_TILES_DONE}) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
     if ((rc = ensure(ctx, ctx->b_wlcount, sizeof(unsigned)*PNL_WL_SLOTS))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));
-    ctx->wl_slots = 1;
+    ctx->run.wl_slots = 1;
     if (nd > 0) {
         // classification -> work list sorted by order -> 16 lanes per pair (k_pw_distant, this orientation alone)
         const size_t want = std::max<size_t>((size_t)nd, 1024);
@@ -243,8 +242,8 @@ int pairs_near_impl(pnl_context *ctx, int np, int nt, int nd, const PwNear &NR) 
                            (double*)nullptr, 0ll, (double*)nullptr, tab_max, 0, NR);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_WORKLIST_DONE], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_MIRROR_DONE], ctx->stream));
     if (nt > 0) {
         const unsigned grid = (unsigned)(((long long)nt*64+PNL_NTHREADS-1)/PNL_NTHREADS);
         const int4 *pp = (const int4*)ctx->b_pw_pairs.p;
@@ -255,9 +254,9 @@ int pairs_near_impl(pnl_context *ctx, int np, int nt, int nd, const PwNear &NR) 
             hipLaunchKernelGGL((k_pw_singular<DIM, DPE, (DIM == 2 ? 2 : 1), true>), dim3(grid), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, pp, nt, (double*)nullptr, 0ll, 0, 0, NR, item);
         HIPCHK(ctx, hipGetLastError());
     }
-    for (int e : {3, 4, 5}) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
-    ctx->ev_valid = true;
-    ctx->visited_pairs = (unsigned long long)np; ctx->visited_is_assembled = false;
+    for (int e : {EV_SINGULAR_DONE, EV_BOUNDARY_DONE, EV_END}) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
+    ctx->run.ev_valid = true;
+    ctx->run.visited_pairs = (unsigned long long)np;
     return PNL_OK;
 }
 
@@ -304,9 +303,8 @@ int pnl_assemble_dense_pointwise(pnl_context *ctx, double *A, int64_t ldA, int z
     }
     if ((rc = upload(ctx, ctx->b_pw_pairs, pairs, (size_t)4*npairs))) return rc;
     if ((rc = upload(ctx, ctx->b_pw_bpairs, bpairs, (size_t)4*nbpairs))) return rc;
-    unsigned long long visited = 0;
-    for (long long c = cell_begin; c < cell_end; c++) visited += (unsigned long long)(ctx->nc-c);
-    ctx->visited_pairs = visited; ctx->visited_is_assembled = false;
+    pnl_begin_assembly(ctx);
+    for (long long c = cell_begin; c < cell_end; c++) ctx->run.visited_pairs += (unsigned long long)(ctx->nc-c);
     if (ctx->dim == 2)
         return ctx->dpe == 6 ? pointwise_impl<2, 6>(ctx, A, ldA, zero_exterior, cell_begin, cell_end, npairs, nbpairs)
                              : pointwise_impl<2, 3>(ctx, A, ldA, zero_exterior, cell_begin, cell_end, npairs, nbpairs);
@@ -347,6 +345,7 @@ int pnl_assemble_pairs_masked_pointwise(pnl_context *ctx, int np, const int32_t 
     PwNear NR;
     if ((rc = near_pattern(ctx, data, NR))) return rc;
     const int nt = (int)titems.size(), nd = (int)distant.size();
+    pnl_begin_assembly(ctx);
     if (ctx->dim == 2) return ctx->dpe == 6 ? pairs_near_impl<2, 6>(ctx, np, nt, nd, NR) : pairs_near_impl<2, 3>(ctx, np, nt, nd, NR);
     return ctx->dpe == 3 ? pairs_near_impl<1, 3>(ctx, np, nt, nd, NR) : pairs_near_impl<1, 2>(ctx, np, nt, nd, NR);
 }

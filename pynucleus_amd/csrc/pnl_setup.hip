@@ -817,8 +817,8 @@ int pnl_set_stream(pnl_context *ctx, void *hip_stream) {
 static int check_overflow(pnl_context *ctx) {
     if (ctx->b_wlcount.p && ctx->wl_cap_each > 0) {
         unsigned wl[PNL_WL_SLOTS];
-        const int n = std::max(1, std::min(ctx->wl_slots, PNL_WL_SLOTS));
-        HIPCHK(ctx, hipMemcpy(wl, ctx->b_wlcount.p, sizeof(unsigned)*n, hipMemcpyDeviceToHost));
+        const int n = std::min(ctx->run.wl_slots, PNL_WL_SLOTS);      // the slots in use; the copy takes one word at least, as it always has
+        HIPCHK(ctx, hipMemcpy(wl, ctx->b_wlcount.p, sizeof(unsigned)*std::max(1, n), hipMemcpyDeviceToHost));
         for (int i = 0; i < n; i++)
             if (wl[i] > ctx->wl_cap_each)
                 return fail(ctx, PNL_ERR_STATE, "work list overflow (pass %d): %u entries needed, capacity %u; the assembled operator is "
@@ -1163,7 +1163,7 @@ static bool tiles_resident(const pnl_context *ctx, const std::vector<int2> &tile
     const std::vector<pnl_order_formula> &forms = R.forms;
     return tiles.size() == ctx->tiles_cached.size() && ctx->b_tiles.p && ctx->tiles_cb == R.cell_begin && ctx->tiles_ce == R.cell_end &&
         forms.size() == ctx->tiles_forms.size() && std::memcmp(forms.data(), ctx->tiles_forms.data(), sizeof(pnl_order_formula)*R.ncls) == 0 &&
-        ctx->tiles_filter == ctx->tile_cell_filter && ctx->stg_want == fold_stages_wanted() && ctx->settled_want == settled_wanted() &&
+        ctx->tiles_filter == ctx->run.tile_cell_filter && ctx->stg_want == fold_stages_wanted() && ctx->settled_want == settled_wanted() &&
         (tiles.empty() || std::memcmp(tiles.data(), ctx->tiles_cached.data(), tiles.size()*sizeof(int2)) == 0);
 }
 
@@ -1482,7 +1482,7 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
     for (int k = 0; k < ncls; k++) R.forms[k] = ctx->cls[k]->form[0];
     if (tiles_resident(ctx, tiles, R)) return PNL_OK;
     const int T = R.T = ctx->tile;
-    R.filter = ctx->tile_cell_filter;
+    R.filter = ctx->run.tile_cell_filter;
     // uniform tiles: order 2 through k_tile_pure (P1 in 1D and 2D), orders 2-4 through k_tile_uniform (2D: P1 orders 3 and 4, P2)
     R.p1 = T == 64 && (ctx->dpe == 3 || ctx->dpe == 2); R.p2 = ctx->dim == 2 && ctx->dpe == 6;
     R.allow = ctx->use_pure && (R.p1 || R.p2) && ctx->qmax >= 2 && !ctx->nonsym;
@@ -1552,9 +1552,8 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
         ctx->code_builds++;
     }
     ctx->settled_want = settled_wanted();
-    ctx->tile_off = 0; ctx->n_mixed = ctx->cls_n_mixed[0]; ctx->n_pure = ctx->cls_n_pure[0];
     ctx->tiles_cached = tiles; ctx->tiles_cb = cell_begin; ctx->tiles_ce = cell_end; ctx->tiles_forms = R.forms;
-    ctx->tiles_filter = ctx->tile_cell_filter;
+    ctx->tiles_filter = ctx->run.tile_cell_filter;
     ctx->stg_want = stages_wanted;
     return PNL_OK;
 }
@@ -1712,17 +1711,17 @@ int pnl_get_counters(pnl_context *ctx, int64_t *out, int n) {
     unsigned long long tmp[PNL_NCOUNTERS];
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipMemcpy(tmp, ctx->b_counters.p, sizeof(tmp), hipMemcpyDeviceToHost));
-    tmp[0] = ctx->visited_is_assembled ? tmp[1] : ctx->visited_pairs;
+    tmp[0] = ctx->run.visited_is_assembled ? tmp[1] : ctx->run.visited_pairs;
     for (int i = 0; i < n && i < PNL_NCOUNTERS; i++) out[i] = (int64_t)tmp[i];
-    if (n > PNL_C_SETTLED_TILES) out[PNL_C_SETTLED_TILES] = ctx->settled_run;
+    if (n > PNL_C_SETTLED_TILES) out[PNL_C_SETTLED_TILES] = ctx->run.settled_run;
     if (n > PNL_C_CODE_BUILDS) out[PNL_C_CODE_BUILDS] = ctx->code_builds;
     if (n > PNL_C_WORKLIST_LENGTH) {
         // entries the tile kernels handed to the work lists, over the passes of the assembly (the fill counters check_overflow reads)
         unsigned wl[PNL_WL_SLOTS];
-        const int ns = std::max(1, std::min(ctx->wl_slots, PNL_WL_SLOTS));
+        const int ns = std::min(ctx->run.wl_slots, PNL_WL_SLOTS);
         out[PNL_C_WORKLIST_LENGTH] = 0;
         if (ctx->b_wlcount.p && ctx->wl_cap_each > 0) {
-            HIPCHK(ctx, hipMemcpy(wl, ctx->b_wlcount.p, sizeof(unsigned)*ns, hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(wl, ctx->b_wlcount.p, sizeof(unsigned)*std::max(1, ns), hipMemcpyDeviceToHost));
             for (int i = 0; i < ns; i++) out[PNL_C_WORKLIST_LENGTH] += wl[i];
         }
     }
@@ -1731,23 +1730,23 @@ int pnl_get_counters(pnl_context *ctx, int64_t *out, int n) {
 
 int pnl_get_phase_ms(pnl_context *ctx, float *out, int n) {
     if (!ctx || !out || n <= 0) return PNL_ERR_INVALID;
-    if (!ctx->ev_valid) return fail(ctx, PNL_ERR_STATE, "nothing assembled yet");
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev[5]));
+    if (!ctx->run.ev_valid) return fail(ctx, PNL_ERR_STATE, "nothing assembled yet");
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev[EV_END]));
     float t[7] = {0, 0, 0, 0, 0, 0, 0}, tmp;
-    if (ctx->tiles_launched) {
-        HIPCHK(ctx, hipEventElapsedTime(&t[0], ctx->ev[0], ctx->ev[6]));  // tile kernels (uniform + general; last class)
-        HIPCHK(ctx, hipEventElapsedTime(&t[1], ctx->ev[6], ctx->ev[1]));  // work-list kernels
-        if (ctx->pure_launched && ctx->cls.size() == 1) {
-            HIPCHK(ctx, hipEventElapsedTime(&t[6], ctx->ev[0], ctx->ev[7]));   // uniform-tile kernel alone
+    if (ctx->run.tiles_launched) {
+        HIPCHK(ctx, hipEventElapsedTime(&t[0], ctx->ev[EV_START], ctx->ev[EV_TILES_DONE]));           // tile kernels (uniform + general; last class)
+        HIPCHK(ctx, hipEventElapsedTime(&t[1], ctx->ev[EV_TILES_DONE], ctx->ev[EV_WORKLIST_DONE]));   // work-list kernels
+        if (ctx->run.pure_launched && ctx->cls.size() == 1) {
+            HIPCHK(ctx, hipEventElapsedTime(&t[6], ctx->ev[EV_START], ctx->ev[EV_TILES_UNIFORM_DONE]));   // uniform-tile kernel alone
             t[0] -= t[6];
         }
     }
-    HIPCHK(ctx, hipEventElapsedTime(&tmp, ctx->ev[1], ctx->ev[2]));       // mirror
-    HIPCHK(ctx, hipEventElapsedTime(&t[2], ctx->ev[2], ctx->ev[3]));      // singular
-    HIPCHK(ctx, hipEventElapsedTime(&t[3], ctx->ev[3], ctx->ev[4]));      // boundary
-    HIPCHK(ctx, hipEventElapsedTime(&t[4], ctx->ev[4], ctx->ev[5]));      // diagonal scatter
+    HIPCHK(ctx, hipEventElapsedTime(&tmp, ctx->ev[EV_WORKLIST_DONE], ctx->ev[EV_MIRROR_DONE]));       // mirror
+    HIPCHK(ctx, hipEventElapsedTime(&t[2], ctx->ev[EV_MIRROR_DONE], ctx->ev[EV_SINGULAR_DONE]));      // singular
+    HIPCHK(ctx, hipEventElapsedTime(&t[3], ctx->ev[EV_SINGULAR_DONE], ctx->ev[EV_BOUNDARY_DONE]));      // boundary
+    HIPCHK(ctx, hipEventElapsedTime(&t[4], ctx->ev[EV_BOUNDARY_DONE], ctx->ev[EV_END]));      // diagonal scatter
     t[4] += tmp;
-    HIPCHK(ctx, hipEventElapsedTime(&t[5], ctx->ev[0], ctx->ev[5]));
+    HIPCHK(ctx, hipEventElapsedTime(&t[5], ctx->ev[EV_START], ctx->ev[EV_END]));
     for (int i = 0; i < n && i < 7; i++) out[i] = t[i];
     return PNL_OK;
 }
@@ -1805,11 +1804,11 @@ int pnl_get_fold_plan(pnl_context *ctx, int32_t *images, int64_t nimages, int8_t
 
 int pnl_get_kernel_ms(pnl_context *ctx, float *out, int n) {
     if (!ctx || !out || n <= 0) return PNL_ERR_INVALID;
-    if (!ctx->ev_valid) return fail(ctx, PNL_ERR_STATE, "nothing assembled yet");
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev[5]));
+    if (!ctx->run.ev_valid) return fail(ctx, PNL_ERR_STATE, "nothing assembled yet");
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev[EV_END]));
     for (int s = 0; s < n && s < PNL_NUM_KERNEL_SLOTS; s++) {
         out[s] = 0.f;
-        for (int k = 0; k < ctx->kev_n[s]; k++) {
+        for (int k = 0; k < ctx->run.kev_n[s]; k++) {
             float t = 0.f;
             HIPCHK(ctx, hipEventElapsedTime(&t, ctx->kev[s][2*k], ctx->kev[s][2*k+1]));
             out[s] += t;

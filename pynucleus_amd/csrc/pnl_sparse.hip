@@ -35,10 +35,10 @@ void scatter_diag_sparse(pnl_context *ctx, const double *D, const SparseOut &S) 
                        ctx->P, D, ctx->nc, S);
 }
 
-// end of an assembly path that skips its later phases: their events, so that the phase timers read zero
-int finish_events(pnl_context *ctx, int from) {
-    for (int e = from; e < 8; e++) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
-    ctx->ev_valid = true; ctx->tiles_launched = true;
+// end of an assembly path that skips its later phases: every event but EV_START, so that the phase timers read zero
+int finish_events(pnl_context *ctx) {
+    for (int e = EV_START+1; e < EV_COUNT; e++) HIPCHK(ctx, hipEventRecord(ctx->ev[e], ctx->stream));
+    ctx->run.ev_valid = true; ctx->run.tiles_launched = true;
     return PNL_OK;
 }
 
@@ -55,7 +55,7 @@ int pairs_masked_impl(pnl_context *ctx, int np, const SparseOut &S, bool classif
     const unsigned unp = (unsigned)np;
     HIPCHK(ctx, hipMemcpyAsync(count, &unp, sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // unp lives on this stack frame
-    if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
     if (classify)
         hipLaunchKernelGGL((k_mp_classify<DIM, DPE>), dim3((np+PNL_NTHREADS-1)/PNL_NTHREADS), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
                            S.pairs, np, wl);
@@ -63,7 +63,7 @@ int pairs_masked_impl(pnl_context *ctx, int np, const SparseOut &S, bool classif
     if ((rc = pnl_wl_sort(ctx, wl, count, unp, (unsigned*)ctx->b_mp_aux.p, sorted, B))) return rc;
     hipLaunchKernelGGL(k_mp_stats, dim3(1), dim3(PNL_WL_BINS), 0, ctx->stream, ctx->P, (const unsigned*)B.hist);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_DONE], ctx->stream));
     {
         // no masks (getSparse): diagonal blocks through the per-cell buffer, one scatter per cell at the end
         constexpr int ND = DPE*(DPE+1)/2;
@@ -76,8 +76,8 @@ int pairs_masked_impl(pnl_context *ctx, int np, const SparseOut &S, bool classif
         if (Dbuf) scatter_diag_sparse<DPE>(ctx, Dbuf, S);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_WORKLIST_DONE], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_MIRROR_DONE], ctx->stream));
     // touching pairs: bins 121 (common vertex), 122 (common edge / identical in 1D), 123 (identical in 2D)
     unsigned hh[PNL_WL_BINS+1];
     HIPCHK(ctx, hipMemcpyAsync(hh, B.hist, sizeof(hh), hipMemcpyDeviceToHost, ctx->stream));
@@ -90,11 +90,11 @@ int pairs_masked_impl(pnl_context *ctx, int np, const SparseOut &S, bool classif
                 return launch_singular_pairs<DIM, DPE, decltype(slot)::value, KT, true>(ctx, INT_MAX, nullptr, 0, nullptr, 0, 0, 0, S, sorted, B.offs,
                                                                                         ClusterTiles{});
             }))) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    ctx->ev_valid = true;
-    ctx->tiles_launched = true;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SINGULAR_DONE], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_BOUNDARY_DONE], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_END], ctx->stream));
+    ctx->run.ev_valid = true;
+    ctx->run.tiles_launched = true;
     return PNL_OK;
 }
 
@@ -122,7 +122,7 @@ int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
     if ((rc = ensure(ctx, ctx->b_mp_pairs, cap*sizeof(int2)))) return rc;
     if ((rc = ensure(ctx, ctx->b_mp_wl, cap*sizeof(int4)))) return rc;
     if ((rc = ensure(ctx, ctx->b_wlcount, sizeof(unsigned)*PNL_WL_SLOTS))) return rc;
-    ctx->wl_slots = 1; ctx->wl_cap_each = (unsigned)cap;
+    ctx->run.wl_slots = 1; ctx->wl_cap_each = (unsigned)cap;
     S.pairs = (const int*)ctx->b_mp_pairs.p;
     S.masks = nullptr;
     unsigned long long total = 0;
@@ -140,11 +140,11 @@ int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
     const bool var = ctx->nlab > 0;
     const bool use_tiles = T == TILE && lds <= 160*1024 && !pnl_tune("PNL_FH_NOTILES") && !var;
     if (!use_tiles && !whole) return fail(ctx, PNL_ERR_UNSUPPORTED, "a range of first cells needs the tile route of the finite-horizon assembly");
-    ctx->visited_is_assembled = use_tiles;
+    ctx->run.visited_is_assembled = use_tiles;
     for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk_tiles) {
         const int nt = (int)std::min(chunk_tiles, tiles.size()-t0);
         HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));
-        if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
         if (use_tiles) {
             auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false, true>;
             const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT, true), lds, nt, 2);
@@ -170,27 +170,26 @@ int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
         if (np > cap) return fail(ctx, PNL_ERR_STATE, "far list of the finite-horizon tiles overflowed (%u > %zu)", np, cap);
         total += np;
         if (np && var) {
-            const int ncls = (int)ctx->cls.size(), norient = ctx->nonsym ? 2 : 1, cur0 = ctx->cur;
-            for (int ko = 0; ko < ncls*norient && !rc; ko++) {
-                ctx->cur = ko/norient; ctx->orient = ko%norient;
-                pnl_refresh_tables(ctx);
-                rc = pairs_masked_impl<DIM, DPE, 0>(ctx, (int)np, S, true, false, false);
+            const int ncls = (int)ctx->cls.size(), norient = ctx->nonsym ? 2 : 1;
+            ClassScope cls(ctx, ctx->cur, true);
+            for (int ko = 0; ko < ncls*norient; ko++) {
+                cls.select(ko/norient, ko%norient);
+                if ((rc = pairs_masked_impl<DIM, DPE, 0>(ctx, (int)np, S, true, false, false))) return rc;
             }
-            ctx->cur = cur0; ctx->orient = 0;
-            pnl_refresh_tables(ctx);
-            if (rc) return rc;
         } else
         if (np && (rc = pairs_masked_impl<DIM, DPE, KT>(ctx, (int)np, S, false, false, use_tiles))) return rc;
         if (!np && use_tiles) {
             // no far entries in this chunk: the diagonal blocks of its tiles still have to reach the matrix
             scatter_diag_sparse<DPE>(ctx, (const double*)ctx->b_D.p, S);
-            if ((rc = finish_events(ctx, 1))) return rc;
+            if ((rc = finish_events(ctx))) return rc;
         }
         first = false;
     }
-    ctx->visited_pairs = total;
-    if (total == 0 && (rc = finish_events(ctx, 1))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));     // pnl_get_counters reads it as the dense work-list fill
+    ctx->run.visited_pairs = total;
+    if (total == 0 && (rc = finish_events(ctx))) return rc;
+    // slot 0 of b_wlcount holds the far-list fill of the last chunk, which check_overflow holds against its capacity (wl_slots = 1); it is
+    // no length of a work list of the tile kernels, and pnl_get_counters sums the slots in use as workListLength
+    HIPCHK(ctx, hipMemsetAsync(ctx->b_wlcount.p, 0, sizeof(unsigned), ctx->stream));
     return PNL_OK;
 }
 
@@ -262,29 +261,28 @@ int pnl_assemble_pairs_masked(pnl_context *ctx, int np, const int32_t *pairs, co
     if ((rc = pnl_sparse_ready(ctx, data, diag, S))) return rc;
     if (!masks) S.masks = nullptr;               // every entry of every pair is requested
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
-    ctx->visited_pairs = (unsigned long long)np; ctx->visited_is_assembled = false;
-    if (np == 0) return PNL_OK;
+    pnl_begin_assembly(ctx);
+    ctx->run.visited_pairs = (unsigned long long)np;
+    if (np == 0) HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
+    if (np == 0) return finish_events(ctx);                  // an empty assembly: every timer reads zero
     // variable order (piecewise constant, symmetric table): the pair list once per class, k_mp_classify keeps the pairs of the
     // class (the interface terms of NA:1966-2156 are boundary items, pnl_assemble_boundary_masked after pnl_select_class)
     // non-symmetric class table (NA:1776-1840 with symmetricCells == False): the listed pairs (c1 <= c2) once per orientation, each
     // with the class of its orientation and half the kernel (the machinery applies the factor 2 of the symmetric case); the masks
     // of (c1, c2) and (c2, c1) request the same DoF pairs, so the list of the symmetric case serves both
-    const int ncls = ctx->nlab > 0 ? (int)ctx->cls.size() : 1, cur0 = ctx->cur;
+    const int ncls = ctx->nlab > 0 ? (int)ctx->cls.size() : 1;
     const int norient = (ctx->nlab > 0 && ctx->nonsym) ? 2 : 1;
+    ClassScope cls(ctx, ctx->cur, norient > 1);
     for (int ko = 0; ko < ncls*norient; ko++) {
-        const int k = ko/norient;
-        ctx->orient = ko%norient;
-        if (ctx->nlab > 0) { ctx->cur = k; pnl_refresh_tables(ctx); }
+        if (ctx->nlab > 0) cls.select(ko/norient, ko%norient);      // a constant order: the class of pnl_select_class
         const bool fast = ctx->P.k.fast != 0, first = ko == 0;
         rc = with_shape(ctx, [&](auto D, auto E) {
             constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;
             return with_kt_2d<DIM>(fast, [&](auto kt) { return pairs_masked_impl<DIM, DPE, decltype(kt)::value>(ctx, np, S, true, first); });
         });
-        if (rc) break;
+        if (rc) return rc;
     }
-    ctx->cur = cur0; ctx->orient = 0;
-    if (norient > 1) pnl_refresh_tables(ctx);
-    return rc;
+    return PNL_OK;
 }
 
 int pnl_assemble_pairs_in_horizon(pnl_context *ctx, double *data, double *diag) {
@@ -304,6 +302,7 @@ int pnl_assemble_pairs_in_horizon_range(pnl_context *ctx, double *data, double *
     SparseOut S;
     if ((rc = pnl_sparse_ready(ctx, data, diag, S))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->b_counters.p, 0, sizeof(unsigned long long)*PNL_NCOUNTERS, ctx->stream));
+    pnl_begin_assembly(ctx);
     const bool fast = ctx->P.k.fast != 0;
     return with_shape(ctx, [&](auto D, auto E) {
         constexpr int DIM = decltype(D)::value, DPE = decltype(E)::value;

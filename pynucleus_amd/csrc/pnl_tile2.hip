@@ -61,9 +61,9 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
         constexpr int NCTR = pnl_context::UNI_CTRS;
         int rc = ensure(ctx, ctx->b_unictr, sizeof(unsigned)*NCTR);
         if (rc) return rc;
-        ctr = (unsigned*)ctx->b_unictr.p+ctx->uni_ctr_next;
-        ctx->uni_ctr_next = (ctx->uni_ctr_next+1)%NCTR;
-        if (ctx->uni_ctr_fresh > 0) ctx->uni_ctr_fresh--;
+        ctr = (unsigned*)ctx->b_unictr.p+ctx->run.uni_ctr_next;
+        ctx->run.uni_ctr_next = (ctx->run.uni_ctr_next+1)%NCTR;
+        if (ctx->run.uni_ctr_fresh > 0) ctx->run.uni_ctr_fresh--;
         else HIPCHK(ctx, hipMemsetAsync(ctr, 0, sizeof(unsigned), ctx->stream));
     }
     if (pnl_tune("PNL_VERBOSE"))
@@ -75,7 +75,7 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
 #endif
     kt_begin(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     hipLaunchKernelGGL(kfun, dim3(grid), dim3(256), lds, ctx->stream, Pt, tiles, tile_cls, (const DevKernel*)ctx->b_kcls.p, ntiles, A,
-                       (long long)ldA, Dglob, acc_stride, q, (ctx->symflush ? 1 : 0) | uni_abl | pow_flag, (const double*)ctx->b_uni.p+ctx->uni_off[q],
+                       (long long)ldA, Dglob, acc_stride, q, (ctx->run.symflush ? 1 : 0) | uni_abl | pow_flag, (const double*)ctx->b_uni.p+ctx->uni_off[q],
                        nUe, SO, ctr);
     kt_end(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     HIPCHK(ctx, hipGetLastError());
@@ -118,7 +118,7 @@ int launch_p2_t(pnl_context *ctx, const int2 *tiles, const int *tile_cls, int nt
     kt_begin(ctx, PNL_K_TILE_GENERAL);
     hipLaunchKernelGGL(kfun, dim3(grid), dim3(P2_NT), lds, ctx->stream, ctx->P, tiles, tile_cls, (const DevKernel*)ctx->b_kcls.p,
                        (const DevFormula*)ctx->b_fcls.p, A, (long long)ldA, (double*)ctx->b_D.p, cell_begin, cell_end, stride,
-                       (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, wl_cap_each, ctx->symflush ? 256 : 0, ntiles,
+                       (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, wl_cap_each, ctx->run.symflush ? 256 : 0, ntiles,
                        (unsigned*)ctx->b_tilectr.p, nUe, SO);
     kt_end(ctx, PNL_K_TILE_GENERAL);
     HIPCHK(ctx, hipGetLastError());

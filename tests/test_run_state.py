@@ -1,0 +1,123 @@
+"""The run record of an assembly (pnl_context.h: AssemblyRun): every C-ABI assembly call starts a fresh one, so nothing of an earlier
+assembly on the same context shows in the counters, the phase timers or the kernel timers of the next, and a failed assembly leaves no
+valid timers behind.  Each test assembles twice on one context and holds the second assembly against the same assembly on a context
+that never saw the first."""
+import copy
+
+import numpy as np
+import pytest
+
+TOL_ATOMIC = 1e-13          # the same terms accumulated with atomics in another order (tests/test_settled_tiles.py: TOL_ORDER)
+
+# the smallest refinement of the disc whose dense plan settles tiles (tests/test_settled_tiles.py): 6,144 cells
+NOREF_SETTLED = 5
+
+INT_COUNTERS = ('numCellPairs', 'numAssembledCellPairs', 'numIntegrations', 'numBoundaryPairs', 'numBoundaryIntegrations', 'orders',
+                'singular', 'uniformTilePairs', 'uniformTilePairsByOrder', 'settledTiles', 'workListLength')
+
+
+def _builder(dm, order, **params):
+    from pynucleus_amd import getFractionalKernel
+    from pynucleus_amd.builder import nonlocalBuilder
+    return nonlocalBuilder(dm, getFractionalKernel(dm.mesh.dim, order), dict({'target_order': 0.5}, **params), zeroExterior=True)
+
+
+def _near_field(b, Pnear):
+    """counters, phase and kernel timers of the context behind the near field of the cluster pairs"""
+    b.assembleClusters(Pnear, forceUnsymmetricMatrix=True)
+    ctx = b.context()
+    return ctx.counters(), ctx.phase_ms(), ctx.kernel_ms()
+
+
+@pytest.mark.gpu
+def test_gpu_cluster_assembly_after_dense_reports_its_own_run():
+    """getDense() on the disc with 6,144 cells takes settled tiles, uniform tiles of every order and the fold pass; the H2 near field
+    (cluster tiles) on the same context then reports none of them, and its work list is its own"""
+    from pynucleus_amd import clusters, disc, P1_DoFMap, PHYSICAL
+    dm = P1_DoFMap(disc(NOREF_SETTLED), PHYSICAL)
+    b = _builder(dm, 0.5)
+    rp = b.getH2RefinementParams()
+    root, Pnear, Pfar = clusters.getNearFieldClusters(dm, rp['eta'], rp['minSize'], rp['maxLevels'], refinementType=rp['refinementType'],
+                                                      planner=b._planner())
+    dense = b.getDense().info
+    kms = b.context().kernel_ms()
+    print('dense: settledTiles', dense['counters']['settledTiles'], 'workListLength', dense['counters']['workListLength'], kms)
+    assert dense['counters']['settledTiles'] > 0
+    assert kms['tile_settled'] > 0. and kms['fold_mirror'] > 0. and dense['phase_ms']['tiles_uniform'] > 0.
+    cnt, ms, kms = _near_field(b, Pnear)
+    cnt0, ms0, kms0 = _near_field(_builder(dm, 0.5), Pnear)
+    print('near field: workListLength', cnt['workListLength'], 'fresh', cnt0['workListLength'])
+    assert cnt['settledTiles'] == 0
+    for slot in ('tile_settled', 'tile_uniform2', 'tile_uniform3', 'tile_uniform4', 'fold_mirror'):
+        assert kms[slot] == 0., (slot, kms[slot])
+    assert ms['tiles_uniform'] == 0.
+    for key in ('workListLength', 'numIntegrations', 'orders', 'singular'):
+        assert cnt[key] == cnt0[key], (key, cnt[key], cnt0[key])
+
+
+@pytest.mark.gpu
+def test_gpu_masked_pairs_after_three_class_dense_read_no_stale_slots():
+    """three order classes: the dense assembly fills three work lists with a counter each; the masked-pair assembly (near field of a
+    variable order) on the same context has no such list, and every integer counter is that of a fresh context"""
+    from pynucleus_amd import clusters, uniformSquare, P1_DoFMap, PHYSICAL
+    from pynucleus_amd.fractionalOrders import layersFractionalOrder
+    dm = P1_DoFMap(uniformSquare(17, None, -1., -1., 1., 1.), PHYSICAL)                  # 512 cells: eight blocks of 64
+    order = layersFractionalOrder(2, np.array([-1., 0., 1.]), np.array([[0.3, 0.5], [0.5, 0.7]]))
+    b = _builder(dm, order, labelBlocks=False)                  # the dense assembly on the builder's own context
+    Pnear = clusters.getNearFieldClusters(dm, eta=3., minClusterSize=8)[1]
+    dense = b.getDense().info['counters']
+    assert len(b.tables.classes) == 3 and b.dense_context() is b.context()
+    print('dense: workListLength', dense['workListLength'])
+    assert dense['workListLength'] > 0
+    cnt = _near_field(b, Pnear)[0]
+    cnt0 = _near_field(_builder(dm, order, labelBlocks=False), Pnear)[0]
+    print('masked pairs: workListLength', cnt['workListLength'], 'fresh', cnt0['workListLength'])
+    for key in INT_COUNTERS:
+        assert cnt[key] == cnt0[key], (key, cnt[key], cnt0[key])
+
+
+@pytest.mark.gpu
+def test_gpu_failed_assembly_leaves_no_timers_and_no_state():
+    """zero exterior requested before boundary facets and boundary kernel are set: the assembly fails inside its boundary phase, behind
+    the tile kernels, with PNL_ERR_STATE.  The timers of the successful assembly before it are gone; once the tables are complete the
+    next assembly is that of a fresh context."""
+    import torch
+    from pynucleus_amd import _lib, disc, P1_DoFMap, PHYSICAL
+    dm = P1_DoFMap(disc(3), PHYSICAL)
+    T = _builder(dm, 0.5).tables
+    N, nc = dm.num_dofs, dm.mesh.num_cells
+    T0 = copy.copy(T)
+    T0.has_boundary_tables = False                              # upload_tables then sets no boundary facets, kernel or rules
+    dev = torch.cuda.current_device()
+
+    def assemble(ctx, zero_exterior):
+        A = torch.zeros((N, N), dtype=torch.float64, device='cuda')
+        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        ctx.assemble_dense(A.data_ptr(), N, zero_exterior, 0, nc)
+        ctx.synchronize()
+        return A.cpu().numpy()
+
+    ctx = _lib.Context(dev)
+    ctx.upload_tables(T0)
+    assemble(ctx, False)
+    assert ctx.phase_ms()['total'] > 0.
+    with pytest.raises(_lib.PnlError, match='status {}: zero_exterior needs'.format(_lib.PNL_ERR_STATE)):
+        assemble(ctx, True)
+    torch.cuda.synchronize()
+    with pytest.raises(_lib.PnlError, match='nothing assembled yet'):
+        ctx.phase_ms()
+    with pytest.raises(_lib.PnlError, match='nothing assembled yet'):
+        ctx.kernel_ms()
+    ctx.upload_tables(T)
+    A = assemble(ctx, True)
+    cnt = ctx.counters()
+    fresh = _lib.Context(dev)
+    fresh.upload_tables(T)
+    A0 = assemble(fresh, True)
+    cnt0 = fresh.counters()
+    err = np.abs(A-A0).max()/np.abs(A0).max()
+    print('max|A - A0|/max|A0| = %.3e' % err)
+    for key in INT_COUNTERS:
+        assert cnt[key] == cnt0[key], (key, cnt[key], cnt0[key])
+    assert cnt['numBoundaryPairs'] > 0
+    assert err <= TOL_ATOMIC
