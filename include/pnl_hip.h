@@ -89,9 +89,10 @@ enum pnl_counter {
     PNL_C_UNIFORM_Q2 = 131,            /* [131..133]: pairs integrated by the uniform-tile kernels of order 2, 3, 4 */
     PNL_C_SETTLED_TILES = 134,         /* mixed tiles the assembly took through the settled instantiation of the tile kernel  */
     PNL_C_CODE_BUILDS = 135,           /* times the context has computed the pair codes of settled tiles (once per tile plan)  */
-    PNL_C_WORKLIST_LENGTH = 136        /* entries the tile kernels handed to the device work lists, summed over the passes      */
+    PNL_C_WORKLIST_LENGTH = 136,       /* entries the tile kernels handed to the device work lists, summed over the passes      */
+    PNL_C_SETTLED_LIST_TILES = 137     /* settled tiles the assembly took with the pair lists of the plan (the others: by their codes) */
 };
-#define PNL_NUM_COUNTERS 137
+#define PNL_NUM_COUNTERS 138
 
 /* Options (process-wide).  The library reads no environment variable on its assembly path; an option exists once it has been
  * set here (value NULL removes it).  A product build accepts
@@ -108,6 +109,9 @@ enum pnl_counter {
  *   "PNL_MIXED_UNSETTLED" the tile plan settles no mixed tile: every mixed tile is classified pair by pair in every assembly
  *                     (tests: both paths against each other; read when the plan is made, changing it makes a new plan).  Tiles are
  *                     settled only where the plan computes exact order ranges: a tuning build's PNL_NO_EXACT_TILES settles nothing too,
+ *   "PNL_SETTLED_CODES" the tile plan keeps the pair codes of the settled tiles but not their pair lists: the tile kernel builds the lists
+ *                     of a settled tile from its codes in every assembly (tests and A/B measurement; read when the plan is made,
+ *                     changing it makes a new plan).  The plan does the same by itself where the device has no memory for the lists,
  *   "PNL_NO_OVERLAP", "PNL_NO_FORK"   profiling: no side streams, every phase on the caller's stream one after the other,
  *   "PNL_FOLD_STAGES" dense 2D P1 assembly of one order class: number of far bands of the staged fold (pnl_get_fold_stages); 0: one
  *                     fold of the whole matrix behind all tile kernels (the default),
@@ -406,6 +410,12 @@ int pnl_get_fold_plan(pnl_context *ctx, int32_t *images, int64_t nimages, int8_t
 /* The settled tiles of the resident dense tile plan (tests): tiles[i][2] = (block a, block b) of the first ntiles of them, in the order
  * of the launch (most pairs of a 6-point rule first).  Returns their number (0: the plan settles nothing), or an error. */
 int pnl_get_settled_tiles(pnl_context *ctx, int32_t *tiles, int64_t ntiles);
+/* Pair codes and pair lists of the first ntiles settled tiles of the resident plan (tests), in the order of pnl_get_settled_tiles; either
+ * pointer may be NULL.  codes[t][512]: word tid holds the 2-bit codes of the eight pairs of thread tid (PNL_SELFTEST_SETTLED_LAYOUT).
+ * lists[t][4104]: words 0 .. 2 = n4, n3, n2, the numbers of pairs of order 4, 3, 2; from word 8 on the n4 + n3 + n2 entries
+ * p | (order - 2) << 12, order 4 first, then 3, then 2, ascending pair index p within an order; zero behind the last entry.
+ * Returns the number of tiles the plan holds lists for (0: it keeps codes only), or an error. */
+int pnl_get_settled_lists(pnl_context *ctx, uint16_t *codes, uint16_t *lists, int64_t ntiles);
 /* device time of the tile kernels of the last assemble call, one HIP-event pair around each launch (milliseconds, 0 if the
  * kernel did not run; a slot that was launched several times -- stages of a staged fold, order classes -- holds the sum over
  * its launches): [0] general tile kernel, [1] uniform tiles of

@@ -21,7 +21,7 @@ PNL_INTERIOR = 0
 PNL_BOUNDARY = 1
 PNL_FLAG_NO_MIRROR = 1
 PNL_FLAG_SYMMETRIC_FLUSH = 2
-PNL_NUM_COUNTERS = 137
+PNL_NUM_COUNTERS = 138
 
 # every symbol include/pnl_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_set_stream', 'pnl_synchronize',
@@ -30,7 +30,7 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_assemble_dense_tiles', 'pnl_get_counters', 'pnl_get_phase_ms', 'pnl_get_kernel_ms', 'pnl_get_fold_stages', 'pnl_get_fold_plan', 'pnl_get_settled_tiles', 'pnl_tree_build', 'pnl_tree_build_blocks', 'pnl_tree_build_refined', 'pnl_tree_build_horizon', 'pnl_tree_build_device', 'pnl_tree_destroy', 'pnl_tree_sizes', 'pnl_tree_get', 'pnl_tree_node_cells', 'pnl_h2_transfer_matrices', 'pnl_nfplan_build', 'pnl_nfplan_destroy', 'pnl_nfplan_sizes', 'pnl_nfplan_get', 'pnl_horizon_pattern', 'pnl_near_pattern', 'pnl_pattern_set_max_nnz', 'pnl_set_option', 'pnl_set_cell_order', 'pnl_set_interaction_transform', 'pnl_set_order_vertex_values', 'pnl_h2_get', 'pnl_h2_set', 'pnl_pattern_nnz', 'pnl_pattern_get', 'pnl_pattern_destroy', 'pnl_set_row_slab', 'pnl_diag_blocks_size', 'pnl_get_diag_blocks', 'pnl_slab_matvec', 'pnl_slab_diagonal', 'pnl_gemv', 'pnl_cg_jacobi',
            'pnl_inv_diagonal', 'pnl_set_classes', 'pnl_select_class', 'pnl_upload_sparsity', 'pnl_upload_sparsity_device', 'pnl_assemble_pairs_masked', 'pnl_assemble_boundary_masked', 'pnl_assemble_clusters_tiled', 'pnl_h2_setup', 'pnl_h2_matvec', 'pnl_h2_upward', 'pnl_h2_interact', 'pnl_h2_downward', 'pnl_h2_sizes', 'pnl_spmv',
            'pnl_assemble_pairs_in_horizon', 'pnl_assemble_pairs_in_horizon_range', 'pnl_set_nonsymmetric', 'pnl_set_order_function', 'pnl_upload_pointwise_rules', 'pnl_assemble_dense_pointwise',
-           'pnl_assemble_pairs_masked_pointwise', 'pnl_assemble_boundary_masked_pointwise',
+           'pnl_assemble_pairs_masked_pointwise', 'pnl_assemble_boundary_masked_pointwise', 'pnl_get_settled_lists',
            'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest',
            'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs',
            'pnl_csr_cg_jacobi', 'pnl_fe_space_create', 'pnl_fe_space_destroy', 'pnl_assemble_nonlinearity', 'pnl_imex_create',
@@ -154,6 +154,7 @@ def load():
     L.pnl_get_fold_stages.argtypes = [vp, vp, i32]
     L.pnl_get_fold_plan.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64]
     L.pnl_get_settled_tiles.argtypes = [vp, vp, C.c_int64]
+    L.pnl_get_settled_lists.argtypes = [vp, vp, vp, C.c_int64]
     L.pnl_set_row_slab.argtypes = [vp, i32, vp, i32, vp]
     L.pnl_tree_build.argtypes = [i32, i32, vp, vp, vp, i32, dbl, i32, i32, i32, C.POINTER(vp)]
     L.pnl_tree_build_blocks.argtypes = [i32, i32, vp, vp, vp, i32, dbl, i32, i32, i32, vp, i32, C.POINTER(vp)]
@@ -560,7 +561,8 @@ class Context:
         return dict(numCellPairs=int(out[0]), numAssembledCellPairs=int(out[1]), numIntegrations=int(out[2]),
                     numBoundaryPairs=int(out[3]), numBoundaryIntegrations=int(out[4]), orders=hist, singular=sing,
                     uniformTilePairs=int(out[6]), uniformTilePairsByOrder={2+k: int(out[131+k]) for k in range(3)},
-                    settledTiles=int(out[134]), codeBuilds=int(out[135]), workListLength=int(out[136]))
+                    settledTiles=int(out[134]), codeBuilds=int(out[135]), workListLength=int(out[136]),
+                    settledListTiles=int(out[137]))
 
     def phase_ms(self):
         out = np.zeros(7, dtype=np.float32)
@@ -611,6 +613,20 @@ class Context:
         if n:
             self.check(min(self.L.pnl_get_settled_tiles(self.h, tiles.ctypes.data, n), 0))
         return tiles
+
+    def settled_lists(self):
+        """(codes [n, 512], lists [n, 4104] or None) of the settled tiles of the resident dense tile plan, uint16, in the order of
+        settled_tiles(): the plan's pair codes and the pair lists it derived from them (include/pnl_hip.h: pnl_get_settled_lists);
+        lists is None where the plan keeps codes only (option PNL_SETTLED_CODES)"""
+        n = self.settled_tiles().shape[0]
+        codes = np.zeros((n, 512), dtype=np.uint16)
+        have = self.L.pnl_get_settled_lists(self.h, codes.ctypes.data if n else None, None, n)
+        self.check(min(have, 0))
+        if not have:
+            return codes, None
+        lists = np.zeros((n, 4104), dtype=np.uint16)
+        self.check(min(self.L.pnl_get_settled_lists(self.h, None, lists.ctypes.data, n), 0))
+        return codes, lists
 
     def fold_plan(self, nblocks):
         """the staged plan: images[:, 3] = (row range, column range, stage), stage and uniform order (0: none) of tile (a, b) as

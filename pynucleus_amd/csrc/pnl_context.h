@@ -49,6 +49,7 @@ struct AssemblyRun {
     // the tile kernels wrote the block-slot storage; ev_fold is recorded behind a fold + mirror pass; the staged sequence runs
     bool slot_used = false, fold_event_set = false, stg_active = false;
     int settled_run = 0;            // tiles taken through k_tile_distant<.., SETTLED>
+    int lists_run = 0;              // ... of them through k_tile_distant<.., SETTLED, LISTS> (pair lists of the plan)
     int tile_off = 0, n_mixed = 0, n_pure = 0;      // slice of b_tiles of the class pass being launched (dense P1 / 1D)
     // fill counters of b_wlcount in use (one per class / pass; 0: the path keeps none): pnl_get_counters sums them, check_overflow
     int wl_slots = 0;               // holds them against wl_cap_each
@@ -122,8 +123,12 @@ struct pnl_context {
     // settled tiles of the resident plan (dense 2D P1, one order class; pnl_setup.hip: settle_tiles): the last n_settled mixed tiles of
     // b_tiles, their pair codes in b_codes (512 16-bit words per tile, allocated with the tile lists and dropped with them).
     // settled_want: the plan was made without the option PNL_MIXED_UNSETTLED; code_builds: times this context has computed codes
-    DevBuf b_codes;
-    int n_settled = 0, settled_want = -1;
+    // b_lists: the pair lists of the settled tiles, derived from the codes (one record of PNL_LIST_STRIDE 16-bit words per tile,
+    // pnl_device.h; k_tile_distant<.., SETTLED, LISTS> reads them instead of building the lists from the codes in every assembly).  Empty with the
+    // option PNL_SETTLED_CODES or where the device has no memory for them: the assembly then takes the settled tiles by their codes.
+    // lists_want: the plan was made without PNL_SETTLED_CODES
+    DevBuf b_codes, b_lists;
+    int n_settled = 0, settled_want = -1, lists_want = -1;
     std::vector<int2> settled_tiles;              // host copy of the settled part of the list (pnl_get_settled_tiles)
     long long code_builds = 0;
     // staged fold of the 2D P1 one-class path (pnl_setup.hip: stage_plan): blocks that hold a copy of a DoF of every range of 32 DoFs
@@ -417,6 +422,9 @@ int pnl_tile_order_range(pnl_context *ctx, const DevFormula &qo, int ncand, sign
 // pnl_hip.hip, for pnl_upload_tiles: k_tile_pair_codes over n tiles of 64 cells (device pointer): codes (device, 512 words per tile) and /
 // or host_stat (per tile -1 not settled, else its number of pairs of a 6-point rule) may be nullptr; synchronises the stream
 int pnl_tile_pair_codes(pnl_context *ctx, const DevFormula &qo, const int2 *tiles, int n, unsigned short *codes, int *host_stat);
+// pnl_hip.hip, for pnl_upload_tiles: k_tile_pair_lists, the list records (device, PNL_LIST_STRIDE words per tile) of n settled tiles from
+// their codes (device); synchronises the stream
+int pnl_tile_pair_lists(pnl_context *ctx, const unsigned short *codes, int n, unsigned short *lists);
 // pnl_hip.hip: counting sort of a work list by order (k_wl_hist / _scan / _scatter): histogram, offsets, 16-pair chunk offsets and cursors
 // of the bins, PNL_WL_BINS + 1 words each, carved out of aux_base
 struct WlBins { unsigned *hist, *offs, *coff, *cursor; };

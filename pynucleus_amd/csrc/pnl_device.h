@@ -101,6 +101,13 @@ struct DevProblem {
 #ifndef PNL_DIAG_MULT
 #define PNL_DIAG_MULT 21
 #endif
+// The pair lists of a settled tile (pnl_context::b_lists), one record of PNL_LIST_STRIDE 16-bit words per tile: words 0 .. 2 the
+// numbers n4, n3, n2 of pairs of order 4, 3, 2, then from word PNL_LIST_HEAD on the n4 + n3 + n2 <= 4096 entries p | (q - 2) << 12, the
+// pairs of order 4 first, then order 3, then order 2 -- the order in which the chunk queue of the tile kernel evaluates them --, ascending
+// pair index p within an order, no padding between the orders (a chunk is 64 consecutive entries of one order, the last one of an
+// order is short).  Words behind the last entry are zero.
+#define PNL_LIST_HEAD 8
+#define PNL_LIST_STRIDE (PNL_LIST_HEAD+4096)
 __host__ __device__ constexpr int tile_sweep_row(int tid, int k, int tile, int nt) { return k*(nt/tile)+tid/tile; }
 __host__ __device__ constexpr int tile_diag_cell(int r, int j, int tile) { return (r+PNL_DIAG_MULT*j)%tile; }
 

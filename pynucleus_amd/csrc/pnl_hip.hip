@@ -167,7 +167,8 @@ int ensure_worklist(pnl_context *ctx, double pairs, int regions) {
 // The plan lists the unsettled tiles first, then the settled ones with their pair codes in b_codes (pnl_setup.hip).  An assembly that
 // writes the block-slot storage of the whole operator (one rank, symmetric, no PNL_FLAG_SYMMETRIC_FLUSH) runs the unsettled tiles
 // -- they fill the work list --, then the settled ones through the SETTLED instantiation with a ticket counter of its own; every
-// other assembly takes the whole list through the classifying kernel.
+// other assembly takes the whole list through the classifying kernel.  Where the plan also holds the pair lists of the settled tiles
+// (b_lists; not with the option PNL_SETTLED_CODES) the settled launch is the LISTS instantiation, which reads the records instead of the codes.
 template <int DIM, int DPE, int TILE, int KT, bool SETTLED = false>
 int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, int cell_begin, int cell_end, const SlotOut &SO) {
     using S = TileSmem<DIM, DPE, TILE, KT == 0>;
@@ -195,6 +196,14 @@ int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, 
         return fail(ctx, PNL_ERR_UNSUPPORTED, "a block of %d cells touches %d DoFs: LDS sub-block of %zu bytes exceeds 160 KiB "
                     "(cells must be numbered with spatial locality)", TILE, ctx->nU, lds);
     auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false, false, SETTLED>;
+    const unsigned short *codes = SETTLED ? (const unsigned short*)ctx->b_codes.p : (const unsigned short*)nullptr;
+    if constexpr (can_settle && SETTLED) {
+        if (ctx->b_lists.p) {
+            kfun = k_tile_distant<DIM, DPE, TILE, KT, false, false, true, true>;
+            codes = (const unsigned short*)ctx->b_lists.p;
+            ctx->run.lists_run = ns;
+        }
+    }
     const int grid_mult = pnl_tune("PNL_GRID_MULT") ? atoi(pnl_tune("PNL_GRID_MULT")) : 1;
     const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT), lds, ntiles, 2, grid_mult);
     if (g.rc) return g.rc;
@@ -210,7 +219,7 @@ int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, 
                            (const int2*)ctx->b_tiles.p+ctx->run.tile_off+first, A,
                            (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), cell_begin, cell_end, acc_stride, (int4*)ctx->b_wl.p,
                            wlc, ctx->wl_cap_each, ctx->ablate | (ctx->run.symflush ? 256 : 0), ntiles, ClusterTiles{},
-                           ctr, SOk, SETTLED ? (const unsigned short*)ctx->b_codes.p : (const unsigned short*)nullptr);
+                           ctr, SOk, codes);
     if (SETTLED) kt_end(ctx, PNL_K_TILE_SETTLED);
     kt_end(ctx, PNL_K_TILE_GENERAL);
     HIPCHK(ctx, hipGetLastError());
@@ -1002,6 +1011,18 @@ int pnl_tile_pair_codes(pnl_context *ctx, const DevFormula &qo, const int2 *tile
                        host_stat ? (int*)ctx->b_candq.p : (int*)nullptr);
     HIPCHK(ctx, hipGetLastError());
     if (host_stat) HIPCHK(ctx, hipMemcpyAsync(host_stat, ctx->b_candq.p, sizeof(int)*(size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PNL_OK;
+}
+
+// the tile plan (pnl_setup.hip): k_tile_pair_lists, the records of n settled tiles (device, PNL_LIST_STRIDE words per tile) from their
+// codes (device, 512 words per tile).  Synchronises the stream.
+int pnl_tile_pair_lists(pnl_context *ctx, const unsigned short *codes, int n, unsigned short *lists) {
+    if (n <= 0) return PNL_OK;
+    if (ctx->tile != 64) return fail(ctx, PNL_ERR_STATE, "pair lists: tiles of 64 cells");
+    HIPCHK(ctx, hipMemsetAsync(lists, 0, (size_t)n*PNL_LIST_STRIDE*sizeof(unsigned short), ctx->stream));
+    hipLaunchKernelGGL(k_tile_pair_lists<64>, dim3(std::min(n, 256*8)), dim3(512), 0, ctx->stream, codes, n, lists);
+    HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PNL_OK;
 }

@@ -599,12 +599,18 @@ __host__ __device__ constexpr int tile_waves(int dpe, int kt, bool fh = false) {
 // pair of order 2, 3 or 4 with a packed rule, and the plan has recorded which: the first pass of the classification is a 16-bit load
 // per thread (codes[tile index][thread], layout: pnl_device.h) and the cell data only it reads is not staged.  Lists, chunk queue,
 // evaluation, flush and statistics are the same code, and they see the same lists in the same order.
-template <int DIM, int DPE, int TILE, int KT, bool CLUSTER, bool FH = false, bool SETTLED = false>
+// LISTS (settled tiles whose pair lists the plan holds as well): the lists, the chunk queue and the order statistics of a settled tile
+// depend on its codes alone, so the plan keeps them too (k_tile_pair_lists, record layout: pnl_device.h; `codes` are the records then).
+// stage() copies the record of the next tile into the front of s_list, its header into s_chunk; the chunk queue and the statistics
+// come from the header, and the two passes over the codes, the reservations and the sort of list C are not compiled.  Evaluators,
+// flush and the ticket counter are the same code.
+template <int DIM, int DPE, int TILE, int KT, bool CLUSTER, bool FH = false, bool SETTLED = false, bool LISTS = false>
 __global__ void __launch_bounds__(tile_threads(DPE, KT, FH), tile_waves(DPE, KT, FH))
 k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__restrict__ A, long long ldA,
                double *__restrict__ Dglob, int cell_begin, int cell_end, int acc_stride, int4 *__restrict__ worklist,
                unsigned *__restrict__ wl_count, unsigned wl_cap, int ablate, int ntiles, const ClusterTiles CT,
                unsigned *__restrict__ tile_ctr, const SlotOut SO, const unsigned short *__restrict__ codes) {
+    static_assert(!LISTS || SETTLED, "pair lists: settled tiles only");
     static_assert(!SETTLED || (!CLUSTER && !FH && DIM == 2 && DPE == 3 && TILE*TILE == 8*tile_threads(DPE, KT, FH)),
                   "settled tiles: dense 2D P1, eight pairs per thread");
     // debug switches that skip work (evaluation, accumulation, flush) exist only in PNL_DEBUG_ABLATE builds; bit 256 is
@@ -703,7 +709,17 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         // what the classification reads per cell: one 8-byte word (padding and volume-zero cells carry negative vertex ids)
         if (!SETTLED) s_cf[side*TILE+l] = make_int2((vid0 >= 0 ? 1 : 0) | (has_dof ? 2 : 0), __float_as_int((float)P.clog[2*(size_t)P.ncp+c]));
     }
-    if (SETTLED) s_code[tid] = codes[(size_t)tile_idx*NT+tid];
+    if constexpr (LISTS) {
+        // the record of the tile: header -> s_chunk[0 .. 2], the entries in use -> s_list (two 8-byte words per thread)
+        static_assert(S::n_int%2 == 0 && S::o_list%4 == 0 && PNL_LIST_HEAD%4 == 0 && PNL_LIST_STRIDE%4 == 0 && 4*2*NT == PAIRS, "8-byte copies of the record");
+        const unsigned short *__restrict__ rec = codes+(size_t)tile_idx*PNL_LIST_STRIDE;
+        const int total = (int)rec[0]+(int)rec[1]+(int)rec[2];
+        if (tid < 3) s_chunk[tid] = rec[tid];
+        const uint2 *__restrict__ src = (const uint2*)(rec+PNL_LIST_HEAD);
+        uint2 *dst = (uint2*)s_list;
+        if (4*tid < total) dst[tid] = src[tid];
+        if (4*(tid+NT) < total) dst[tid+NT] = src[tid+NT];
+    } else if (SETTLED) s_code[tid] = codes[(size_t)tile_idx*NT+tid];
     };
     // The tiles of a workgroup run as a software pipeline: the cell data of the NEXT tile is staged before the flush of this one is
     // issued (a load issued behind the stores / atomics would wait for all of them), the flush zeroes the accumulators it has
@@ -739,9 +755,11 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     // list A grows from the front of s_list, list C from its back; list B from the front of s_l32, the far list (pairs for
     // the global work list) from its back
     int *s_l32 = (int*)(s_list+PAIRS+((((size_t)(s_list+PAIRS)) & 2) ? 1 : 0));
-    int overflow = 0;
     const int lane = tid & 63;
     const unsigned long long lt = (1ull << lane)-1ull;
+    // settled tiles with lists: the record staged with the cell data holds the lists; nothing to classify, no second barrier
+    if constexpr (!LISTS) {
+    int overflow = 0;
     int cnt234[3] = {0, 0, 0};
     // The workgroup size is a multiple of the tile edge: a thread keeps its cell j of block b for the whole tile, so what depends
     // on j alone is read once.  Two passes: the first computes (list, order key) of every pair of the thread -- 16 bits each, kept
@@ -881,13 +899,14 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         for (int k = 0; k < 3; k++) if (cnt234[k]) atomicAdd(&s_cnt[2+k], cnt234[k]);
     }
     lds_barrier();
+    }
     // next tile of this workgroup (every thread has read the previous value before the barrier above; the barrier at the end
     // of the tile publishes this one)
     int next_tile = 0;                                    // asked for here, published behind the evaluation: the counter's latency is hidden
     if (tid == 0) next_tile = (int)(gridDim.x+atomicAdd(tile_ctr, 1u));
     // list C: counting sort by order into the free middle of the 32-bit list (behind list B, before the far list), chunks of 64
     // pairs of ONE order, highest order first.  s_cnt[0] = number of these chunks, s_cnt[1] = the chunk queue of the evaluation
-    const int nC = __builtin_amdgcn_readfirstlane(s_misc[3]), nBl = __builtin_amdgcn_readfirstlane(s_misc[1]);
+    const int nC = LISTS ? 0 : __builtin_amdgcn_readfirstlane(s_misc[3]), nBl = LISTS ? 0 : __builtin_amdgcn_readfirstlane(s_misc[1]);
     if (nC && tid == 64 && !(abl & 2)) {
         int run = 0, nch = 0;
         for (int q = min(17, P.qmax); q >= 2; q--) {
@@ -955,7 +974,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     for (int r = 0; r < (PNL_MAXQ+NT)/NT; r++) {
         const int q = 2+tid+r*NT;
         if (q <= P.qmax) {
-            const int cq = s_cnt[q];
+            const int cq = LISTS ? (q <= 4 ? s_chunk[4-q] : 0) : s_cnt[q];      // lists: the header n4, n3, n2 of the record
             if (cq) {
                 const int ne = s_ttn[q];
                 const unsigned long long n = (unsigned long long)(ne ? ne : P.off[q+1]-P.off[q]);
@@ -1021,8 +1040,11 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     if (!(abl & 2))
     kern_dispatch<KT, fh>(P.k, lpow, [&](auto ktag) {
     constexpr int KTE = decltype(ktag)::value;              // KT, or 3: the branch-free general power (pnl_common.h)
-    const int nAl = __builtin_amdgcn_readfirstlane(s_misc[0]);
-    const int nchC = nC ? __builtin_amdgcn_readfirstlane(s_cnt[0]) : 0, nchB = (nBl+63) >> 6, nchA = (nAl+63) >> 6;
+    // lists of the record: order 4, 3, 2 (n4, n3, n2 entries, one behind the other); else list C, B, A
+    const int n4 = LISTS ? __builtin_amdgcn_readfirstlane(s_chunk[0]) : 0, n3 = LISTS ? __builtin_amdgcn_readfirstlane(s_chunk[1]) : 0;
+    const int nAl = __builtin_amdgcn_readfirstlane(LISTS ? s_chunk[2] : s_misc[0]);
+    const int nchC = LISTS ? (n4+63) >> 6 : (nC ? __builtin_amdgcn_readfirstlane(s_cnt[0]) : 0);
+    const int nchB = ((LISTS ? n3 : nBl)+63) >> 6, nchA = (nAl+63) >> 6;
     const int total = nchC+nchB+nchA;
 #pragma unroll 1
     for (;;) {
@@ -1032,6 +1054,14 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         if (c >= total) break;
         int q, p;
         bool act;
+        if constexpr (LISTS) {
+            const int g = c < nchC ? 0 : (c < nchC+nchB ? 1 : 2);                     // wave-uniform
+            const int ng = g == 0 ? n4 : (g == 1 ? n3 : nAl), off = g == 0 ? 0 : (g == 1 ? n4 : n4+n3);
+            const int idx = (c-(g == 0 ? 0 : (g == 1 ? nchC : nchC+nchB)))*64+lane;
+            q = 4-g;
+            act = idx < ng;
+            p = (int)s_list[off+(act ? idx : 0)] & 4095;
+        } else
         if (c < nchC) {
             const int desc = __builtin_amdgcn_readfirstlane(s_chunk[c]);
             const int start = (desc >> 7) & 8191, cnt = (desc & 127)+1;
@@ -3463,6 +3493,52 @@ k_tile_pair_codes(const DevProblem P, const DevFormula qo, const int2 *__restric
             __syncthreads();
             if (tid == 0) stat[t] = s_red[0] ? -1 : s_red[1];
         }
+        __syncthreads();
+    }
+}
+
+// Pair lists of the settled tiles from their codes (record layout: pnl_device.h; the codes stay the plan's decision, the lists only
+// restate them in the order of the evaluation).  Thread u takes the eight pairs p = 8 u .. 8 u + 7: pair p = 64 r + j is sweep r / 8 of
+// thread (r % 8) 64 + j of the tile kernel (tile_sweep_row), so ascending p within an order is ascending thread, then ascending pair of
+// the thread.  lists must be zeroed by the caller (words behind the last entry).
+template <int TILE>
+__global__ void __launch_bounds__(512)
+k_tile_pair_lists(const unsigned short *__restrict__ codes, int ntiles, unsigned short *__restrict__ lists) {
+    constexpr int NT = 512, PER = TILE*TILE/NT, ROWS = NT/TILE;
+    static_assert(PER == 8 && TILE*TILE <= 4096 && PNL_LIST_STRIDE >= PNL_LIST_HEAD+TILE*TILE, "one record holds every pair of a tile");
+    __shared__ unsigned short s_code[NT];
+    __shared__ int s_n[3][NT+1];                          // per order 4, 3, 2: pairs of the threads before this one
+    const int tid = threadIdx.x;
+#pragma unroll 1
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        s_code[tid] = codes[(size_t)t*NT+tid];
+        __syncthreads();
+        int c[PER], n[3] = {0, 0, 0};
+#pragma unroll
+        for (int u = 0; u < PER; u++) {
+            const int p = PER*tid+u, r = p/TILE, j = p%TILE;
+            c[u] = (s_code[(r%ROWS)*TILE+j] >> (2*(r/ROWS))) & 3;         // 0 none, 1 .. 3 order 2 .. 4
+#pragma unroll
+            for (int g = 0; g < 3; g++) n[g] += c[u] == 3-g ? 1 : 0;
+        }
+#pragma unroll
+        for (int g = 0; g < 3; g++) s_n[g][tid+1] = n[g];
+        __syncthreads();
+        if (tid < 3) {
+            int run = 0;
+            s_n[tid][0] = 0;
+            for (int k = 1; k <= NT; k++) { run += s_n[tid][k]; s_n[tid][k] = run; }
+        }
+        __syncthreads();
+        unsigned short *__restrict__ rec = lists+(size_t)t*PNL_LIST_STRIDE;
+        if (tid < 3) rec[tid] = (unsigned short)s_n[tid][NT];
+        const int n4 = s_n[0][NT], n3 = s_n[1][NT];
+        int pos[3] = {s_n[0][tid], n4+s_n[1][tid], n4+n3+s_n[2][tid]};
+#pragma unroll
+        for (int u = 0; u < PER; u++)
+#pragma unroll
+            for (int g = 0; g < 3; g++)
+                if (c[u] == 3-g) rec[PNL_LIST_HEAD+pos[g]++] = (unsigned short)((PER*tid+u) | ((4-g-2) << 12));
         __syncthreads();
     }
 }

@@ -699,7 +699,7 @@ const char *const k_product_options[] = {"PNL_WL_FRAC", "PNL_FH_NOTILES", "PNL_N
                                          "PNL_NO_OVERLAP", "PNL_NO_FORK",
                                          // tests: at most this many workgroups of a persistent tile kernel (every workgroup then walks
                                          // many tiles at test sizes: the pipelined tile loops against the oracle)
-                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED",
+                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED", "PNL_SETTLED_CODES",
                                          // staged fold of the dense 2D P1 assembly: far bands (0: one fold behind all tiles), spare workgroup
                                          // slots per CU of the far uniform launches, where the boundary term starts (3 / 4)
                                          "PNL_FOLD_STAGES", "PNL_UNI_SPARE", "PNL_BND_MODE"};
@@ -1157,13 +1157,16 @@ struct TilePlan {
 static int fold_stages_wanted();
 // the option PNL_MIXED_UNSETTLED (a product option, read when the plan is made): the plan settles no mixed tile
 static int settled_wanted() { return pnl_tune("PNL_MIXED_UNSETTLED") ? 0 : 1; }
+// the option PNL_SETTLED_CODES (a product option, read when the plan is made): the plan keeps the codes of the settled tiles only, and
+// the tile kernel builds their pair lists from the codes in every assembly
+static int lists_wanted() { return pnl_tune("PNL_SETTLED_CODES") ? 0 : 1; }
 
 // repeated assemblies of the same work list keep it resident
 static bool tiles_resident(const pnl_context *ctx, const std::vector<int2> &tiles, const TilePlan &R) {
     const std::vector<pnl_order_formula> &forms = R.forms;
     return tiles.size() == ctx->tiles_cached.size() && ctx->b_tiles.p && ctx->tiles_cb == R.cell_begin && ctx->tiles_ce == R.cell_end &&
         forms.size() == ctx->tiles_forms.size() && std::memcmp(forms.data(), ctx->tiles_forms.data(), sizeof(pnl_order_formula)*R.ncls) == 0 &&
-        ctx->tiles_filter == ctx->run.tile_cell_filter && ctx->stg_want == fold_stages_wanted() && ctx->settled_want == settled_wanted() &&
+        ctx->tiles_filter == ctx->run.tile_cell_filter && ctx->stg_want == fold_stages_wanted() && ctx->settled_want == settled_wanted() && ctx->lists_want == lists_wanted() &&
         (tiles.empty() || std::memcmp(tiles.data(), ctx->tiles_cached.data(), tiles.size()*sizeof(int2)) == 0);
 }
 
@@ -1528,6 +1531,7 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
         mixed[k].insert(mixed[k].end(), settled.begin(), settled.end());
     }
     if (settled.empty()) ctx->b_codes.release();
+    if (settled.empty() || !lists_wanted()) ctx->b_lists.release();
     ctx->settled_tiles.clear();
     std::vector<int2> all;
     ctx->single_launch = R.p2;
@@ -1550,8 +1554,18 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
         ctx->n_settled = (int)settled.size();
         ctx->settled_tiles = settled;
         ctx->code_builds++;
+        // the pair lists of these codes.  No device memory for them: the settled tiles stay settled and are taken by their codes
+        if (lists_wanted()) {
+            if (ensure(ctx, ctx->b_lists, settled.size()*PNL_LIST_STRIDE*sizeof(unsigned short)) != PNL_OK) {
+                (void)hipGetLastError();
+                ctx->err.clear();
+                ctx->b_lists.release();
+            } else if ((rc = pnl_tile_pair_lists(ctx, (const unsigned short*)ctx->b_codes.p, (int)settled.size(), (unsigned short*)ctx->b_lists.p)))
+                return rc;
+        }
     }
     ctx->settled_want = settled_wanted();
+    ctx->lists_want = lists_wanted();
     ctx->tiles_cached = tiles; ctx->tiles_cb = cell_begin; ctx->tiles_ce = cell_end; ctx->tiles_forms = R.forms;
     ctx->tiles_filter = ctx->run.tile_cell_filter;
     ctx->stg_want = stages_wanted;
@@ -1714,6 +1728,7 @@ int pnl_get_counters(pnl_context *ctx, int64_t *out, int n) {
     tmp[0] = ctx->run.visited_is_assembled ? tmp[1] : ctx->run.visited_pairs;
     for (int i = 0; i < n && i < PNL_NCOUNTERS; i++) out[i] = (int64_t)tmp[i];
     if (n > PNL_C_SETTLED_TILES) out[PNL_C_SETTLED_TILES] = ctx->run.settled_run;
+    if (n > PNL_C_SETTLED_LIST_TILES) out[PNL_C_SETTLED_LIST_TILES] = ctx->run.lists_run;
     if (n > PNL_C_CODE_BUILDS) out[PNL_C_CODE_BUILDS] = ctx->code_builds;
     if (n > PNL_C_WORKLIST_LENGTH) {
         // entries the tile kernels handed to the work lists, over the passes of the assembly (the fill counters check_overflow reads)
@@ -1779,6 +1794,19 @@ int pnl_get_settled_tiles(pnl_context *ctx, int32_t *tiles, int64_t ntiles) {
     if ((int)st.size() != ctx->n_settled) return fail(ctx, PNL_ERR_STATE, "the resident tile list is not that of a dense assembly");
     for (size_t i = 0; i < st.size() && (int64_t)i < ntiles; i++) { tiles[2*i] = st[i].x; tiles[2*i+1] = st[i].y; }
     return (int)st.size();
+}
+
+int pnl_get_settled_lists(pnl_context *ctx, uint16_t *codes, uint16_t *lists, int64_t ntiles) {
+    if (!ctx || ntiles < 0) return PNL_ERR_INVALID;
+    if (!ctx->b_tiles.p || ctx->cls_n_mixed.empty()) return fail(ctx, PNL_ERR_STATE, "no tile plan yet");
+    const int64_t n = std::min<int64_t>(ntiles, ctx->n_settled);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (codes && n > 0) HIPCHK(ctx, hipMemcpy(codes, ctx->b_codes.p, (size_t)n*512*sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (lists && n > 0) {
+        if (!ctx->b_lists.p) return fail(ctx, PNL_ERR_STATE, "the resident tile plan keeps no pair lists");
+        HIPCHK(ctx, hipMemcpy(lists, ctx->b_lists.p, (size_t)n*PNL_LIST_STRIDE*sizeof(uint16_t), hipMemcpyDeviceToHost));
+    }
+    return ctx->b_lists.p ? ctx->n_settled : 0;
 }
 
 int pnl_get_fold_plan(pnl_context *ctx, int32_t *images, int64_t nimages, int8_t *tile_stage, int8_t *tile_order, int64_t ntiles) {

@@ -5,7 +5,10 @@ branch targets and the padding behind the last instruction) and its resources (V
 object's notes).  A kernel whose stream differs only in the literal added to s_getpc_b64 (the distance to a table in .rodata,
 which depends on what else the code object holds) is reported as "pc-relative" with the number of such sites.  Prints what moved,
 what vanished, what is new, what differs, and the digest of every unit's .text.
-usage: unit_kernels.py OLD_BUILD_DIR NEW_BUILD_DIR [-v]     (no GPU needed; -v lists every kernel, not only the differences)"""
+usage: unit_kernels.py OLD_BUILD_DIR NEW_BUILD_DIR [-v] [--old-name REGEX REPL]
+(no GPU needed; -v lists every kernel, not only the differences; --old-name rewrites the demangled names of the OLD build before the
+two are matched, for a kernel that has gained a template parameter:
+--old-name '(k_tile_distant<[^>]*)>' '\\1, false>' compares every old instantiation with the new one whose added flag is off)"""
 import hashlib, os, re, subprocess, sys, tempfile
 LLVM = '/opt/rocm/lib/llvm/bin'
 
@@ -67,12 +70,14 @@ def build(d, tmp):
     return units
 
 
-def by_symbol(units):
+def by_symbol(units, rename=None):
     """keyed by the demangled name without any `(anonymous namespace)::`, in the kernel's name and in its parameter types: a kernel
     that moves into or out of an unnamed namespace stays the same kernel"""
     syms = sorted({k for ks, _ in units.values() for k in ks})
     names = subprocess.run(['c++filt'], input='\n'.join(syms), capture_output=True, text=True).stdout.split('\n')
     plain = {k: d.replace('(anonymous namespace)::', '') for k, d in zip(syms, names)}
+    if rename:
+        plain = {k: re.sub(rename[0], rename[1], d, count=1) for k, d in plain.items()}
     sym = {}
     for u, (ks, _) in units.items():
         for k, v in ks.items():
@@ -82,14 +87,19 @@ def by_symbol(units):
 
 def main():
     verbose = '-v' in sys.argv
-    old_dir, new_dir = [a for a in sys.argv[1:] if a != '-v']
+    args, rename = [a for a in sys.argv[1:] if a != '-v'], None
+    if '--old-name' in args:
+        i = args.index('--old-name')
+        rename = (args[i+1], args[i+2])
+        del args[i:i+3]
+    old_dir, new_dir = args
     with tempfile.TemporaryDirectory() as t1, tempfile.TemporaryDirectory() as t2:
         old, new = build(old_dir, t1), build(new_dir, t2)
     print('== .text of the units (digest old -> new)')
     for u in sorted(set(old) | set(new)):
         a, b = old.get(u, ({}, '-')), new.get(u, ({}, '-'))
         print('{:14s} {:4d} -> {:4d} kernels   {} -> {}   {}'.format(u, len(a[0]), len(b[0]), a[1], b[1], 'identical' if a[1] == b[1] else 'CHANGED'))
-    so, sn = by_symbol(old), by_symbol(new)
+    so, sn = by_symbol(old, rename), by_symbol(new)
     short = {k: re.sub(r'^void ', '', k)[:110] for k in set(so) | set(sn)}
     count = {'same': 0, 'moved': 0, 'copies dropped': 0, 'vanished': 0, 'new': 0, 'pc-relative': 0, 'differs': 0}
     print('== kernels (symbol: units old -> units new)')
