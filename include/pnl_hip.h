@@ -692,6 +692,35 @@ int pnl_lincomb(pnl_context *ctx, int m, const double *const *A_dev, int64_t ldA
 int pnl_gemv_multi(pnl_context *ctx, int m, const double *const *A_dev, int64_t ldA, int nrows, int ncols, const double *coeffs_host,
                    const double *x_dev, double alpha, double beta, const double *b_dev, double *y_dev);
 
+/* ---- products with a block of vectors (csrc/pnl_block.hip): LinearOperator.matvec_multi / dotMV / A * X for a 2-D X
+ *      (base/PyNucleus_base/LinearOperator_{SCALAR}.pxi:23-26, 64-76, 120-121). --------------------------------------------------------
+ * Vectors are stored one per row, the layout of pnl_potrs / pnl_getrs: vector v is X_dev[v*ldx .. v*ldx + ncols), its result
+ * Y_dev[v*ldy .. v*ldy + nrows).  Any nvec >= 1; the vectors are processed in groups of at most 16, one pass over the matrix per group
+ * (nvec = 17 costs two passes).  Both calls are asynchronous on the context's stream and allocate nothing per call beyond growing a
+ * scratch buffer of the context once.
+ *
+ * pnl_gemv_block: Y[v][r] = alpha * sum_c A[r][c] X[v][c] + beta * B[v][r], v < nvec, r < nrows; A row-major nrows x ncols (square or
+ * rectangular), ldA >= ncols.  The contraction runs on v_mfma_f64_16x16x4_f64, a group of vectors being the 16-wide B operand (vectors
+ * that do not exist are zero operands whose results are not stored).  No floating-point atomics: every reduction has a fixed shape
+ * that depends on (nrows, ncols, ldA, alignment) only (more than 2048 columns are split over workgroups, whose partial sums go
+ * through a scratch buffer of the context and are added in ascending order), so the same input gives the same bits, and the bits of
+ * Y[v] depend neither on nvec nor on the position v nor on the other vectors.  beta == 0: B_dev may be NULL and is not read, Y is
+ * overwritten (a NaN in Y before the call does not survive).  B_dev may equal Y_dev (with ldb == ldy); X must not overlap Y.
+ * Unaligned bases, odd ldA and ld > n are correct (16-byte loads where the addresses allow, scalar loads otherwise); the padding
+ * columns of A, X, B and Y are neither read into a sum nor written.  A symmetric matrix is read in full (no half-read as
+ * pnl_gemv's symmetric_half = 2).  PNL_ERR_INVALID, before any launch, for a null ctx, A, X or Y; nvec, nrows or ncols < 1;
+ * ldA < ncols, ldx < ncols or ldy < nrows; beta != 0 with a null B or ldb < nrows; X_dev == Y_dev. */
+int pnl_gemv_block(pnl_context *ctx, const double *A_dev, int64_t ldA, int nrows, int ncols, int nvec, const double *X_dev, int64_t ldx,
+                   double alpha, double beta, const double *B_dev, int64_t ldb, double *Y_dev, int64_t ldy);
+/* The pattern resident in the context (pnl_upload_sparsity*), as pnl_spmv: CSR (diag_dev NULL) Y[v] = A X[v]; SSS (diag_dev given, data =
+ * strict lower triangle) Y[v] = (L + L^T + D) X[v].  State and validation as pnl_spmv (PNL_ERR_STATE without a pattern, null data with
+ * nnz > 0 invalid); nvec < 1, ldx or ldy below the number of DoFs and X_dev == Y_dev are invalid too.  Every (index, value) pair of the
+ * matrix is loaded once per group of at most 16 vectors; the group is transposed once into a scratch buffer of the context.  CSR uses
+ * no atomics and its bits are independent of nvec and of the position; SSS adds the mirrored entries with atomics (Y is zeroed by the
+ * call): its contract is the value, not the bits. */
+int pnl_spmv_block(pnl_context *ctx, const double *data_dev, const double *diag_dev, int nvec, const double *X_dev, int64_t ldx,
+                   double *Y_dev, int64_t ldy);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,7 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest',
            'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs',
            'pnl_csr_cg_jacobi', 'pnl_fe_space_create', 'pnl_fe_space_destroy', 'pnl_assemble_nonlinearity', 'pnl_imex_create',
-           'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi']
+           'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi', 'pnl_gemv_block', 'pnl_spmv_block']
 
 PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
 PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
@@ -212,6 +212,8 @@ def load():
     L.pnl_imex_sweep.argtypes = [vp, vp, vp, vp, vp]
     L.pnl_lincomb.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, i64]
     L.pnl_gemv_multi.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, dbl, dbl, vp, vp]
+    L.pnl_gemv_block.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, dbl, dbl, vp, i64, vp, i64]
+    L.pnl_spmv_block.argtypes = [vp, vp, vp, i32, vp, i64, vp, i64]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
     L.pnl_upload_sparsity_device.argtypes = [vp, i32, vp, vp]
     L.pnl_set_classes.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -671,6 +673,18 @@ class Context:
         arr, c = self._block_list(A_ptrs, coeffs)
         self.check(self.L.pnl_gemv_multi(self.h, len(A_ptrs), arr, int(ldA), int(nrows), int(ncols), c.ctypes.data, C.c_void_p(x_ptr), float(alpha),
                                          float(beta), C.c_void_p(b_ptr) if b_ptr else None, C.c_void_p(y_ptr)))
+
+    # -- products with a block of vectors (pnl_block.hip): vector v is X[v*ldx .. v*ldx + ncols) -------
+    def gemv_block(self, A_ptr, ldA, nrows, ncols, nvec, X_ptr, ldx, alpha, beta, B_ptr, ldb, Y_ptr, ldy):
+        """Y[v] = alpha A X[v] + beta B[v] for v < nvec, one pass over A per group of 16 vectors"""
+        self.check(self.L.pnl_gemv_block(self.h, C.c_void_p(A_ptr) if A_ptr else None, int(ldA), int(nrows), int(ncols), int(nvec),
+                                         C.c_void_p(X_ptr) if X_ptr else None, int(ldx), float(alpha), float(beta),
+                                         C.c_void_p(B_ptr) if B_ptr else None, int(ldb), C.c_void_p(Y_ptr) if Y_ptr else None, int(ldy)))
+
+    def spmv_block(self, data_ptr, diag_ptr, nvec, X_ptr, ldx, Y_ptr, ldy):
+        """Y[v] = A X[v] for the uploaded pattern (CSR: diag_ptr 0; SSS: lower triangle + diagonal)"""
+        self.check(self.L.pnl_spmv_block(self.h, C.c_void_p(data_ptr) if data_ptr else None, C.c_void_p(diag_ptr) if diag_ptr else None, int(nvec),
+                                         C.c_void_p(X_ptr) if X_ptr else None, int(ldx), C.c_void_p(Y_ptr) if Y_ptr else None, int(ldy)))
 
     def csr_matvec(self, nrows, indptr_ptr, indices_ptr, data_ptr, x_ptr, alpha, beta, y_ptr):
         self.check(self.L.pnl_csr_matvec(self.h, int(nrows), C.c_void_p(indptr_ptr), C.c_void_p(indices_ptr), C.c_void_p(data_ptr),

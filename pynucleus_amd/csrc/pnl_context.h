@@ -150,6 +150,7 @@ struct pnl_context {
     DevBuf b_rowmap, b_rowdof, b_colmap, b_coldof;
     DevBuf b_cholinfo;                // pnl_potrf (pnl_direct.hip): the word that takes the first pivot that is not positive
     DevBuf b_luwork, b_lutmp;         // pnl_getrf (pnl_direct.hip): info word, ticket, pivot rows, partial maxima; pnl_getrs: the permuted right-hand sides
+    DevBuf b_blk_part, b_blk_xt;      // pnl_block.hip: partial sums of the column chunks [chunk][16][nrows]; the transposed group of vectors [n][NV]
     std::vector<int32_t> slab_rowdofs, slab_coldofs;
     int slab_rows = 0, slab_cols = 0;
     std::vector<DevKernel> kcls_host;

@@ -14,6 +14,7 @@ and pair lists, so every rank computes them for all ranks without a set-up Allto
 import ctypes as C
 import numpy as np
 import torch
+from .linear_operators import blockProducts
 
 
 def subtree_owners(flat, size):
@@ -42,8 +43,9 @@ def subtree_owners(flat, size):
     return owner, cut
 
 
-class DistributedH2Matrix_localData:
-    """see the module docstring; built by nonlocalBuilder.getH2() under a communicator with params['localFarFieldIndexing']"""
+class DistributedH2Matrix_localData(blockProducts):
+    """see the module docstring; built by nonlocalBuilder.getH2() under a communicator with params['localFarFieldIndexing'].
+    ``matvec_multi`` / ``dotMV`` loop ``matvec`` over the vectors (blockProducts): a uniform API with the bits of ``matvec``."""
 
     def __init__(self, builder, root, Pnear, Pfar, m, far_class=None, group=None):
         import torch.distributed as dist
@@ -198,7 +200,9 @@ class DistributedH2Matrix_localData:
     def matvec(self, x, y=None):
         """convenience for callers that hold the whole vector on every rank: restrict, multiply, all-gather the owned parts"""
         import torch.distributed as dist
-        from .linear_operators import _as_dev
+        from .linear_operators import _as_dev, _ndim
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         xd = _as_dev(x, self.device)
         yo = self.matvec_owned(xd[self._owned_t])
         counts = [int((self.dof_owner == q).sum()) for q in range(self.size)]

@@ -8,6 +8,7 @@ matrices (pure geometry, a few hundred M x M blocks) are built here.
 """
 import ctypes as C
 import numpy as np
+from .linear_operators import blockProducts
 
 
 def interpolationOrder(kernel, mesh, target_order):
@@ -131,8 +132,9 @@ class h2Plan:
         return P
 
 
-class H2Matrix:
-    """y = Anear x + (far field through the cluster tree); clusterMethodCy.pyx:2240-2295"""
+class H2Matrix(blockProducts):
+    """y = Anear x + (far field through the cluster tree); clusterMethodCy.pyx:2240-2295.  ``matvec_multi`` / ``dotMV`` loop
+    ``matvec`` over the vectors (blockProducts): a uniform API with the bits of ``matvec``; a multi-vector far field is a follow-up."""
 
     def __init__(self, Anear, plan, ctx, root, Pfar):
         self.Anear, self.plan, self.ctx = Anear, plan, ctx
@@ -149,7 +151,9 @@ class H2Matrix:
 
     def matvec(self, x, y=None):
         import torch
-        from .linear_operators import _as_dev
+        from .linear_operators import _as_dev, _ndim
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         self._ensure_setup()
         xd = _as_dev(x, self.device)
         yd = self.Anear.matvec(xd)

@@ -16,7 +16,76 @@ def _as_dev(x, device):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float64)).to(device)
 
 
-class Dense_LinearOperator:
+def _ndim(x):
+    return x.dim() if isinstance(x, torch.Tensor) else np.ndim(x)
+
+
+def _as_block(X, device):
+    """a block of vectors, one per row, as a float64 tensor on ``device`` with unit inner stride: a strided torch view that has one is
+    passed on as it is (its row stride becomes the leading dimension), anything else is copied"""
+    if isinstance(X, torch.Tensor):
+        Xd = X.to(device=device, dtype=torch.float64)
+    else:
+        Xd = torch.from_numpy(np.ascontiguousarray(np.asarray(X), dtype=np.float64)).to(device)
+    assert Xd.dim() == 2, 'a block of vectors is 2-D'
+    if Xd.stride(1) != 1 or (Xd.shape[0] > 1 and Xd.stride(0) < Xd.shape[1]):
+        Xd = Xd.contiguous()
+    return Xd
+
+
+def _block_out(X, Yd, Y):
+    """torch in / torch out, else numpy; ``Y`` is filled and returned if given"""
+    if isinstance(X, torch.Tensor):
+        if Y is not None:
+            Y.copy_(Yd)
+            return Y
+        return Yd
+    out = Yd.cpu().numpy() if isinstance(Yd, torch.Tensor) else Yd
+    if Y is not None:
+        Y[...] = out
+        return Y
+    return out
+
+
+def matvec_multi_loop(op, X, Y=None):
+    """Y[v] = op.matvec(X[v]) for the rows v of X: the block product of the operators that have no kernel for it.  One product per
+    vector, so every row carries the bits of the single ``matvec``."""
+    assert _ndim(X) == 2 and X.shape[0] >= 1 and X.shape[1] == op.num_columns, (tuple(X.shape), op.num_columns)
+    rows = [op.matvec(X[v]) for v in range(X.shape[0])]
+    if isinstance(rows[0], torch.Tensor):
+        return _block_out(X, torch.stack(rows), Y)
+    return _block_out(X, np.stack([np.asarray(r) for r in rows]), Y)
+
+
+class blockProducts:
+    """the products with a 2-D argument that every operator has (LinearOperator_{SCALAR}.pxi:23-26, 64-76, 120-121):
+    ``matvec_multi(X, Y=None)`` for X [k, num_columns], rows are vectors (the layout ``solve`` takes), returns [k, num_rows];
+    ``dotMV(X)`` with the reference's shape rule; ``matvec`` / ``dot`` / ``*`` with a 2-D argument go to ``dotMV``.  A class without
+    a block kernel keeps this ``matvec_multi``, a loop of its ``matvec`` over the vectors."""
+
+    def matvec_multi(self, X, Y=None):
+        return matvec_multi_loop(self, X, Y)
+
+    def dotMV(self, X):
+        """X.shape[0] == num_columns: the columns are vectors, (num_rows, k) is returned (this rule wins for a square X); else
+        X.shape[1] == num_columns: the rows are vectors, (k, num_rows) is returned"""
+        if _ndim(X) != 2:
+            raise ValueError('dotMV takes a 2-D argument')
+        if not isinstance(X, torch.Tensor):
+            X = np.asarray(X)
+        if X.shape[0] == self.num_columns:
+            Yt = self.matvec_multi(X.t() if isinstance(X, torch.Tensor) else np.ascontiguousarray(X.T))
+            return Yt.t().contiguous() if isinstance(Yt, torch.Tensor) else np.ascontiguousarray(Yt.T)
+        if X.shape[1] == self.num_columns:
+            return self.matvec_multi(X)
+        raise ValueError('dotMV: shape {} does not fit {} columns'.format(tuple(X.shape), self.num_columns))
+
+    def _dot_2d(self, X, Y=None):
+        out = self.dotMV(X)
+        return out if Y is None else _block_out(X, out, Y)
+
+
+class Dense_LinearOperator(blockProducts):
     def __init__(self, A_dev, ctx, info=None, symmetric=False):
         # row-major with a leading dimension >= number of columns (the builder pads rows to 64-byte lines)
         assert A_dev.dtype == torch.float64 and A_dev.stride(1) == 1 and A_dev.stride(0) >= A_dev.shape[1]
@@ -60,7 +129,9 @@ class Dense_LinearOperator:
         return torch.diagonal(self.A).cpu().numpy().copy()
 
     def matvec(self, x, y=None):
-        """y = A x through the hand-written GEMV; accepts numpy or torch vectors"""
+        """y = A x through the hand-written GEMV; accepts numpy or torch vectors (a 2-D argument: dotMV)"""
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         dev = self.A.device
         xd = _as_dev(x, dev)
         assert xd.shape[0] == self.num_columns
@@ -82,6 +153,20 @@ class Dense_LinearOperator:
             y[:] = out
             return y
         return out
+
+    def matvec_multi(self, X, Y=None):
+        """Y[v] = A X[v] for the rows of X in one pass over the block per 16 vectors (pnl_gemv_block: fp64 MFMA, no atomics, the bits of
+        a row do not depend on the other rows).  A symmetric operator is read in full here."""
+        dev = self.A.device
+        Xd = _as_block(X, dev)
+        k = Xd.shape[0]
+        assert k >= 1 and Xd.shape[1] == self.num_columns, (tuple(Xd.shape), self.num_columns)
+        Yd = torch.empty((k, self.num_rows), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self.ctx.gemv_block(self.A.data_ptr(), self.A.stride(0), self.num_rows, self.num_columns, k, Xd.data_ptr(),
+                            max(int(Xd.stride(0)), self.num_columns), 1., 0., None, 0, Yd.data_ptr(), self.num_rows)
+        self.ctx.synchronize()
+        return _block_out(X, Yd, Y)
 
     def __mul__(self, x):
         return self.matvec(x)
@@ -139,6 +224,8 @@ class DistributedDense_LinearOperator(Dense_LinearOperator):
         self.group = comm_group
 
     def matvec(self, x, y=None):
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         import torch.distributed as dist
         dev = self.A.device
         xd = _as_dev(x, dev)
@@ -152,6 +239,11 @@ class DistributedDense_LinearOperator(Dense_LinearOperator):
             return yd
         return yd.cpu().numpy()
 
+    def matvec_multi(self, X, Y=None):
+        """one distributed ``matvec`` per vector (not the local-only block product of the base class): the API of the other operators
+        with the bits of ``matvec``; a block all-reduce is a follow-up"""
+        return matvec_multi_loop(self, X, Y)
+
     def reduce(self):
         """all-reduce the matrix itself (what the reference's getDense does, NA:1449-1450)"""
         import torch.distributed as dist
@@ -160,11 +252,12 @@ class DistributedDense_LinearOperator(Dense_LinearOperator):
         return Dense_LinearOperator(self.A, self.ctx, self.info)
 
 
-class DistributedSlab_LinearOperator:
+class DistributedSlab_LinearOperator(blockProducts):
     """Row-owned distributed dense operator: every rank keeps the one-sided slab of its block rows,
     rows x (N - col0) doubles <= N^2 / P, and its partial per-cell diagonal blocks; matvec = local slab products + ONE
     all-reduce of the N-vector (DistributedH2Matrix_globalData.matvec, clusterMethodCy.pyx:3127-3154).  No collective in
-    the assembly."""
+    the assembly.  ``matvec_multi`` / ``dotMV`` loop ``matvec`` over the vectors (blockProducts): a uniform API with the bits of
+    ``matvec``."""
 
     def __init__(self, slab, dblocks, rowdofs, coldofs, num_dofs, ctx, group, info=None):
         self.slab, self.dblocks = slab, dblocks
@@ -216,6 +309,8 @@ class DistributedSlab_LinearOperator:
         return yd
 
     def matvec(self, x, y=None):
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         import torch.distributed as dist
         xd = _as_dev(x, self.device).contiguous()
         if dist.is_initialized():
@@ -275,7 +370,7 @@ class DistributedSlab_LinearOperator:
                                                                                         self.rowdofs.shape[0], self.coldofs.shape[0], self.device)
 
 
-class CSR_LinearOperator:
+class CSR_LinearOperator(blockProducts):
     """Near-field matrix in HBM, CSR layout (base/PyNucleus_base/CSR_LinearOperator_{SCALAR}.pxi:20-60: ``indptr``,
     ``indices``, ``data``).  The pattern is fixed by getSparseNearField; ``data`` is filled by
     pnl_assemble_pairs_masked / pnl_assemble_boundary_masked with the reference's addToEntry semantics."""
@@ -383,6 +478,8 @@ class CSR_LinearOperator:
         return d
 
     def matvec(self, x, y=None):
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         self._bind()
         xd = _as_dev(x, self.device)
         assert xd.shape[0] == self.num_columns
@@ -398,6 +495,20 @@ class CSR_LinearOperator:
             y[:] = out
             return y
         return out
+
+    def matvec_multi(self, X, Y=None):
+        """Y[v] = A X[v] for the rows of X; every stored entry is loaded once per 16 vectors (pnl_spmv_block; SSS: the mirrored entries
+        through atomics, as ``matvec``)"""
+        self._bind()
+        Xd = _as_block(X, self.device)
+        k = Xd.shape[0]
+        assert k >= 1 and Xd.shape[1] == self.num_columns, (tuple(Xd.shape), self.num_columns)
+        Yd = torch.empty((k, self.num_rows), dtype=torch.float64, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        d, g = self._ptrs()
+        self.ctx.spmv_block(d, g, k, Xd.data_ptr(), max(int(Xd.stride(0)), self.num_columns), Yd.data_ptr(), self.num_rows)
+        self.ctx.synchronize()
+        return _block_out(X, Yd, Y)
 
     def __mul__(self, x):
         return self.matvec(x)
@@ -427,7 +538,7 @@ class SSS_LinearOperator(CSR_LinearOperator):
         return L+L.T+np.diag(self.diagonal)
 
 
-class diagonalOperator:
+class diagonalOperator(blockProducts):
     """base/PyNucleus_base/linear_operators.pyx diagonalOperator: ``data`` = the diagonal; matvec scales"""
 
     def __init__(self, diag):
@@ -440,22 +551,35 @@ class diagonalOperator:
         return self.data
 
     def matvec(self, x, y=None):
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         out = self.data*np.asarray(x)
         if y is not None:
             y[:] = out
             return y
         return out
 
+    def matvec_multi(self, X, Y=None):
+        X = np.asarray(X)
+        assert X.ndim == 2 and X.shape[1] == self.num_columns, (X.shape, self.num_columns)
+        out = self.data[None, :]*X
+        if Y is not None:
+            Y[...] = out
+            return Y
+        return out
+
     __mul__ = matvec
+    dot = matvec
 
     def toarray(self):
         return np.diag(self.data)
 
 
-class DistributedSparse_LinearOperator:
+class DistributedSparse_LinearOperator(blockProducts):
     """Row-sharded near field: every rank holds the CSR blocks of its cluster pairs; A = sum over ranks.  matvec follows
     the reference's DistributedH2Matrix_globalData (clusterMethodCy.pyx:3127-3154): Bcast(x), local product, Allreduce(y)
-    -- an N-vector over RCCL (or gloo), never the matrix."""
+    -- an N-vector over RCCL (or gloo), never the matrix.  ``matvec_multi`` / ``dotMV`` loop ``matvec`` over the vectors
+    (blockProducts): a uniform API with the bits of ``matvec``."""
 
     def __init__(self, local, comm_group=None, far=None, Pfar=None):
         self.local = local
@@ -478,6 +602,8 @@ class DistributedSparse_LinearOperator:
         return d.cpu().numpy()
 
     def matvec(self, x, y=None):
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         import torch.distributed as dist
         dev = self.local.device
         xd = _as_dev(x, dev)
@@ -552,7 +678,7 @@ def _is_pending(op):
     return callable(op) and not hasattr(op, 'matvec')
 
 
-class interpolationOperator:
+class interpolationOperator(blockProducts):
     """A(val) = sum_k c_k(val) A_k for operators A_k at the interpolation nodes of one interval [left, right]
     (base/PyNucleus_base/linear_operators.pyx:1261-1391).  ``set(val, derivative)`` computes the weights c = the Lagrange basis on
     ``nodes`` (or its first / second derivative) at val on the host; nothing is assembled or combined by it.
@@ -657,7 +783,37 @@ class interpolationOperator:
             yd = float(c)*t if yd is None else yd.add_(t, alpha=float(c))
         return yd
 
+    def matvec_multi(self, X, Y=None):
+        """Y[v] = (sum_j c_j A_j) X[v].  Dense node operators: m calls of pnl_gemv_block in ascending j, Y = c_0 A_0 X, then
+        Y = c_j A_j X + Y, so the m blocks are read once per 16 vectors.  Others: their own matvec_multi, combined in the same order."""
+        ops = self._ready()
+        blocks = self._fused()
+        if blocks is not None:
+            ctx, dev = ops[0].ctx, blocks[0].device
+            Xd = _as_block(X, dev)
+            k = Xd.shape[0]
+            nrows, ncols = self.shape
+            assert k >= 1 and Xd.shape[1] == ncols, (tuple(Xd.shape), ncols)
+            Yd = torch.empty((k, nrows), dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            for j, A in enumerate(blocks):
+                ctx.gemv_block(A.data_ptr(), A.stride(0), nrows, ncols, k, Xd.data_ptr(), max(int(Xd.stride(0)), ncols), float(self.coeffs[j]),
+                               0. if j == 0 else 1., None if j == 0 else Yd.data_ptr(), nrows, Yd.data_ptr(), nrows)
+            ctx.synchronize()
+            return _block_out(X, Yd, Y)
+        dev = self._device()
+        Xd = _as_block(X, dev)
+        arg = Xd if Xd.is_cuda else Xd.numpy()
+        Yd = None
+        for c, op in zip(self.coeffs, ops):
+            t = op.matvec_multi(arg)
+            t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t, dtype=np.float64)).to(dev)
+            Yd = float(c)*t if Yd is None else Yd.add_(t, alpha=float(c))
+        return _block_out(X, Yd, Y)
+
     def matvec(self, x, y=None):
+        if _ndim(x) == 2:
+            return self._dot_2d(x, y)
         self._ready()
         xd = _as_dev(x, self._device())
         assert xd.shape[0] == self.shape[1]
@@ -720,7 +876,7 @@ class interpolationOperator:
         return '<{}x{} {} with {} interpolation nodes>'.format(self.shape[0], self.shape[1], type(self).__name__, self.numInterpolationNodes)
 
 
-class multiIntervalInterpolationOperator:
+class multiIntervalInterpolationOperator(blockProducts):
     """interpolation operators on adjacent intervals; ``set(val)`` selects the first interval that contains val and sets its weights,
     everything else acts on the selected one (base/PyNucleus_base/linear_operators.pyx:1393-1504).  The operators of an interval are
     built when ``set`` first selects it."""
@@ -762,6 +918,12 @@ class multiIntervalInterpolationOperator:
 
     def matvec(self, x, y=None):
         return self.getSelectedOp().matvec(x, y)
+
+    def matvec_multi(self, X, Y=None):
+        return self.getSelectedOp().matvec_multi(X, Y)
+
+    def dotMV(self, X):
+        return self.getSelectedOp().dotMV(X)
 
     def __mul__(self, x):
         return self.matvec(x)

@@ -1,0 +1,125 @@
+"""Micro-benchmark of the block products against loops of the single-vector kernels, in one process.
+
+  pnl_gemv_block for nvec in {1, 2, 4, 8, 16, 32} against the same number of pnl_gemv mode-0 calls on a random N x N block with the
+  builder's row padding; 8 N^2 / t per pass over the block in TB/s (k_gemv: 6.05 TB/s at N = 48,769) and the ratio loop / block;
+  pnl_spmv_block against repeated pnl_spmv on the near-field pattern of the H2 configuration of bench.py (disc, s = 0.75, eta = 3).
+
+Device events around a window of >= 0.2 s after three warm-up calls of every shape; block and loop alternate, three rounds, the
+median is reported.  Prints one JSON line.
+usage: block_probe.py [--n N ...] [--nvec K ...] [--h2-noref R | --no-spmv]      (defaults: --n 12097 48769 --h2-noref 7)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from pynucleus_amd import _lib
+
+NVECS = (1, 2, 4, 8, 16, 32)
+
+
+def timed(ctx, fn, min_s=0.2):
+    """seconds per call of fn() from device events over a window of at least min_s"""
+    for _ in range(3):
+        fn()
+    ctx.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    reps = 1
+    while True:
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        t = 1e-3*e0.elapsed_time(e1)
+        if t >= min_s or reps >= 4096:
+            return t/reps
+        reps = max(reps*2, int(reps*min_s/max(t, 1e-6))+1)
+
+
+def median_pair(ctx, block, loop, rounds=3):
+    tb, tl = [], []
+    for _ in range(rounds):
+        tb.append(timed(ctx, block))
+        tl.append(timed(ctx, loop))
+    return statistics.median(tb), statistics.median(tl)
+
+
+def dense(ctx, N, nvecs=NVECS):
+    ld = (N+7) & ~7
+    g = torch.Generator(device='cuda'); g.manual_seed(1)
+    A = torch.empty((N, ld), dtype=torch.float64, device='cuda')
+    for i in range(0, N, 4096):
+        A[i:i+4096] = torch.rand((min(4096, N-i), ld), dtype=torch.float64, device='cuda', generator=g)-0.5
+    kmax = max(nvecs)
+    X = torch.rand((kmax, N), dtype=torch.float64, device='cuda', generator=g)
+    Y = torch.empty((kmax, N), dtype=torch.float64, device='cuda')
+    Y1 = torch.empty_like(Y)
+    out = dict(N=N, ld=ld, bytes_per_pass=8*N*N, nvec={})
+    for k in nvecs:
+        def block():
+            ctx.gemv_block(A.data_ptr(), ld, N, N, k, X.data_ptr(), N, 1., 0., None, 0, Y.data_ptr(), N)
+
+        def loop():
+            for v in range(k):
+                ctx.gemv(A.data_ptr(), ld, N, X[v].data_ptr(), Y1[v].data_ptr(), 0)
+        tb, tl = median_pair(ctx, block, loop)
+        block(); loop(); ctx.synchronize()
+        diff = float((Y[:k]-Y1[:k]).abs().max()/Y1[:k].abs().max())
+        passes = (k+15)//16
+        out['nvec'][k] = dict(block_ms=1e3*tb, loop_ms=1e3*tl, loop_over_block=tl/tb, block_TBps_per_pass=passes*8*N*N/tb/1e12,
+                              loop_TBps_per_pass=k*8*N*N/tl/1e12, max_rel_diff=diff)
+    del A, X, Y, Y1
+    torch.cuda.empty_cache()
+    return out
+
+
+def sparse(noref):
+    from pynucleus_amd import disc, P1_DoFMap, PHYSICAL, getFractionalKernel
+    from pynucleus_amd.builder import nonlocalBuilder
+    dm = P1_DoFMap(disc(noref), PHYSICAL)
+    b = nonlocalBuilder(dm, getFractionalKernel(2, 0.75), {'target_order': 0.5, 'eta': 3.}, zeroExterior=True)
+    near = b.getH2().Anear
+    ctx, N = near.ctx, near.num_rows
+    near._bind()
+    d, gdiag = near._ptrs()
+    g = torch.Generator(device='cuda'); g.manual_seed(2)
+    kmax = 16
+    X = torch.rand((kmax, N), dtype=torch.float64, device='cuda', generator=g)
+    Y = torch.empty((kmax, N), dtype=torch.float64, device='cuda')
+    Y1 = torch.empty_like(Y)
+    out = dict(N=N, nnz=int(near.nnz), format=type(near).__name__, nvec={})
+    for k in (1, 2, 4, 8, 16):
+        def block():
+            ctx.spmv_block(d, gdiag, k, X.data_ptr(), N, Y.data_ptr(), N)
+
+        def loop():
+            for v in range(k):
+                ctx.spmv(d, gdiag, X[v].data_ptr(), Y1[v].data_ptr())
+        tb, tl = median_pair(ctx, block, loop)
+        block(); loop(); ctx.synchronize()
+        out['nvec'][k] = dict(block_ms=1e3*tb, loop_ms=1e3*tl, loop_over_block=tl/tb,
+                              max_rel_diff=float((Y[:k]-Y1[:k]).abs().max()/Y1[:k].abs().max()))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--n', type=int, nargs='*', default=[12097, 48769])
+    ap.add_argument('--nvec', type=int, nargs='*', default=list(NVECS))
+    ap.add_argument('--h2-noref', type=int, default=7)
+    ap.add_argument('--no-spmv', action='store_true')
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'block_probe.py needs a GPU'
+    ctx = _lib.Context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    res = dict(gemv_block=[dense(ctx, N, tuple(a.nvec)) for N in a.n])
+    ctx.close()
+    if not a.no_spmv:
+        res['spmv_block'] = sparse(a.h2_noref)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
