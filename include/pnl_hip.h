@@ -90,9 +90,11 @@ enum pnl_counter {
     PNL_C_SETTLED_TILES = 134,         /* mixed tiles the assembly took through the settled instantiation of the tile kernel  */
     PNL_C_CODE_BUILDS = 135,           /* times the context has computed the pair codes of settled tiles (once per tile plan)  */
     PNL_C_WORKLIST_LENGTH = 136,       /* entries the tile kernels handed to the device work lists, summed over the passes      */
-    PNL_C_SETTLED_LIST_TILES = 137     /* settled tiles the assembly took with the pair lists of the plan (the others: by their codes) */
+    PNL_C_SETTLED_LIST_TILES = 137,    /* settled tiles the assembly took with the pair lists of the plan (the others: by their codes) */
+    PNL_C_UNIFORM_TILES_UNCHECKED = 138, /* P1 uniform tiles whose cells are all real and have a DoF: pair loop without the validity test */
+    PNL_C_UNIFORM_TILES_CHECKED = 139  /* P1 uniform tiles taken through the pair loop that tests every pair (all with PNL_UNI_CHECKED) */
 };
-#define PNL_NUM_COUNTERS 138
+#define PNL_NUM_COUNTERS 140
 
 /* Options (process-wide).  The library reads no environment variable on its assembly path; an option exists once it has been
  * set here (value NULL removes it).  A product build accepts
@@ -104,6 +106,8 @@ enum pnl_counter {
  *   "PNL_TILE_WGS"    at most this many workgroups per persistent tile kernel (tests: every workgroup then walks many tiles),
  *   "PNL_UNI_GENERIC" uniform-order tiles: the evaluator for arbitrary rules also where the rule has the orbit structure of the
  *                     symmetric 3- and 6-point rules (tests: both evaluators against each other),
+ *   "PNL_UNI_CHECKED" P1 uniform-order tiles: every tile through the pair loop that tests whether a pair exists, also the tiles whose
+ *                     cells are all real and have a DoF (tests: both loops against each other; read at every launch),
  *   "PNL_MIXED_GENERIC" mixed tiles: the evaluators for arbitrary rules also for the pairs whose rule has that orbit structure
  *                     (tests: both evaluators against each other),
  *   "PNL_MIXED_UNSETTLED" the tile plan settles no mixed tile: every mixed tile is classified pair by pair in every assembly

@@ -21,7 +21,7 @@ PNL_INTERIOR = 0
 PNL_BOUNDARY = 1
 PNL_FLAG_NO_MIRROR = 1
 PNL_FLAG_SYMMETRIC_FLUSH = 2
-PNL_NUM_COUNTERS = 138
+PNL_NUM_COUNTERS = 140
 
 # every symbol include/pnl_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_set_stream', 'pnl_synchronize',
@@ -564,7 +564,7 @@ class Context:
                     numBoundaryPairs=int(out[3]), numBoundaryIntegrations=int(out[4]), orders=hist, singular=sing,
                     uniformTilePairs=int(out[6]), uniformTilePairsByOrder={2+k: int(out[131+k]) for k in range(3)},
                     settledTiles=int(out[134]), codeBuilds=int(out[135]), workListLength=int(out[136]),
-                    settledListTiles=int(out[137]))
+                    settledListTiles=int(out[137]), uniformTilesUnchecked=int(out[138]), uniformTilesChecked=int(out[139]))
 
     def phase_ms(self):
         out = np.zeros(7, dtype=np.float32)

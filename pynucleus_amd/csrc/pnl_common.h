@@ -160,6 +160,7 @@ __device__ __noinline__ static double pnl_erfc(double x) { return erfc(x); }
 // e < 5e-6 for d2 in [1e-10, 8]), then y^QM (1 - e)^(-QM/4) with the series to e^2 (the next term is below 4e-16).  Two quarter-rate
 // single-precision operations and 8-9 double-precision ones instead of two v_rsq_f64 (17.7 cycles per wave each) with a cubic
 // correction each and the integer power: 88 instead of 126 cycles per kernel value for QM = 7 (tools/probes/valu_rate_probe.hip).
+// (kern_eval_c below holds a copy of this formula that takes c1 from its caller: a change here belongs there too)
 template <int QM>
 __device__ __forceinline__ double pnl_pow_quarter_odd(double d2) {
     static_assert(QM == 3 || QM == 5 || QM == 7, "exponents -3/4, -5/4, -7/4");
@@ -212,6 +213,7 @@ __device__ __forceinline__ double kern_eval(const DevKernel &k, double d2, const
         // 3/2 is no inline constant: as an immediate the compiler rebuilds it in a register pair for every evaluation (v_fmac wants
         // the addend in its destination: two v_mov per kernel value, 18 of the 270 instructions per pair of the 3-point tile loop);
         // an opaque loop-invariant register pair and the three-address form spelled out make it one v_fma
+        // (kern_eval_c below holds a copy of this formula that takes the 3/2 from its caller: a change here belongs there too)
         double c15 = 1.5, p;
         asm("" : "+v"(c15));
         const double r = __builtin_amdgcn_rsq(d2);
@@ -267,6 +269,40 @@ __device__ __forceinline__ double kern_eval(const DevKernel &k, double d2, const
         if (k.ktype == 7) return k.scale*pnl_exp_ranged(k.exponent*d2)/(-k.exponent*d2);
         return 2.*k.scale*pnl_exp_ranged(k.exponent*sqrt(d2))/(-k.exponent*sqrt(d2));
     }
+}
+
+// kern_eval makes its opaque constant (3/2 for KT == 2, QM/4 for KT == 13, 15, 17) where it is called: inside a loop of the caller the
+// register pair is copied once per trip.  A caller makes it once in front of its loops with kern_opaque_const<KT>() and evaluates with
+// kern_eval_c: the same operations on the same operands as kern_eval; the other KT take no constant and go to kern_eval.
+// The two formulas are COPIES of kern_eval<2> and pnl_pow_quarter_odd, not shared code: with kern_eval routed through one shared
+// function the instruction streams of 55 kernels of three units moved.  Keep the copies in step.
+template <int KT> constexpr bool kern_has_opaque_const() { return KT == 2 || KT == 13 || KT == 15 || KT == 17; }
+template <int KT>
+__device__ __forceinline__ double kern_opaque_const() {
+    double c = KT == 2 ? 1.5 : (kern_has_opaque_const<KT>() ? 0.25*(KT-10) : 0.);
+    if constexpr (kern_has_opaque_const<KT>()) asm("" : "+v"(c));
+    return c;
+}
+template <int KT>
+__device__ __forceinline__ double kern_eval_c(const DevKernel &k, double d2, const double *__restrict__ ltab, double c) {
+    if constexpr (KT == 2) {
+        double p;
+        const double r = __builtin_amdgcn_rsq(d2);
+        const double t = r*r;
+        const double e = __builtin_fma(-d2, t, 1.0);
+        const double g0 = r*t;
+        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "v"(e), "s"(1.875), "v"(c));
+        return __builtin_fma(g0, e*p, g0);
+    } else if constexpr (KT == 13 || KT == 15 || KT == 17) {
+        constexpr int QM = KT-10;
+        const double y = (double)__builtin_amdgcn_exp2f(-0.25f*__builtin_amdgcn_logf((float)d2));
+        const double y2 = y*y, y4 = y2*y2;
+        const double e = __builtin_fma(-d2, y4, 1.0);
+        const double P = QM == 3 ? y2*y : (QM == 5 ? y4*y : (y4*y2)*y);
+        double q;
+        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(q) : "v"(e), "s"(0.25*QM*(0.25*QM+1.)*0.5), "v"(c));
+        return __builtin_fma(P, e*q, P);
+    } else return kern_eval<KT>(k, d2, ltab);
 }
 
 template <int KT>

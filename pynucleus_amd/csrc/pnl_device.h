@@ -5,7 +5,11 @@
 
 #define PNL_NTHREADS 256
 #define PNL_MAXQ 120            // nonlocalOperator.pyx:107 MAX_PANEL
-#define PNL_NCOUNTERS 134
+#define PNL_NCOUNTERS 136
+// device counters behind those of the public enum pnl_counter ([0, 134) are its values): P1 uniform tiles taken without / with the
+// validity test of the pair loop (pnl_get_counters: PNL_C_UNIFORM_TILES_UNCHECKED / _CHECKED)
+#define PNL_DC_UNI_TILES_UNCHECKED 134
+#define PNL_DC_UNI_TILES_CHECKED 135
 #define PNL_WL_SLOTS 256          // work-list fill counters: one per order class / class pass of an assembly
 #define PNL_WL_BINS 128           // bins of the counting sort of a work list by order (pnl_wl_sort)
 #define PNL_POW_TAB_DOUBLES 384   // doubles of the tables of pnl_pow_tab (pnl_common.h) per exponent

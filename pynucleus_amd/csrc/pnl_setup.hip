@@ -699,7 +699,7 @@ const char *const k_product_options[] = {"PNL_WL_FRAC", "PNL_FH_NOTILES", "PNL_N
                                          "PNL_NO_OVERLAP", "PNL_NO_FORK",
                                          // tests: at most this many workgroups of a persistent tile kernel (every workgroup then walks
                                          // many tiles at test sizes: the pipelined tile loops against the oracle)
-                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED", "PNL_SETTLED_CODES",
+                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_UNI_CHECKED", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED", "PNL_SETTLED_CODES",
                                          // staged fold of the dense 2D P1 assembly: far bands (0: one fold behind all tiles), spare workgroup
                                          // slots per CU of the far uniform launches, where the boundary term starts (3 / 4)
                                          "PNL_FOLD_STAGES", "PNL_UNI_SPARE", "PNL_BND_MODE"};
@@ -1726,7 +1726,9 @@ int pnl_get_counters(pnl_context *ctx, int64_t *out, int n) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipMemcpy(tmp, ctx->b_counters.p, sizeof(tmp), hipMemcpyDeviceToHost));
     tmp[0] = ctx->run.visited_is_assembled ? tmp[1] : ctx->run.visited_pairs;
-    for (int i = 0; i < n && i < PNL_NCOUNTERS; i++) out[i] = (int64_t)tmp[i];
+    for (int i = 0; i < n && i < PNL_C_SETTLED_TILES; i++) out[i] = (int64_t)tmp[i];
+    if (n > PNL_C_UNIFORM_TILES_UNCHECKED) out[PNL_C_UNIFORM_TILES_UNCHECKED] = (int64_t)tmp[PNL_DC_UNI_TILES_UNCHECKED];
+    if (n > PNL_C_UNIFORM_TILES_CHECKED) out[PNL_C_UNIFORM_TILES_CHECKED] = (int64_t)tmp[PNL_DC_UNI_TILES_CHECKED];
     if (n > PNL_C_SETTLED_TILES) out[PNL_C_SETTLED_TILES] = ctx->run.settled_run;
     if (n > PNL_C_SETTLED_LIST_TILES) out[PNL_C_SETTLED_LIST_TILES] = ctx->run.lists_run;
     if (n > PNL_C_CODE_BUILDS) out[PNL_C_CODE_BUILDS] = ctx->code_builds;

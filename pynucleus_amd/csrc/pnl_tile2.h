@@ -224,6 +224,26 @@ __host__ __device__ constexpr size_t uniform_fixed_lds(int dpe, int np, int tile
 // STRUCT with six points: two orbits of three points, w phi_b(y_j) = A_o + B_o delta(b, j mod 3) in orbit o = j / 3: per row of the rule
 // the orbit sums s_0, s_1 of the kernel values give r = w_0 s_0 + w_1 s_1 and u_b = A_0 s_0 + A_1 s_1 + B_0 g_b + B_1 g_{3+b}
 // (14 instead of 24 instructions per row).
+// P1: what is constant over a tile or over the launch stays out of the pair loop.
+//   validity  a pair exists if both cells are real and one of them has a DoF.  stage() knows that per cell; the two staging waves reduce
+//             "all 64 cells are real and have a DoF" with a ballot and publish it beside the ticket.  In a tile whose 128 cells all pass
+//             a step of the pair loop skips the test with one scalar branch (no flags, no select of the volume, no ballot; 64 pairs per
+//             step); every other tile (padding behind the last cell, zero-volume padding cells, cells without a DoF) and every tile of a
+//             launch with bit 4 of flags (the option PNL_UNI_CHECKED) tests every pair.  One loop with the branch inside and not two
+//             copies of it under one branch per tile: with two copies the kernels need more registers than there are (scratch of the
+//             order-2 kernel of s = 1/2 20 -> 64 bytes, of the 6-point one 0 -> 20) for three instructions per pair less.
+//   constants the orbit constants of the structured rules and their products are formed in front of the loop and kept in scalar registers
+//             (uniform_f64), the opaque constant of kern_eval is made once (kern_opaque_const); the same operations on the same operands.
+//   offsets   s_slotb and s_sa hold byte offsets into the sub-block; the index of the b-cell does not travel, the lane that meets a
+//             cell last computes it behind the loop.
+__device__ __forceinline__ double uniform_f64(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+// a value loaded through the scalar cache, opaque from here on: the compiler keeps it in its scalar registers and does not load it again
+// inside a loop behind this point (it sinks loop-invariant scalar loads into the loop otherwise)
+__device__ __forceinline__ double scalar_f64(double v) { asm("" : "+s"(v)); return v; }
+#define PNL_UNI_FLAG_CHECKED 16                            // bit of k_tile_uniform's flags: every tile through the checked pair loop
+
 template <int DPE, int NP, int KT, bool STRUCT = false>
 __global__ void __launch_bounds__(256, (DPE == 3 && NP == 3) ? (KT == 0 ? PNL_U33K0_WAVES : (KT == 2 ? 4 : 2)) : ((DPE == 3 && NP == 6) ? 3 : 2))
 k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__restrict__ tile_cls, const DevKernel *__restrict__ kcls,
@@ -240,6 +260,8 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
     // step) instead of being read from and added to LDS for every pair; the LDS pipe of a CU was 80-90 % busy with 24 instructions per
     // pair (12 ds_add_f64, the reads of a b-cell of its own per lane), the VALU 63 %.  P2 (two half-waves of 32 cells) reads per lane.
     constexpr bool TRAVEL = (TILE == 64);
+    constexpr bool P1 = DPE == 3;                        // tile-constant work out of the pair loop (see above); P2 as it was
+    constexpr int OFFB = P1 ? (int)sizeof(double) : 1;   // unit of s_slotb / s_sa: bytes (P1) or entries of the sub-block
     const pnl_const_f64_ptr rule = (pnl_const_f64_ptr)(unsigned long long)rule_g;
 #ifndef PNL_DEBUG_ABLATE
     flags &= 1;                                          // the other bits skip work (debug builds only)
@@ -252,11 +274,12 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
     double *s_Ra = s_volb+TILE;                          // [TILE][NP] row sums of the a-cells, scaled
     double *s_Rb = s_Ra+TILE*RS;                         // [TILE][RS] column sums of the b-cells, scaled
     double *s_PP = s_Rb+TILE*RS;                         // [ND][NP] w phi_a phi_b at the points
-    int *s_slotb = (int*)(s_PP+ND*NP);                   // [TILE][DPE] column of the sub-block (trash column nUe)
-    int *s_sa = s_slotb+TILE*SS;                         // [TILE][SS] row offset in the sub-block (trash row nUe)
+    int *s_slotb = (int*)(s_PP+ND*NP);                   // [TILE][DPE] column of the sub-block (trash column nUe); P1: times 8, in bytes
+    int *s_sa = s_slotb+TILE*SS;                         // [TILE][SS] row offset in the sub-block (trash row nUe); P1: in bytes
     int *s_ha = s_sa+TILE*SS;                            // [TILE] has-a-DoF flags
     int *s_hb = s_ha+TILE;
-    int *s_next = s_hb+TILE;                             // [2] P1: the next tile of this workgroup (ticket), padding
+    int *s_next = s_hb+TILE;                             // [2] P1: the next tile of this workgroup (ticket); two 16-bit flags: every
+                                                         // a-cell (low half) / b-cell (high half) of the staged tile is real and has a DoF
     int *s_dof = s_next+(DPE == 3 ? 2 : 0);              // [2][2][nUe] global DoFs of both blocks (ping-pong over tiles);
     const bool dof_lists = SO.A2 == nullptr;             // not with the block-slot storage (uniform_fixed_lds)
     double *s_acc = (double*)(s_dof+(dof_lists ? 4*nUe : 0));    // [nUe+1][acc_stride]; nUe even
@@ -268,6 +291,7 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
     const int li = lane%TILE, half = lane/TILE;
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     unsigned long long npairs = 0;
+    unsigned tiles_unchecked = 0, tiles_checked = 0;     // P1: tiles this workgroup took without / with the validity test (wave-uniform)
     const double *cur_ptab = nullptr;                    // general power: whose tables s_pow holds
 
     // inputs of tile t -> LDS (b-side: threads [0, TILE), a-side: threads [TILE, 2 TILE), DoF lists: everybody)
@@ -286,6 +310,11 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
             for (int k = 0; k < DPE; k++) { sl[k] = P.cslot[(size_t)k*P.ncp+c]; any |= (sl[k] >= 0); }
             // bit 1: a real cell (zero-volume padding cells inside the mesh carry negative vertex ids: their pairs do not exist)
             any |= (P.cvid[c] >= 0) ? 2 : 0;
+            if constexpr (P1) {
+                // one wave per side: are all its cells real and with a DoF?
+                const bool all = __ballot(any == 3) == ~0ull;
+                if (l == 0) ((short*)(s_next+1))[bside ? 1 : 0] = all ? 1 : 0;
+            }
             // the points of both sides are formed here, once per cell and tile: as loaded values they stay in registers over the
             // pair loop (points recomputed from the vertices are rematerialised inside it when registers get tight)
             double *__restrict__ pts = (bside ? s_y : s_x)+l*PS;
@@ -306,11 +335,11 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
             if (bside) {
                 s_volb[l] = vol; s_hb[l] = any;
 #pragma unroll
-                for (int k = 0; k < DPE; k++) s_slotb[l*SS+k] = sl[k] >= 0 ? sl[k] : nUe;
+                for (int k = 0; k < DPE; k++) s_slotb[l*SS+k] = (sl[k] >= 0 ? sl[k] : nUe)*OFFB;
             } else {
                 s_vola[l] = vol; s_ha[l] = any;
 #pragma unroll
-                for (int k = 0; k < DPE; k++) s_sa[l*SS+k] = (sl[k] >= 0 ? sl[k] : nUe)*acc_stride;
+                for (int k = 0; k < DPE; k++) s_sa[l*SS+k] = (sl[k] >= 0 ? sl[k] : nUe)*acc_stride*OFFB;
             }
         }
         const int *__restrict__ dofA = P.blk_dofs+(size_t)tl.x*P.blk_stride;
@@ -370,6 +399,11 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
         for (int k = 0; k < DPE; k++) sa[k] = s_sa[li*SS+k];
         const int fa = s_ha[li];
         const double vola = s_vola[li];
+        bool unchecked = false;                              // wave-uniform, the same in every wave
+        if constexpr (P1) {
+            unchecked = __builtin_amdgcn_readfirstlane(s_next[1]) == 0x00010001 && !(flags_in & PNL_UNI_FLAG_CHECKED);
+            tiles_unchecked += unchecked ? 1u : 0u; tiles_checked += unchecked ? 0u : 1u;
+        }
         kern_dispatch<KT>(kk, ptab, [&](auto ktag) {
         constexpr int KTE = decltype(ktag)::value;          // KT, or 3: the branch-free general power (pnl_common.h)
         // lane li meets cell (jb + li) mod TILE of block b at step jb: every lane of a group has a b-cell of its own, so the column
@@ -391,15 +425,31 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
             for (int b = 0; b < DPE; b++) sbj[b] = s_slotb[j*SS+b];
         };
         if (TRAVEL) load_b();
+        // P1: what the rule and the kernel hold constant over the launch, made here and not per pair
+        double kc = 0.;                                      // opaque constant of kern_eval_c
+        double qw = 0., qk2 = 0., qk1 = 0., qk0 = 0.;        // 3 points: w, B^2, A B, A^2
+        double qw0 = 0., qw1 = 0., qA0 = 0., qB0 = 0., qA1 = 0., qB1 = 0.;   // 6 points: weights and A_o, B_o of the two orbits
+        if constexpr (P1) kc = kern_opaque_const<KTE>();
+        if constexpr (STRUCT && NP == 3) {
+            const double A0 = rule[R_WPH+1], B0 = rule[R_WPH]-rule[R_WPH+1];
+            qw = scalar_f64(rule[R_W]);
+            qk2 = uniform_f64(B0*B0); qk1 = uniform_f64(A0*B0); qk0 = uniform_f64(A0*A0);
+        }
+        if constexpr (STRUCT && NP == 6) {
+            qw0 = scalar_f64(rule[R_W]); qw1 = scalar_f64(rule[R_W+3]);
+            qA0 = scalar_f64(rule[R_WPH+1]); qB0 = uniform_f64(rule[R_WPH]-rule[R_WPH+1]);
+            qA1 = scalar_f64(rule[R_WPH+3*DPE+1]); qB1 = uniform_f64(rule[R_WPH+3*DPE]-rule[R_WPH+3*DPE+1]);
+        }
+        auto kev = [&](double d2) {
+            if constexpr (P1) return kern_eval_c<KTE>(kk, d2, ptab, kc); else return kern_eval<KTE>(kk, d2, ptab);
+        };
 #pragma unroll 1
         for (int jj = 0; jj < ITER; jj++) {
             if (!TRAVEL) { j = (wave*JW+jj*HALVES+half+li) & (TILE-1); load_b(); }
             else if (jj) {
-                // one lane on: whichever way the rotation goes, the wave meets 16 consecutive cells of block b per lane, and the index
-                // travels with the data
+                // one lane on: lane l takes the data of lane l + 1 (mod 64), so the wave meets 16 consecutive cells of block b per lane;
+                // the index does not travel (see behind the loop), the flags travel where they are read
                 constexpr int ROT = 0x134;                 // wave_rol:1
-                j = __builtin_amdgcn_update_dpp(0, j, ROT, 0xf, 0xf, true);
-                fb = __builtin_amdgcn_update_dpp(0, fb, ROT, 0xf, 0xf, true);
                 volb_j = dpp_get<ROT>(volb_j);
 #pragma unroll
                 for (int b = 0; b < DPE; b++) sbj[b] = __builtin_amdgcn_update_dpp(0, sbj[b], ROT, 0xf, 0xf, true);
@@ -411,11 +461,24 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                 }
             }
             // NA:138-150: pairs with boundary DoFs only are skipped; pairs that hold a padding cell do not exist
-            const bool valid = (((fa | fb) & 1) != 0) && (((fa & fb) & 2) != 0);
-            npairs += (unsigned long long)__popcll(__ballot(valid));
-            const double volb = valid ? volb_j : 0.;
-            // NA:1405-1410: symmetric cell pairs count twice
-            const double vv = scale2*vola*volb;
+            // NA:1405-1410: symmetric cell pairs count twice (scale2)
+            double vv;
+            if (P1 && unchecked) {
+                // every pair of the tile exists.  The product is made in both arms (opaque: the compiler would join the volumes and
+                // multiply once, which costs the copy of a register pair here)
+                npairs += 64;
+                vv = scale2*vola*volb_j;
+                asm("" : "+v"(vv));
+            } else {
+                const bool valid = (((fa | fb) & 1) != 0) && (((fa & fb) & 2) != 0);
+                npairs += (unsigned long long)__popcll(__ballot(valid));
+                const double volb = valid ? volb_j : 0.;
+                vv = scale2*vola*volb;
+                if constexpr (P1) {
+                    asm("" : "+v"(vv));
+                    fb = __builtin_amdgcn_update_dpp(0, fb, 0x134, 0xf, 0xf, true);    // the flags travel in the tiles that read them
+                }
+            }
             static_assert(!STRUCT || (DPE == 3 && TRAVEL && XPTS), "the structured rules: P1");
             if constexpr (STRUCT && NP == 3) {
                 double g[3][3];
@@ -426,28 +489,27 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                         double d2 = 0.;
 #pragma unroll
                         for (int d = 0; d < DIM; d++) { const double t = xa[a][d]-y[b][d]; d2 = __builtin_fma(t, t, d2); }
-                        g[a][b] = kern_eval<KTE>(kk, d2, ptab);
+                        g[a][b] = kev(d2);
                     }
                 double sr[3], sc[3];
 #pragma unroll
                 for (int a = 0; a < 3; a++) { sr[a] = (g[a][0]+g[a][1])+g[a][2]; sc[a] = (g[0][a]+g[1][a])+g[2][a]; }
                 const double S = (sr[0]+sr[1])+sr[2];
-                const double w = rule[R_W], A0 = rule[R_WPH+1], B0 = rule[R_WPH]-rule[R_WPH+1];
-                const double vvw = vv*w;
+                const double vvw = vv*qw;
 #pragma unroll
                 for (int a = 0; a < 3; a++) {
                     racc[a] = __builtin_fma(vvw, sr[a], racc[a]);
                     cacc[a] = __builtin_fma(vvw, sc[a], cacc[a]);
                 }
                 if (!(flags & 4)) {
-                    const double k2 = -vv*(B0*B0), k1 = -vv*(A0*B0), T = (-vv*(A0*A0))*S;
+                    const double k2 = -vv*qk2, k1 = -vv*qk1, T = (-vv*qk0)*S;
                     double ra[3], cb[3];
 #pragma unroll
                     for (int a = 0; a < 3; a++) { ra[a] = __builtin_fma(k1, sr[a], T); cb[a] = k1*sc[a]; }
 #pragma unroll
                     for (int b = 0; b < 3; b++)
 #pragma unroll
-                        for (int a = 0; a < 3; a++) lds_add_f64(&s_acc[sa[a]+sbj[b]], __builtin_fma(k2, g[a][b], ra[a]+cb[b]));
+                        for (int a = 0; a < 3; a++) lds_add_f64((double*)((char*)s_acc+(sa[a]+sbj[b])), __builtin_fma(k2, g[a][b], ra[a]+cb[b]));
                 } else if (S == 1.2345e300) s_acc[0] = vv;
                 continue;
             }
@@ -483,23 +545,21 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                         double d2 = 0.;
 #pragma unroll
                         for (int d = 0; d < DIM; d++) { const double t = x[d]-y[jp][d]; d2 = __builtin_fma(t, t, d2); }
-                        g[jp] = kern_eval<KTE>(kk, d2, ptab);
+                        g[jp] = kev(d2);
                         c[jp] = __builtin_fma(wi, g[jp], c[jp]);
                     }
                     const double s0 = (g[0]+g[1])+g[2], s1 = (g[3]+g[4])+g[NP-1];
-                    const double A0 = rule[R_WPH+1], B0 = rule[R_WPH]-rule[R_WPH+1];
-                    const double A1 = rule[R_WPH+3*DPE+1], B1 = rule[R_WPH+3*DPE]-rule[R_WPH+3*DPE+1];
-                    r = __builtin_fma(rule[R_W], s0, rule[R_W+3]*s1);
-                    const double base = __builtin_fma(A0, s0, A1*s1);
+                    r = __builtin_fma(qw0, s0, qw1*s1);
+                    const double base = __builtin_fma(qA0, s0, qA1*s1);
 #pragma unroll
-                    for (int b = 0; b < DPE; b++) u[b] = __builtin_fma(B0, g[b], __builtin_fma(B1, g[NP == 6 ? 3+b : 0], base));
+                    for (int b = 0; b < DPE; b++) u[b] = __builtin_fma(qB0, g[b], __builtin_fma(qB1, g[NP == 6 ? 3+b : 0], base));
                 } else {
 #pragma unroll
                 for (int jp = 0; jp < NP; jp++) {
                     double d2 = 0.;
 #pragma unroll
                     for (int d = 0; d < DIM; d++) { const double t = x[d]-y[jp][d]; d2 = __builtin_fma(t, t, d2); }
-                    const double g = kern_eval<KTE>(kk, d2, ptab);
+                    const double g = kev(d2);
                     r = __builtin_fma(rule[R_W+jp], g, r);
                     c[jp] = __builtin_fma(wi, g, c[jp]);
 #pragma unroll
@@ -521,7 +581,10 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                 for (int b = 0; b < DPE; b++) {
                     const int sb = sbj[b];
 #pragma unroll
-                    for (int a = 0; a < DPE; a++) lds_add_f64(&s_acc[sa[a]+sb], -vv*G[a][b]);
+                    for (int a = 0; a < DPE; a++) {
+                        if constexpr (P1) lds_add_f64((double*)((char*)s_acc+(sa[a]+sb)), -vv*G[a][b]);
+                        else lds_add_f64(&s_acc[sa[a]+sb], -vv*G[a][b]);
+                    }
                 }
             } else if (G[0][0]+G[1][2]+G[DPE-1][DPE-1] == 1.2345e300) s_acc[0] = vv;
             // scaled column sums of cell j
@@ -532,7 +595,10 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
             }
         }
         if (TRAVEL) {
-            // the sums that travelled through this wave's lanes, now at the lane that met cell j last
+            // the sums that travelled through this wave's lanes, now at the lane that met cell j last: ITER - 1 rotations by one lane
+            // wave_rol:1 (ROT in the loop): lane l reads lane l + 1 (mod 64), once per trip behind the first
+            static_assert(!TRAVEL || (HALVES == 1 && ITER == JW), "the closed form of j: one rotation by one lane per trip, ITER - 1 in all");
+            j = (wave*JW+half+li+(ITER-1)) & (TILE-1);
 #pragma unroll
             for (int jp = 0; jp < NP; jp++) lds_add_f64(&s_Rb[j*RS+jp], cacc[TRAVEL ? jp : 0]);
         }
@@ -628,6 +694,10 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
         atomicAdd(&P.counters[2], npairs*(unsigned long long)(NP*NP));
         atomicAdd(&P.counters[6], npairs);
         atomicAdd(&P.counters[131+q_uniform-2], npairs);
+    }
+    if (P1 && tid == 0) {
+        if (tiles_unchecked) atomicAdd(&P.counters[PNL_DC_UNI_TILES_UNCHECKED], (unsigned long long)tiles_unchecked);
+        if (tiles_checked) atomicAdd(&P.counters[PNL_DC_UNI_TILES_CHECKED], (unsigned long long)tiles_checked);
     }
 }
 

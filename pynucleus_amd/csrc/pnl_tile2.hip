@@ -69,13 +69,14 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
     if (pnl_tune("PNL_VERBOSE"))
         fprintf(stderr, "[pnl] uniform tiles of order %d: %d, dpe=%d np=%d kt=%d struct=%d lds=%zu bytes (%d per CU), acc_stride=%d\n", q, ntiles, DPE,
                 NP, KT, (int)STRUCT, lds, per_cu, acc_stride);
+    const int uni_checked = (DPE == 3 && pnl_tune("PNL_UNI_CHECKED")) ? PNL_UNI_FLAG_CHECKED : 0;      // tests: no tile skips the validity test
     int uni_abl = 0;
 #ifdef PNL_DEBUG_ABLATE
     uni_abl = pnl_tune("PNL_UNI_ABL") ? atoi(pnl_tune("PNL_UNI_ABL")) : 0;
 #endif
     kt_begin(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     hipLaunchKernelGGL(kfun, dim3(grid), dim3(256), lds, ctx->stream, Pt, tiles, tile_cls, (const DevKernel*)ctx->b_kcls.p, ntiles, A,
-                       (long long)ldA, Dglob, acc_stride, q, (ctx->run.symflush ? 1 : 0) | uni_abl | pow_flag, (const double*)ctx->b_uni.p+ctx->uni_off[q],
+                       (long long)ldA, Dglob, acc_stride, q, (ctx->run.symflush ? 1 : 0) | uni_abl | pow_flag | uni_checked, (const double*)ctx->b_uni.p+ctx->uni_off[q],
                        nUe, SO, ctr);
     kt_end(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     HIPCHK(ctx, hipGetLastError());
