@@ -108,6 +108,9 @@ enum pnl_counter {
  *                     symmetric 3- and 6-point rules (tests: both evaluators against each other),
  *   "PNL_UNI_CHECKED" P1 uniform-order tiles: every tile through the pair loop that tests whether a pair exists, also the tiles whose
  *                     cells are all real and have a DoF (tests: both loops against each other; read at every launch),
+ *   "PNL_UNI_LANES"   P1 uniform-order tiles: the lane layout of the blocks (pnl_uniform_lane_layout) -- 1 searched (the default), 0 lane =
+ *                     cell and column = slot with the row stride 1 mod 32 (the access pattern before the layout existed), 2 random
+ *                     (tests: results do not rest on the layout; read at every launch),
  *   "PNL_MIXED_GENERIC" mixed tiles: the evaluators for arbitrary rules also for the pairs whose rule has that orbit structure
  *                     (tests: both evaluators against each other),
  *   "PNL_MIXED_UNSETTLED" the tile plan settles no mixed tile: every mixed tile is classified pair by pair in every assembly
@@ -420,6 +423,18 @@ int pnl_get_settled_tiles(pnl_context *ctx, int32_t *tiles, int64_t ntiles);
  * p | (order - 2) << 12, order 4 first, then 3, then 2, ascending pair index p within an order; zero behind the last entry.
  * Returns the number of tiles the plan holds lists for (0: it keeps codes only), or an error. */
 int pnl_get_settled_lists(pnl_context *ctx, uint16_t *codes, uint16_t *lists, int64_t ntiles);
+/* Lane layout of the 64-cell blocks for the P1 uniform-tile kernels (2D; needs no device).  cells [nc][3] vertex ids, dofs [nc][3]
+ * global DoFs (negative: none).  mode: the option PNL_UNI_LANES -- 0 identity (lane = cell, column = slot; the row stride of the
+ * sub-block is the launcher's, 1 mod 32 doubles), 1 searched (default), 2 random (a bad layout; results must not depend on it).
+ * sizes[4] = number of blocks, nU (largest number of DoFs of a block), row stride of the LDS sub-block in doubles (0 for mode 0),
+ * padded number of cells ncp.  With the arrays NULL only sizes is filled.  lane_cell [nblocks][64]: the cell of the block lane l
+ * holds; lds_col [nblocks][nU]: LDS column of a block slot; vorder [nc][3]: local vertex order of the tile kernels; cell_col [3][ncp]:
+ * LDS column of (local position, cell), a trash column >= stride - 16 where the cell has no DoF; mult [nblocks]: modelled cost of a
+ * sub-block add relative to a conflict-free one (mean over the 12 classes (16-lane group, local position) of the most loaded
+ * double-bank; 0 for mode 0, where the bank depends on the partner block); *seconds: wall time of the layout of all blocks.
+ * nthreads <= 0: the library's host-thread pool.  The tables do not depend on the number of threads. */
+int pnl_uniform_lane_layout(int nc, const int32_t *cells, const int32_t *dofs, int mode, int nthreads, int32_t *sizes, uint8_t *lane_cell,
+                            int16_t *lds_col, int8_t *vorder, int16_t *cell_col, double *mult, double *seconds);
 /* device time of the tile kernels of the last assemble call, one HIP-event pair around each launch (milliseconds, 0 if the
  * kernel did not run; a slot that was launched several times -- stages of a staged fold, order classes -- holds the sum over
  * its launches): [0] general tile kernel, [1] uniform tiles of

@@ -34,7 +34,7 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest',
            'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs',
            'pnl_csr_cg_jacobi', 'pnl_fe_space_create', 'pnl_fe_space_destroy', 'pnl_assemble_nonlinearity', 'pnl_imex_create',
-           'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi', 'pnl_gemv_block', 'pnl_spmv_block']
+           'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi', 'pnl_gemv_block', 'pnl_spmv_block', 'pnl_uniform_lane_layout']
 
 PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
 PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
@@ -155,6 +155,7 @@ def load():
     L.pnl_get_fold_plan.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64]
     L.pnl_get_settled_tiles.argtypes = [vp, vp, C.c_int64]
     L.pnl_get_settled_lists.argtypes = [vp, vp, vp, C.c_int64]
+    L.pnl_uniform_lane_layout.argtypes = [i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.pnl_set_row_slab.argtypes = [vp, i32, vp, i32, vp]
     L.pnl_tree_build.argtypes = [i32, i32, vp, vp, vp, i32, dbl, i32, i32, i32, C.POINTER(vp)]
     L.pnl_tree_build_blocks.argtypes = [i32, i32, vp, vp, vp, i32, dbl, i32, i32, i32, vp, i32, C.POINTER(vp)]
@@ -244,6 +245,32 @@ def load():
             f.restype = C.c_int
     _LIB = L
     return L
+
+
+def uniform_lane_layout(cells, dofs, mode=1, nthreads=0):
+    """pnl_uniform_lane_layout: the lane layout of the 64-cell blocks for the P1 uniform-tile kernels (no device needed).
+    cells [nc, 3] vertex ids, dofs [nc, 3] global DoFs (negative: none).  Returns a dict with nU, stride, lane_cell [nblocks, 64],
+    lds_col [nblocks, nU], vorder [nc, 3], cell_col [3, ncp], mult [nblocks] and the wall time of the layout in seconds."""
+    L = load()
+    cells = np.ascontiguousarray(cells, dtype=np.int32)
+    dofs = np.ascontiguousarray(dofs, dtype=np.int32)
+    nc = cells.shape[0]
+    assert cells.shape == (nc, 3) and dofs.shape == (nc, 3)
+    sizes = np.zeros(4, dtype=np.int32)
+    rc = L.pnl_uniform_lane_layout(nc, cells.ctypes.data, dofs.ctypes.data, mode, nthreads, sizes.ctypes.data, None, None, None, None, None, None)
+    if rc:
+        raise PnlError('pnl_uniform_lane_layout failed: {}'.format(rc))
+    nblocks, nU, _, ncp = (int(v) for v in sizes)
+    out = dict(lane_cell=np.zeros((nblocks, 64), dtype=np.uint8), lds_col=np.zeros((nblocks, nU), dtype=np.int16),
+               vorder=np.zeros((nc, 3), dtype=np.int8), cell_col=np.zeros((3, ncp), dtype=np.int16), mult=np.zeros(nblocks))
+    sec = C.c_double(0.)
+    rc = L.pnl_uniform_lane_layout(nc, cells.ctypes.data, dofs.ctypes.data, mode, nthreads, sizes.ctypes.data, out['lane_cell'].ctypes.data,
+                                   out['lds_col'].ctypes.data, out['vorder'].ctypes.data, out['cell_col'].ctypes.data, out['mult'].ctypes.data,
+                                   C.byref(sec))
+    if rc:
+        raise PnlError('pnl_uniform_lane_layout failed: {}'.format(rc))
+    out.update(nU=nU, stride=int(sizes[2]), ncp=ncp, seconds=sec.value)
+    return out
 
 
 def set_option(name, value=None):

@@ -59,6 +59,14 @@ struct AssemblyRun {
     bool visited_is_assembled = false;      // (finite-horizon tiles) every visited (non-REMOTE) pair is an assembled one
 };
 
+// host copy of the lane layout tables (UniLanes, pnl_device.h)
+struct UniLaneTables {
+    std::vector<unsigned char> lane_cell;
+    std::vector<short> lds_col, cell_col;       // cell_col in cell order [3][ncp] (pnl_uni_lanes_ready permutes the device copy)
+    std::vector<double> mult;         // [nblocks] modelled LDS cycles of a sub-block add over the conflict-free ones
+    int stride = 0;                   // row stride of the sub-block in doubles (0: the launcher's rule for the identity layout)
+};
+
 struct pnl_context {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -167,6 +175,14 @@ struct pnl_context {
     bool have_tile_order = false;     // permuted cell tables for the tile kernels (finalize starts the search, tile_order_ready ends it)
     struct TileOrderJob *tile_job = nullptr;
     DevBuf b_cellv_t, b_cdof_t, b_cslot_t, b_Dt;    // b_Dt: diagonal blocks in the tile kernels' local order
+    // 2D P1: lane layout of the blocks for k_tile_uniform (pnl_setup.hip: uni_lane_layout), one set of tables per value of the option
+    // PNL_UNI_LANES (0 identity, 1 searched, 2 random); the device copies hold the set uni_lanes_up (-1: none)
+    UniLaneTables uni_lanes[3];
+    int uni_lanes_up = -1;
+    double uni_lanes_seconds = 0.;
+    DevBuf b_ul_cell, b_ul_col, b_ul_ccol, b_ul_cellv, b_ul_cvol, b_ul_cslot, b_ul_real;
+    std::vector<double> ul_cellv_t;             // host copies of the cell tables in the tile kernels' vertex order, for the lane-ordered
+    std::vector<short> ul_cslot_t;              // device tables of a layout
     PwDev pw;
     bool have_pw = false, have_pw_rules[2][3] = {{false, false, false}, {false, false, false}};
     int pw_nkeys[2] = {0, 0};
@@ -382,6 +398,9 @@ inline void kt_end(pnl_context *ctx, int slot) {
 
 // pnl_setup.hip: joins the vertex-order search finalize() started and uploads the permuted cell tables (sets have_tile_order)
 int pnl_tile_order_ready(pnl_context *ctx);
+// pnl_setup.hip: the lane layout tables of the option PNL_UNI_LANES on the device (2D P1, after pnl_tile_order_ready); *mode: the value
+// in force, *stride: row stride of the LDS sub-block in doubles (0: the launcher's own rule, mode 0)
+int pnl_uni_lanes_ready(pnl_context *ctx, UniLanes *UL, int *mode, int *stride);
 
 // pnl_setup.hip: what pnl_h2_setup (pnl_h2.hip) shares with the assemblies of a constant or piecewise constant order -- kernels, order
 // formulas and rules are set, the tables derived from mesh and DoF map exist (finalize), the problem description holds the current class

@@ -188,3 +188,18 @@ struct SlotOut {
     const int *colbase;         // [nblocks+1], multiples of 8
     int S, nU;                  // nU: the largest number of DoFs of a block (rows of the LDS sub-block of the tile kernels)
 };
+
+// Lane layout of the 64-cell blocks for k_tile_uniform (2D P1; pnl_setup.hip: uni_lane_layout).  The lanes of a pair-wave own the cells
+// of the COLUMN block, so the LDS double-bank of a sub-block add is (column of the lane's DoF) mod 16 when the row stride is a multiple
+// of 16 doubles; the tables place cells and columns so that the 16 lanes of a group hold 16 different residues.
+struct UniLanes {
+    const unsigned char *lane_cell;   // [nblocks][64] cell of the block that lane l holds (a permutation)
+    const short *lds_col;             // [nblocks][nU] LDS column of a block slot (injective, < stride)
+    // the cell tables of the kernel in LANE order, entry blk*64 + l = cell blk*64 + lane_cell[blk][l]: the staging loads of a tile do not
+    // wait for lane_cell (a dependent load per tile cost the order-2 launch 2 ms at 98,304 cells)
+    const double *cellv;              // [6][ncp] vertices in the tile kernels' local order
+    const double *cvol;               // [ncp]
+    const short *cslot;               // [3][ncp] block slot of the DoF at local position k, -1: none
+    const short *cell_col;            // [3][ncp] its LDS column: lds_col of the slot, or a trash column
+    const unsigned char *real;        // [ncp] 1: a cell of the mesh (no padding cell)
+};

@@ -8,6 +8,7 @@
 // pnl_tile_order_range (pnl_hip.hip); what the launching units need from here is declared in pnl_context.h.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -22,8 +23,8 @@
 
 // body(th, nthr) on up to eight host threads th = 0 .. nthr-1, joined before the return; the caller splits its index range
 template <class F>
-static void host_threads(F body) {
-    const int nthr = (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+static void host_threads(F body, int want = 0) {
+    const int nthr = want > 0 ? std::min(want, 64) : (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
     std::vector<std::thread> pool;
     for (int th = 0; th < nthr; th++) pool.emplace_back([&body, th, nthr]() { body(th, nthr); });
     for (auto &t : pool) t.join();
@@ -36,6 +37,10 @@ struct TileOrderJob {
     std::vector<double> cellv;
     std::vector<int32_t> cdof;
     std::vector<int16_t> cslot;
+    bool reorder = true;                       // false (PNL_NO_REORDER): the reference's vertex order, lane tables only
+    int nU = 0;
+    UniLaneTables lanes[3];
+    double lanes_seconds = 0.;
     std::thread worker;
 };
 
@@ -52,6 +57,9 @@ int pnl_tile_order_ready(pnl_context *ctx) {
     TileOrderJob *job = ctx->tile_job;
     if (!job) return PNL_OK;
     if (job->worker.joinable()) job->worker.join();
+    for (int m = 0; m < 3; m++) ctx->uni_lanes[m] = std::move(job->lanes[m]);
+    ctx->uni_lanes_seconds = job->lanes_seconds;
+    ctx->uni_lanes_up = -1;
     const int nV = job->dim+1, NC = nV*job->dim, ncp = job->ncp, dpe = job->dpe, dim = job->dim;
     std::vector<double> cellv_t((size_t)NC*ncp, 0.);
     std::vector<int32_t> cdof_t((size_t)dpe*ncp, -1);
@@ -64,6 +72,9 @@ int pnl_tile_order_ready(pnl_context *ctx) {
             cslot_t[(size_t)k*ncp+c] = job->cslot[(size_t)src*ncp+c];
         }
     int rc2;
+    ctx->ul_cellv_t = cellv_t;
+    ctx->ul_cslot_t.assign(cslot_t.begin(), cslot_t.end());
+    if (!job->reorder) { delete job; ctx->tile_job = nullptr; return PNL_OK; }       // lperm is the identity: no tables of their own
     if ((rc2 = upload(ctx, ctx->b_cellv_t, cellv_t.data(), cellv_t.size()))) return rc2;
     if ((rc2 = upload(ctx, ctx->b_cdof_t, cdof_t.data(), cdof_t.size()))) return rc2;
     if ((rc2 = upload(ctx, ctx->b_cslot_t, cslot_t.data(), cslot_t.size()))) return rc2;
@@ -81,31 +92,242 @@ int pnl_tile_order_ready(pnl_context *ctx) {
 // The search runs on host threads of its own (0.24 s on one thread at 98,304 cells, 30-50 ms on eight) and is waited for by the
 // first dense assembly (pnl_tile_order_ready): the near-field / H2 path never reads the permuted tables, and a dense assembly
 // overlaps it with the rest of finalize() and with the uploads of rules and kernels.
-static void tile_order_search(TileOrderJob *job) {
+static void tile_order_block(int b, int nc, int T, const int *cells, int *lperm) {
     static const int perms[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {2, 1, 0}, {1, 0, 2}};
-    const int nc = job->nc, T = job->T, nblocks = job->nblocks;
-    const std::vector<int> &cells = job->cells;
-    std::vector<int> &lperm = job->lperm;
-    // the blocks are independent: a few host threads
-    host_threads([&](int th, int nthr) {
-        for (int b = th; b < nblocks; b += nthr) {
-            std::vector<std::pair<long long, int>> seen;   // (vertex*3+pos) -> count, small per block
-            auto get = [&](int v, int pos) { for (auto &e : seen) if (e.first == (long long)v*3+pos) return e.second; return 0; };
-            auto add = [&](int v, int pos, int d) { for (auto &e : seen) if (e.first == (long long)v*3+pos) { e.second += d; return; } seen.push_back({(long long)v*3+pos, d}); };
-            // greedy pass, then a few sweeps of local search (every cell re-chooses its order given all the others)
-            for (int sweep = 0; sweep < 5; sweep++)
-                for (int c = b*T; c < std::min(nc, (b+1)*T); c++) {
-                    if (sweep) for (int k = 0; k < 3; k++) add(cells[(size_t)c*3+lperm[(size_t)c*3+k]], k, -1);
-                    int best = 0, bestmax = 1 << 30, bestsum = 1 << 30;
-                    for (int p = 0; p < 6; p++) {
-                        int mx = 0, sum = 0;
-                        for (int k = 0; k < 3; k++) { const int g = get(cells[(size_t)c*3+perms[p][k]], k); mx = std::max(mx, g); sum += g*g; }
-                        if (mx < bestmax || (mx == bestmax && sum < bestsum)) { best = p; bestmax = mx; bestsum = sum; }
-                    }
-                    for (int k = 0; k < 3; k++) { lperm[(size_t)c*3+k] = perms[best][k]; add(cells[(size_t)c*3+perms[best][k]], k, 1); }
+    std::vector<std::pair<long long, int>> seen;   // (vertex*3+pos) -> count, small per block
+    auto get = [&](int v, int pos) { for (auto &e : seen) if (e.first == (long long)v*3+pos) return e.second; return 0; };
+    auto add = [&](int v, int pos, int d) { for (auto &e : seen) if (e.first == (long long)v*3+pos) { e.second += d; return; } seen.push_back({(long long)v*3+pos, d}); };
+    // greedy pass, then a few sweeps of local search (every cell re-chooses its order given all the others)
+    for (int sweep = 0; sweep < 5; sweep++)
+        for (int c = b*T; c < std::min(nc, (b+1)*T); c++) {
+            if (sweep) for (int k = 0; k < 3; k++) add(cells[(size_t)c*3+lperm[(size_t)c*3+k]], k, -1);
+            int best = 0, bestmax = 1 << 30, bestsum = 1 << 30;
+            for (int p = 0; p < 6; p++) {
+                int mx = 0, sum = 0;
+                for (int k = 0; k < 3; k++) { const int g = get(cells[(size_t)c*3+perms[p][k]], k); mx = std::max(mx, g); sum += g*g; }
+                if (mx < bestmax || (mx == bestmax && sum < bestsum)) { best = p; bestmax = mx; bestsum = sum; }
+            }
+            for (int k = 0; k < 3; k++) { lperm[(size_t)c*3+k] = perms[best][k]; add(cells[(size_t)c*3+perms[best][k]], k, 1); }
+        }
+}
+
+// ---- lane layout of a block for k_tile_uniform (2D P1) ------------------------------------------------------------------------
+// ds_add_f64 serves a wave in four groups of 16 contiguous lanes, 16 double-banks (tools/probes/lds_atomic_probe.hip: distinct banks
+// inside every group 8.1 cycles whatever the other groups do, n lanes of a group on one bank n times that, the cost is the sum over the
+// groups; two lanes on one ADDRESS 2.5 times).  In k_tile_uniform the lanes own the cells of the column block and the row stride of the
+// sub-block is a multiple of 16 doubles, so the bank of the add (local position k of the lane's cell, any row) is the column of that
+// DoF mod 16: the same for every step of the rotation and every partner block.  Free per block: which cell sits in which lane, and the
+// column of every DoF.  The vertex order of the cells is the one of the order search above (shared with the mixed-tile kernels, whose
+// tables therefore do not change).  Objective: over the 12 classes (lane group, local position), the pairs of lanes on one residue.
+// Min-conflicts search: a lane of a loaded residue either trades places with a lane of another group or its DoF takes another
+// residue (at most cap DoFs per residue, trading with one of that residue's DoFs when it is full); the best move is taken if it does
+// not raise the objective.  Seeded per block, so the result does not depend on the number of host threads.
+// mode 0: identity (lane = cell, column = slot, trash column nUe); 1: searched; 2: random lanes and columns (tests: a bad layout)
+namespace {
+struct LaneSearch {
+    int cnt[4][3][16], cost = 0;
+    int dof[64][3];                               // slot of (cell of the block, local position), -1: none
+    int lane_of[64], cell_at[64];
+    std::vector<int> res, inc_off, inc;           // residue per slot; incidences (cell << 2 | position) per slot
+    int nres[16];
+    unsigned long long rng;
+    unsigned next() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (unsigned)(rng >> 11); }
+    void bump(int g, int k, int r, int s) { int &c = cnt[g][k][r]; if (s > 0) { cost += c; c++; } else { c--; cost -= c; } }
+    void cell(int c, int g, int s) { for (int k = 0; k < 3; k++) if (dof[c][k] >= 0) bump(g, k, res[dof[c][k]], s); }
+    void swap_lanes(int p, int q) {
+        const int cp = cell_at[p], cq = cell_at[q], gp = p >> 4, gq = q >> 4;
+        if (gp != gq) { cell(cp, gp, -1); cell(cq, gq, -1); cell(cp, gq, 1); cell(cq, gp, 1); }
+        cell_at[p] = cq; cell_at[q] = cp; lane_of[cp] = q; lane_of[cq] = p;
+    }
+    void set_res(int d, int r) {
+        for (int e = inc_off[d]; e < inc_off[d+1]; e++) {
+            const int g = lane_of[inc[e] >> 2] >> 4, k = inc[e] & 3;
+            bump(g, k, res[d], -1); bump(g, k, r, 1);
+        }
+        nres[res[d]]--; nres[r]++; res[d] = r;
+    }
+    double multiplier() const {
+        double m = 0.;
+        for (int g = 0; g < 4; g++) for (int k = 0; k < 3; k++) { int mx = 1; for (int r = 0; r < 16; r++) mx = std::max(mx, cnt[g][k][r]); m += mx; }
+        return m/12.;
+    }
+};
+}  // namespace
+
+// columns of the searched / random layouts: cap = ceil(nU / 16) DoFs per residue, then 16 trash columns
+static int uni_lane_cap(int nU) { return std::max(1, (nU+15)/16); }
+
+static void uni_lane_block(int b, int ncp, int nU, const int16_t *cslot_t, int mode, UniLaneTables &out) {
+    const int nUe = (nU+1) & ~1, cap = uni_lane_cap(nU), ncol = 16*cap;
+    unsigned char *lane_cell = out.lane_cell.data()+(size_t)b*64;
+    short *lds_col = out.lds_col.data()+(size_t)b*nU;
+    LaneSearch S;
+    std::memset(S.cnt, 0, sizeof(S.cnt)); std::memset(S.nres, 0, sizeof(S.nres));
+    S.rng = 0x9E3779B97F4A7C15ull*(unsigned long long)(b+1)+(unsigned long long)mode;
+    for (int c = 0; c < 64; c++) for (int k = 0; k < 3; k++) S.dof[c][k] = cslot_t[(size_t)k*ncp+b*64+c];
+    S.res.assign(nU, 0); S.inc_off.assign(nU+1, 0);
+    for (int c = 0; c < 64; c++) for (int k = 0; k < 3; k++) if (S.dof[c][k] >= 0) S.inc_off[S.dof[c][k]+1]++;
+    for (int d = 0; d < nU; d++) S.inc_off[d+1] += S.inc_off[d];
+    S.inc.assign(S.inc_off[nU], 0);
+    { std::vector<int> fill(S.inc_off.begin(), S.inc_off.end()-1);
+      for (int c = 0; c < 64; c++) for (int k = 0; k < 3; k++) if (S.dof[c][k] >= 0) S.inc[fill[S.dof[c][k]]++] = c << 2 | k; }
+    for (int l = 0; l < 64; l++) S.lane_of[l] = S.cell_at[l] = l;
+    if (mode == 0) {
+        for (int l = 0; l < 64; l++) lane_cell[l] = (unsigned char)l;
+        for (int d = 0; d < nU; d++) lds_col[d] = (short)d;
+        for (int c = 0; c < 64; c++) for (int k = 0; k < 3; k++) out.cell_col[(size_t)k*ncp+b*64+c] = (short)(S.dof[c][k] >= 0 ? S.dof[c][k] : nUe);
+        out.mult[b] = 0.;                             // depends on the partner block (bank = row + column): see the tests
+        return;
+    }
+    if (mode == 2) {
+        for (int l = 63; l > 0; l--) { const int m = (int)(S.next()%(unsigned)(l+1)); std::swap(S.cell_at[l], S.cell_at[m]); }
+        for (int l = 0; l < 64; l++) S.lane_of[S.cell_at[l]] = l;
+        std::vector<int> cols(ncol);
+        for (int i = 0; i < ncol; i++) cols[i] = i;
+        for (int i = ncol-1; i > 0; i--) std::swap(cols[i], cols[S.next()%(unsigned)(i+1)]);
+        for (int d = 0; d < nU; d++) { lds_col[d] = (short)cols[d]; S.res[d] = cols[d] & 15; }
+        for (int c = 0; c < 64; c++) S.cell(c, S.lane_of[c] >> 4, 1);
+        for (int c = 0; c < 64; c++) for (int k = 0; k < 3; k++) {
+            const int t = ncol+(int)(S.next() & 15);
+            if (S.dof[c][k] < 0) S.bump(S.lane_of[c] >> 4, k, t & 15, 1);
+            out.cell_col[(size_t)k*ncp+b*64+c] = (short)(S.dof[c][k] >= 0 ? lds_col[S.dof[c][k]] : t);
+        }
+        for (int l = 0; l < 64; l++) lane_cell[l] = (unsigned char)S.cell_at[l];
+        out.mult[b] = S.multiplier();
+        return;
+    }
+    // searched: start from residue = slot mod 16 (at most cap per residue), lanes in cell order
+    for (int d = 0; d < nU; d++) { S.res[d] = d & 15; S.nres[d & 15]++; }
+    for (int c = 0; c < 64; c++) S.cell(c, c >> 4, 1);
+    std::vector<int> best_res = S.res;
+    int best_cell_at[64], best_cost = S.cost;
+    std::memcpy(best_cell_at, S.cell_at, sizeof(best_cell_at));
+    const int max_steps = 600;
+    for (int step = 0; step < max_steps && best_cost > 0; step++) {
+        // a lane and position on a loaded residue, from a random start
+        int p = -1, k = 0;
+        const unsigned start = S.next()%192u;
+        for (unsigned t = 0; t < 192u; t++) {
+            const unsigned e = (start+t)%192u;
+            const int l = (int)(e/3u), kk = (int)(e%3u), d = S.dof[S.cell_at[l]][kk];
+            if (d >= 0 && S.cnt[l >> 4][kk][S.res[d]] > 1) { p = l; k = kk; break; }
+        }
+        if (p < 0) break;
+        const int d = S.dof[S.cell_at[p]][k], c0 = S.cost;
+        // candidates: kind 0 trade lanes p, q; kind 1 residue r for d (trading with DoF e if r is full)
+        int bk = -1, bx = 0, by = -1, bcost = 1 << 30, nties = 0;
+        auto consider = [&](int kind, int x, int y) {
+            if (S.cost < bcost) { bcost = S.cost; nties = 0; }
+            if (S.cost == bcost && S.next()%(unsigned)(++nties) == 0) { bk = kind; bx = x; by = y; }
+        };
+        for (int q = 0; q < 64; q++) {
+            if ((q >> 4) == (p >> 4)) continue;
+            S.swap_lanes(p, q); consider(0, q, -1); S.swap_lanes(p, q);
+        }
+        const int r0 = S.res[d];
+        for (int r = 0; r < 16; r++) {
+            if (r == r0) continue;
+            if (S.nres[r] < cap) { S.set_res(d, r); consider(1, r, -1); S.set_res(d, r0); }
+            else
+                for (int e = 0; e < nU; e++) {
+                    if (S.res[e] != r) continue;
+                    S.set_res(e, r0); S.set_res(d, r); consider(1, r, e); S.set_res(d, r0); S.set_res(e, r);
                 }
         }
-    });
+        if (bk < 0 || bcost > c0) continue;               // no move that does not raise the objective: another lane next time
+        if (bk == 0) S.swap_lanes(p, bx);
+        else { if (by >= 0) S.set_res(by, r0); S.set_res(d, bx); }
+        if (S.cost < best_cost) { best_cost = S.cost; best_res = S.res; std::memcpy(best_cell_at, S.cell_at, sizeof(best_cell_at)); }
+    }
+    // the best state, counted again; trash columns: per class the lanes without a DoF take residues no lane of the class holds
+    std::memset(S.cnt, 0, sizeof(S.cnt)); S.cost = 0;
+    S.res = best_res;
+    for (int l = 0; l < 64; l++) { S.cell_at[l] = best_cell_at[l]; S.lane_of[best_cell_at[l]] = l; }
+    for (int c = 0; c < 64; c++) S.cell(c, S.lane_of[c] >> 4, 1);
+    { int used[16] = {};
+      for (int d = 0; d < nU; d++) lds_col[d] = (short)(S.res[d]+16*used[S.res[d]]++); }
+    for (int g = 0; g < 4; g++)
+        for (int k = 0; k < 3; k++) {
+            int r = 0;
+            for (int l = 16*g; l < 16*g+16; l++) {
+                const int c = S.cell_at[l], d = S.dof[c][k];
+                short col;
+                if (d >= 0) col = lds_col[d];
+                else {
+                    while (r < 16 && S.cnt[g][k][r] > 0) r++;
+                    const int rr = r < 16 ? r : 0;
+                    S.bump(g, k, rr, 1);
+                    col = (short)(ncol+rr);
+                }
+                out.cell_col[(size_t)k*ncp+b*64+c] = col;
+            }
+        }
+    for (int l = 0; l < 64; l++) lane_cell[l] = (unsigned char)S.cell_at[l];
+    out.mult[b] = S.multiplier();
+}
+
+// the tables of all three settings of PNL_UNI_LANES for every block; cslot_t: [3][ncp] slots in the tile kernels' vertex order
+static void uni_lane_layout(int nblocks, int ncp, int nU, const int16_t *cslot_t, UniLaneTables (&out)[3], int nthreads = 0) {
+    for (int m = 0; m < 3; m++) {
+        out[m].lane_cell.assign((size_t)nblocks*64, 0); out[m].lds_col.assign((size_t)nblocks*nU, 0);
+        out[m].cell_col.assign((size_t)3*ncp, 0); out[m].mult.assign(nblocks, 0.);
+        out[m].stride = m == 0 ? 0 : 16*uni_lane_cap(nU)+16;
+    }
+    host_threads([&](int th, int nthr) {
+        for (int b = th; b < nblocks; b += nthr)
+            for (int m = 0; m < 3; m++) uni_lane_block(b, ncp, nU, cslot_t, m, out[m]);
+    }, nthreads);
+}
+
+static void tile_order_search(TileOrderJob *job) {
+    const int nc = job->nc, T = job->T, nblocks = job->nblocks, ncp = job->ncp;
+    // the blocks are independent: a few host threads
+    if (job->reorder)
+        host_threads([&](int th, int nthr) {
+            for (int b = th; b < nblocks; b += nthr) tile_order_block(b, nc, T, job->cells.data(), job->lperm.data());
+        });
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int16_t> cslot_t((size_t)3*ncp, -1);
+    for (int c = 0; c < nc; c++) for (int k = 0; k < 3; k++) cslot_t[(size_t)k*ncp+c] = job->cslot[(size_t)job->lperm[(size_t)c*3+k]*ncp+c];
+    uni_lane_layout(nblocks, ncp, job->nU, cslot_t.data(), job->lanes);
+    job->lanes_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now()-t0).count();
+}
+
+// the lane layout of the option in force on the device (uploaded when the option or the tables changed)
+int pnl_uni_lanes_ready(pnl_context *ctx, UniLanes *UL, int *mode, int *stride) {
+    int rc = pnl_tile_order_ready(ctx);
+    if (rc) return rc;
+    int m = pnl_tune("PNL_UNI_LANES") ? atoi(pnl_tune("PNL_UNI_LANES")) : 1;
+    if (m < 0 || m > 2) return fail(ctx, PNL_ERR_INVALID, "PNL_UNI_LANES = %d (0 identity, 1 searched, 2 random)", m);
+    const UniLaneTables &T = ctx->uni_lanes[m];
+    if (T.lane_cell.empty()) return fail(ctx, PNL_ERR_STATE, "no lane layout (2D P1 only)");
+    if (ctx->uni_lanes_up != m) {
+        if ((rc = upload(ctx, ctx->b_ul_cell, T.lane_cell.data(), T.lane_cell.size()))) return rc;
+        if ((rc = upload(ctx, ctx->b_ul_col, T.lds_col.data(), T.lds_col.size()))) return rc;
+        // the cell tables in lane order
+        const int ncp = ctx->ncp, nc = ctx->nc;
+        std::vector<double> cellv((size_t)6*ncp), cvol(ncp);
+        std::vector<short> cslot((size_t)3*ncp), ccol((size_t)3*ncp);
+        std::vector<unsigned char> real(ncp);
+        for (int p = 0; p < ncp; p++) {
+            const int c = (p & ~63)+T.lane_cell[p];
+            for (int k = 0; k < 6; k++) cellv[(size_t)k*ncp+p] = ctx->ul_cellv_t[(size_t)k*ncp+c];
+            for (int k = 0; k < 3; k++) { cslot[(size_t)k*ncp+p] = ctx->ul_cslot_t[(size_t)k*ncp+c]; ccol[(size_t)k*ncp+p] = T.cell_col[(size_t)k*ncp+c]; }
+            cvol[p] = c < nc ? ctx->vol[c] : 0.;
+            real[p] = c < nc && ctx->vol[c] != 0.;
+        }
+        if ((rc = upload(ctx, ctx->b_ul_ccol, ccol.data(), ccol.size()))) return rc;
+        if ((rc = upload(ctx, ctx->b_ul_cellv, cellv.data(), cellv.size()))) return rc;
+        if ((rc = upload(ctx, ctx->b_ul_cvol, cvol.data(), cvol.size()))) return rc;
+        if ((rc = upload(ctx, ctx->b_ul_cslot, cslot.data(), cslot.size()))) return rc;
+        if ((rc = upload(ctx, ctx->b_ul_real, real.data(), real.size()))) return rc;
+        ctx->uni_lanes_up = m;
+    }
+    UL->lane_cell = (const unsigned char*)ctx->b_ul_cell.p; UL->lds_col = (const short*)ctx->b_ul_col.p; UL->cell_col = (const short*)ctx->b_ul_ccol.p;
+    UL->cellv = (const double*)ctx->b_ul_cellv.p; UL->cvol = (const double*)ctx->b_ul_cvol.p; UL->cslot = (const short*)ctx->b_ul_cslot.p;
+    UL->real = (const unsigned char*)ctx->b_ul_real.p;
+    *mode = m; *stride = T.stride;
+    return PNL_OK;
 }
 
 // ---- finalize(): everything derived from mesh + DoF map, in steps ---------------------------------------------------------
@@ -121,12 +343,14 @@ struct CellTables {
     std::vector<int> vptr, vcells;            // vertex -> cells adjacency (real cells)
 };
 
-static void start_tile_order_search(pnl_context *ctx, const CellTables &F) {
+static void start_tile_order_search(pnl_context *ctx, const CellTables &F, bool reorder) {
     const int nc = F.nc, nV = F.nV;
     TileOrderJob *job = new TileOrderJob;
     ctx->tile_job = job;
     job->cells = ctx->cells;
     job->nc = nc; job->T = F.T; job->nblocks = F.nblocks; job->ncp = F.ncp; job->dim = F.dim; job->dpe = F.dpe;
+    job->reorder = reorder; job->nU = ctx->nU;
+    job->cellv = F.cellv; job->cdof = F.cdof; job->cslot = F.cslot;   // the lane layout reads the slots: before the worker starts
     job->lperm.resize((size_t)nc*nV);
     for (int c = 0; c < nc; c++) for (int k = 0; k < nV; k++) job->lperm[(size_t)c*nV+k] = k;
     job->worker = std::thread(tile_order_search, job);
@@ -541,13 +765,14 @@ static int finalize(pnl_context *ctx) {
     F.dim = dim; F.nV = nV; F.nc = nc; F.dpe = dpe; F.T = T; F.nblocks = nblocks; F.ncp = ncp;
     const bool reorder = dpe == nV && dim == 2 && !pnl_tune("PNL_NO_REORDER");
     tile_order_drop(ctx);
-    if (reorder) start_tile_order_search(ctx, F);
     int rc;
     if ((rc = padded_cell_tables(ctx, F))) return rc;
     block_dofs(ctx, F);
-    // permuted copies for the tile kernels: built and uploaded by pnl_tile_order_ready once the search has finished
+    // permuted copies for the tile kernels: built and uploaded by pnl_tile_order_ready once the search has finished; 2D P1 also the
+    // lane layout of the uniform-tile kernels, which reads the slots of the blocks (so the job starts behind block_dofs)
     ctx->have_tile_order = false;
-    if (reorder) { ctx->tile_job->cellv = F.cellv; ctx->tile_job->cdof = F.cdof; ctx->tile_job->cslot = F.cslot; }
+    ctx->uni_lanes_up = -1;
+    if (dpe == nV && dim == 2) start_tile_order_search(ctx, F, reorder);
     if ((rc = touching_cell_pairs(ctx, F))) return rc;
     if (ctx->nlab > 0 && (int)ctx->cell_labels.size() != nc) return fail(ctx, PNL_ERR_STATE, "cell labels do not match the mesh");
     if ((rc = upload_touching_pairs(ctx))) return rc;
@@ -699,7 +924,7 @@ const char *const k_product_options[] = {"PNL_WL_FRAC", "PNL_FH_NOTILES", "PNL_N
                                          "PNL_NO_OVERLAP", "PNL_NO_FORK",
                                          // tests: at most this many workgroups of a persistent tile kernel (every workgroup then walks
                                          // many tiles at test sizes: the pipelined tile loops against the oracle)
-                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_UNI_CHECKED", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED", "PNL_SETTLED_CODES",
+                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_UNI_CHECKED", "PNL_UNI_LANES", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED", "PNL_SETTLED_CODES",
                                          // staged fold of the dense 2D P1 assembly: far bands (0: one fold behind all tiles), spare workgroup
                                          // slots per CU of the far uniform launches, where the boundary term starts (3 / 4)
                                          "PNL_FOLD_STAGES", "PNL_UNI_SPARE", "PNL_BND_MODE"};
@@ -1809,6 +2034,47 @@ int pnl_get_settled_lists(pnl_context *ctx, uint16_t *codes, uint16_t *lists, in
         HIPCHK(ctx, hipMemcpy(lists, ctx->b_lists.p, (size_t)n*PNL_LIST_STRIDE*sizeof(uint16_t), hipMemcpyDeviceToHost));
     }
     return ctx->b_lists.p ? ctx->n_settled : 0;
+}
+
+int pnl_uniform_lane_layout(int nc, const int32_t *cells, const int32_t *dofs, int mode, int nthreads, int32_t *sizes, uint8_t *lane_cell,
+                            int16_t *lds_col, int8_t *vorder, int16_t *cell_col, double *mult, double *seconds) {
+    if (nc <= 0 || !cells || !dofs || !sizes || mode < 0 || mode > 2) return PNL_ERR_INVALID;
+    const int T = 64, nblocks = (nc+T-1)/T, ncp = nblocks*T;
+    // unique DoFs per block and the slots of the cells, as finalize() makes them
+    std::vector<int16_t> cslot((size_t)3*ncp, -1);
+    std::vector<std::vector<int>> lists(nblocks);
+    int nU = 1;
+    for (int b = 0; b < nblocks; b++) {
+        auto &L = lists[b];
+        for (int c = b*T; c < std::min(nc, (b+1)*T); c++) for (int k = 0; k < 3; k++) if (dofs[(size_t)c*3+k] >= 0) L.push_back(dofs[(size_t)c*3+k]);
+        std::sort(L.begin(), L.end());
+        L.erase(std::unique(L.begin(), L.end()), L.end());
+        nU = std::max<int>(nU, (int)L.size());
+    }
+    sizes[0] = nblocks; sizes[1] = nU; sizes[2] = mode == 0 ? 0 : 16*uni_lane_cap(nU)+16; sizes[3] = ncp;
+    if (!lane_cell || !lds_col || !vorder || !cell_col || !mult) return PNL_OK;
+    std::vector<int> cl(cells, cells+(size_t)nc*3), lperm((size_t)nc*3);
+    for (int c = 0; c < nc; c++) for (int k = 0; k < 3; k++) lperm[(size_t)c*3+k] = k;
+    host_threads([&](int th, int nthr) {
+        for (int b = th; b < nblocks; b += nthr) tile_order_block(b, nc, T, cl.data(), lperm.data());
+    }, nthreads);
+    for (int c = 0; c < nc; c++)
+        for (int k = 0; k < 3; k++) {
+            const int g = dofs[(size_t)c*3+lperm[(size_t)c*3+k]];
+            const auto &L = lists[c/T];
+            if (g >= 0) cslot[(size_t)k*ncp+c] = (int16_t)(std::lower_bound(L.begin(), L.end(), g)-L.begin());
+        }
+    const auto t0 = std::chrono::steady_clock::now();
+    UniLaneTables tabs[3];
+    uni_lane_layout(nblocks, ncp, nU, cslot.data(), tabs, nthreads);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now()-t0).count();
+    const UniLaneTables &R = tabs[mode];
+    std::copy(R.lane_cell.begin(), R.lane_cell.end(), lane_cell);
+    std::copy(R.lds_col.begin(), R.lds_col.end(), lds_col);
+    std::copy(R.cell_col.begin(), R.cell_col.end(), cell_col);
+    std::copy(R.mult.begin(), R.mult.end(), mult);
+    for (size_t i = 0; i < lperm.size(); i++) vorder[i] = (int8_t)lperm[i];
+    return PNL_OK;
 }
 
 int pnl_get_fold_plan(pnl_context *ctx, int32_t *images, int64_t nimages, int8_t *tile_stage, int8_t *tile_order, int64_t ntiles) {

@@ -200,7 +200,7 @@ __host__ __device__ constexpr size_t uniform_fixed_lds(int dpe, int np, int tile
     // per-cell rows have odd strides (in doubles / ints): the lanes of a wave read the rows of 64 different cells
     // (P1; the P2 kernels, two workgroups of just under 80 KB per CU, keep compact rows and the vertices of the a-cells)
     return dpe == 3 ? sizeof(double)*(size_t)(2*tile*(np*2+1)+2*tile+2*tile*(np|1)+(dpe*(dpe+1)/2)*np)
-                      +sizeof(int)*(size_t)(2*tile*(dpe|1)+2*tile+2+(dof_lists ? 4*nUe : 0))
+                      +sizeof(int)*(size_t)(2*tile*(dpe|1)+2*tile+2+nUe+tile+(dof_lists ? 4*nUe : 0))
                     : sizeof(double)*(size_t)(tile*np*2+tile*6+2*tile+2*tile*np+(dpe*(dpe+1)/2)*np)
                       +sizeof(int)*(size_t)(2*tile*dpe+2*tile+(dof_lists ? 4*nUe : 0));
 }
@@ -234,8 +234,14 @@ __host__ __device__ constexpr size_t uniform_fixed_lds(int dpe, int np, int tile
 //             order-2 kernel of s = 1/2 20 -> 64 bytes, of the 6-point one 0 -> 20) for three instructions per pair less.
 //   constants the orbit constants of the structured rules and their products are formed in front of the loop and kept in scalar registers
 //             (uniform_f64), the opaque constant of kern_eval is made once (kern_opaque_const); the same operations on the same operands.
-//   offsets   s_slotb and s_sa hold byte offsets into the sub-block; the index of the b-cell does not travel, the lane that meets a
-//             cell last computes it behind the loop.
+//   offsets   s_slotb and s_sa hold byte offsets into the sub-block; the index of the travelling cell does not travel, the lane that
+//             meets a cell last computes it behind the loop.
+//   lanes     (UniLanes, pnl_device.h) the lanes own the cells of the COLUMN block tb and the cells of the row block ta travel: the
+//             address of a sub-block add is row(travelling cell) * stride + column(lane's cell), and with a stride that is a multiple of
+//             16 doubles its LDS double-bank is the column mod 16, fixed per lane.  Lane l of either side holds cell lane_cell[block][l],
+//             the columns are lds_col[tb][slot] (trash columns per cell: cell_col), both chosen on the host so that the 16 lanes of a
+//             ds_add_f64 group hold 16 different banks.  The arrays named after the a side (s_x, s_sa, s_ha, s_vola, s_Ra) therefore
+//             hold the cells of tb, those named after the b side the cells of ta.  Any table gives the same sums: the adds are atomics.
 __device__ __forceinline__ double uniform_f64(double v) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
@@ -248,7 +254,7 @@ template <int DPE, int NP, int KT, bool STRUCT = false>
 __global__ void __launch_bounds__(256, (DPE == 3 && NP == 3) ? (KT == 0 ? PNL_U33K0_WAVES : (KT == 2 ? 4 : 2)) : ((DPE == 3 && NP == 6) ? 3 : 2))
 k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__restrict__ tile_cls, const DevKernel *__restrict__ kcls,
                int ntiles, double *__restrict__ A, long long ldA, double *__restrict__ Dglob, int acc_stride, int q_uniform,
-               int flags, const double *__restrict__ rule_g, int nUe, const SlotOut SO, unsigned *__restrict__ tile_ctr) {
+               int flags, const double *__restrict__ rule_g, int nUe, const SlotOut SO, unsigned *__restrict__ tile_ctr, const UniLanes UL) {
     const int flags_in = flags;
     constexpr int DIM = 2, NV = 3, NC = 6, ND = DPE*(DPE+1)/2, NT = 256, NW = NT/64;
     constexpr int TILE = DPE == 6 ? 32 : 64, HALVES = 64/TILE, JW = TILE/NW, ITER = JW/HALVES;
@@ -280,7 +286,9 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
     int *s_hb = s_ha+TILE;
     int *s_next = s_hb+TILE;                             // [2] P1: the next tile of this workgroup (ticket); two 16-bit flags: every
                                                          // a-cell (low half) / b-cell (high half) of the staged tile is real and has a DoF
-    int *s_dof = s_next+(DPE == 3 ? 2 : 0);              // [2][2][nUe] global DoFs of both blocks (ping-pong over tiles);
+    short *s_fcol = (short*)(s_next+(DPE == 3 ? 2 : 0)); // P1: [2][nUe] LDS column of the slots of block tb (ping-pong over tiles)
+    unsigned char *s_lc = (unsigned char*)(s_fcol+(P1 ? 2*nUe : 0));     // P1: [2][2][TILE] lane position of a cell: travelling side (ta), lane side (tb)
+    int *s_dof = (int*)(s_lc+(P1 ? 4*TILE : 0));         // [2][2][nUe] global DoFs of both blocks (ping-pong over tiles);
     const bool dof_lists = SO.A2 == nullptr;             // not with the block-slot storage (uniform_fixed_lds)
     double *s_acc = (double*)(s_dof+(dof_lists ? 4*nUe : 0));    // [nUe+1][acc_stride]; nUe even
     // tables of the general power (KT == 0) behind the sub-block, if the launcher made room for them (bit 8 of flags: they
@@ -299,17 +307,23 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
         const int2 tl = tiles[t];
         const int nA = P.blk_ndof[tl.x], nB = P.blk_ndof[tl.y];
         if (tid < 2*TILE) {
+            // bside: the travelling side.  P2: the cells of tb, lane = cell; P1: the cells of ta, in the lane order of the block
             const bool bside = tid < TILE;
-            const int l = bside ? tid : tid-TILE, c = (bside ? tl.y : tl.x)*TILE+l;
+            const int l = bside ? tid : tid-TILE, blk = (bside != P1) ? tl.y : tl.x;
+            // P1: c is a lane position, the tables are in lane order (UniLanes); the cell itself is needed by the flush of the diagonal blocks
+            const int c = blk*TILE+l;
             double v[NC];
 #pragma unroll
-            for (int k = 0; k < NC; k++) v[k] = P.cellv[(size_t)k*P.ncp+c];
-            const double vol = P.cvol[c];
+            for (int k = 0; k < NC; k++) v[k] = P1 ? UL.cellv[(size_t)k*P.ncp+c] : P.cellv[(size_t)k*P.ncp+c];
+            const double vol = P1 ? UL.cvol[c] : P.cvol[c];
             int sl[DPE], any = 0;
 #pragma unroll
-            for (int k = 0; k < DPE; k++) { sl[k] = P.cslot[(size_t)k*P.ncp+c]; any |= (sl[k] >= 0); }
+            for (int k = 0; k < DPE; k++) { sl[k] = P1 ? UL.cslot[(size_t)k*P.ncp+c] : P.cslot[(size_t)k*P.ncp+c]; any |= (sl[k] >= 0); }
             // bit 1: a real cell (zero-volume padding cells inside the mesh carry negative vertex ids: their pairs do not exist)
-            any |= (P.cvid[c] >= 0) ? 2 : 0;
+            if constexpr (P1) {
+                any |= UL.real[c] ? 2 : 0;
+                s_lc[(buf*2+(bside ? 0 : 1))*TILE+UL.lane_cell[c]] = (unsigned char)l;
+            } else any |= (P.cvid[c] >= 0) ? 2 : 0;
             if constexpr (P1) {
                 // one wave per side: are all its cells real and with a DoF?
                 const bool all = __ballot(any == 3) == ~0ull;
@@ -335,12 +349,22 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
             if (bside) {
                 s_volb[l] = vol; s_hb[l] = any;
 #pragma unroll
-                for (int k = 0; k < DPE; k++) s_slotb[l*SS+k] = (sl[k] >= 0 ? sl[k] : nUe)*OFFB;
+                for (int k = 0; k < DPE; k++) s_slotb[l*SS+k] = P1 ? (sl[k] >= 0 ? sl[k] : nUe)*acc_stride*OFFB : (sl[k] >= 0 ? sl[k] : nUe)*OFFB;
             } else {
                 s_vola[l] = vol; s_ha[l] = any;
 #pragma unroll
-                for (int k = 0; k < DPE; k++) s_sa[l*SS+k] = (sl[k] >= 0 ? sl[k] : nUe)*acc_stride*OFFB;
+                for (int k = 0; k < DPE; k++) {
+                    if constexpr (P1) s_sa[l*SS+k] = (int)UL.cell_col[(size_t)k*P.ncp+c]*OFFB;
+                    else s_sa[l*SS+k] = (sl[k] >= 0 ? sl[k] : nUe)*acc_stride*OFFB;
+                }
             }
+        }
+        if constexpr (P1) {
+            // the idle half of the workgroup: the LDS columns of the slots of tb, for the flush
+            if (tid >= 2*TILE && tid-2*TILE < nB) s_fcol[buf*nUe+tid-2*TILE] = UL.lds_col[(size_t)tl.y*P.blk_stride+tid-2*TILE];
+            if (nB > NT-2*TILE)
+#pragma unroll 1
+                for (int k = tid+NT-2*TILE; k < nB; k += NT) s_fcol[buf*nUe+k] = UL.lds_col[(size_t)tl.y*P.blk_stride+k];
         }
         const int *__restrict__ dofA = P.blk_dofs+(size_t)tl.x*P.blk_stride;
         const int *__restrict__ dofB = P.blk_dofs+(size_t)tl.y*P.blk_stride;
@@ -467,13 +491,13 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                 // every pair of the tile exists.  The product is made in both arms (opaque: the compiler would join the volumes and
                 // multiply once, which costs the copy of a register pair here)
                 npairs += 64;
-                vv = scale2*vola*volb_j;
+                vv = P1 ? scale2*volb_j*vola : scale2*vola*volb_j;       // P1: the travelling cell is the a-cell
                 asm("" : "+v"(vv));
             } else {
                 const bool valid = (((fa | fb) & 1) != 0) && (((fa & fb) & 2) != 0);
                 npairs += (unsigned long long)__popcll(__ballot(valid));
                 const double volb = valid ? volb_j : 0.;
-                vv = scale2*vola*volb;
+                vv = P1 ? scale2*volb*vola : scale2*vola*volb;
                 if constexpr (P1) {
                     asm("" : "+v"(vv));
                     fb = __builtin_amdgcn_update_dpp(0, fb, 0x134, 0xf, 0xf, true);    // the flags travel in the tiles that read them
@@ -494,7 +518,9 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                 double sr[3], sc[3];
 #pragma unroll
                 for (int a = 0; a < 3; a++) { sr[a] = (g[a][0]+g[a][1])+g[a][2]; sc[a] = (g[0][a]+g[1][a])+g[2][a]; }
-                const double S = (sr[0]+sr[1])+sr[2];
+                // the first index of g is the point of the lane's cell (column side), the second the point of the travelling cell (row
+                // side): sc holds the row sums of the entry's row side, and T stays with them
+                const double S = (sc[0]+sc[1])+sc[2];
                 const double vvw = vv*qw;
 #pragma unroll
                 for (int a = 0; a < 3; a++) {
@@ -505,11 +531,11 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                     const double k2 = -vv*qk2, k1 = -vv*qk1, T = (-vv*qk0)*S;
                     double ra[3], cb[3];
 #pragma unroll
-                    for (int a = 0; a < 3; a++) { ra[a] = __builtin_fma(k1, sr[a], T); cb[a] = k1*sc[a]; }
+                    for (int a = 0; a < 3; a++) { ra[a] = __builtin_fma(k1, sc[a], T); cb[a] = k1*sr[a]; }
 #pragma unroll
                     for (int b = 0; b < 3; b++)
 #pragma unroll
-                        for (int a = 0; a < 3; a++) lds_add_f64((double*)((char*)s_acc+(sa[a]+sbj[b])), __builtin_fma(k2, g[a][b], ra[a]+cb[b]));
+                        for (int a = 0; a < 3; a++) lds_add_f64((double*)((char*)s_acc+(sa[a]+sbj[b])), __builtin_fma(k2, g[a][b], ra[b]+cb[a]));
                 } else if (S == 1.2345e300) s_acc[0] = vv;
                 continue;
             }
@@ -619,18 +645,27 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
         if (more) stage(nxt, buf^1);
         const int *__restrict__ dA = s_dof+(buf*2+0)*nUe, *__restrict__ dB = s_dof+(buf*2+1)*nUe;
         const bool sym = (flags & 1) != 0 && dof_lists;
+        auto fcol = [&](int cc) { if constexpr (P1) return (int)s_fcol[buf*nUe+cc]; else return cc; };       // LDS column of slot cc of tb
         if (SO.A2) {
             // block-slot storage: this tile owns its nA x nB sub-block, plain 16-byte stores of every entry
             // (writing the padded width, whole 64-byte lines, was measured: no less traffic, the fold 1 ms slower)
             const int ca = SO.colbase[ta], W = SO.S-ca;
             double *__restrict__ base = SO.A2+SO.rowoff[ta]+(SO.colbase[tb]-ca);
+            // the columns of this lane's first two slots once, not per row (the stores to the sub-block keep the compiler from it)
+            int fc0 = 0, fc1 = 0;
+            if constexpr (P1) { fc0 = 2*lane < nB ? fcol(2*lane) : 0; fc1 = 2*lane+1 < nB ? fcol(2*lane+1) : 0; }
 #pragma unroll 1
             for (int r = wv; r < nA; r += NW) {
                 double *__restrict__ row = base+(long long)r*W;
                 for (int cc = 2*lane; cc < nB; cc += 128) {
                     double2 v = make_double2(0., 0.);
-                    if (cc < nB) { v.x = s_acc[r*acc_stride+cc]; s_acc[r*acc_stride+cc] = 0.; }
-                    if (cc+1 < nB) { v.y = s_acc[r*acc_stride+cc+1]; s_acc[r*acc_stride+cc+1] = 0.; }
+                    if constexpr (P1) {
+                        if (cc < nB) { const int k0 = r*acc_stride+(cc < 128 ? fc0 : fcol(cc)); v.x = s_acc[k0]; s_acc[k0] = 0.; }
+                        if (cc+1 < nB) { const int k1 = r*acc_stride+(cc < 128 ? fc1 : fcol(cc+1)); v.y = s_acc[k1]; s_acc[k1] = 0.; }
+                    } else {
+                        if (cc < nB) { v.x = s_acc[r*acc_stride+cc]; s_acc[r*acc_stride+cc] = 0.; }
+                        if (cc+1 < nB) { v.y = s_acc[r*acc_stride+cc+1]; s_acc[r*acc_stride+cc+1] = 0.; }
+                    }
                     slot_store2(row+cc, v.x, v.y);
                 }
             }
@@ -639,9 +674,9 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
         for (int r = wv; r < nA; r += NW) {
             double *__restrict__ row = A+(long long)__builtin_amdgcn_readfirstlane(dA[r])*ldA;
             for (int cc = lane; cc < nB; cc += 64) {
-                const double v = s_acc[r*acc_stride+cc];
+                const double v = s_acc[r*acc_stride+fcol(cc)];
                 if (v != 0.) {
-                    if (!sym) s_acc[r*acc_stride+cc] = 0.;
+                    if (!sym) s_acc[r*acc_stride+fcol(cc)] = 0.;
                     atomic_add_f64(&row[dB[cc]], v);
                 }
             }
@@ -654,9 +689,9 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
             for (int cc = wv; cc < nB; cc += NW) {
                 double *__restrict__ row = A+(long long)__builtin_amdgcn_readfirstlane(dB[cc])*ldA;
                 for (int r = lane; r < nA; r += 64) {
-                    const double v = s_acc[r*acc_stride+cc];
+                    const double v = s_acc[r*acc_stride+fcol(cc)];
                     if (v != 0.) {
-                        s_acc[r*acc_stride+cc] = 0.;
+                        s_acc[r*acc_stride+fcol(cc)] = 0.;
                         atomic_add_f64(&row[dA[r]], v);
                     }
                 }
@@ -669,7 +704,12 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
             constexpr int PARTS = NT/(2*TILE);
             static_assert(PARTS*2*TILE == NT && 64%PARTS == 0, "one (side, cell) per group of PARTS lanes");
             const int item = tid/PARTS, part = tid-item*PARTS, side = item/TILE, cl = item-side*TILE;
-            double *__restrict__ R = (side ? s_Rb : s_Ra)+cl*RS;
+            // P1: s_Rb holds the sums of the travelling cells (ta), s_Ra those of the lanes' cells (tb), both in lane positions.  The items
+            // walk the CELLS in order and look their lane position up, so that a wave's atomics fall on neighbouring diagonal blocks
+            // (items in lane order spread them over twice the cache lines: 1.8 us per tile)
+            const int pos = P1 ? (int)s_lc[(buf*2+(side ? 0 : 1))*TILE+cl] : cl;
+            double *__restrict__ R = (side ? s_Rb : s_Ra)+pos*RS;
+            const int dcell = (P1 ? (side ? ta : tb) : (side ? tb : ta))*TILE+cl;
             double Rv[NP];
 #pragma unroll
             for (int ip = 0; ip < NP; ip++) Rv[ip] = R[ip];
@@ -680,7 +720,7 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                 double v = 0.;
 #pragma unroll
                 for (int ip = 0; ip < NP; ip++) v = __builtin_fma(s_PP[e*NP+ip], Rv[ip], v);
-                if (v != 0.) atomic_add_f64(&Dglob[(size_t)((side ? tb : ta)*TILE+cl)*ND+e], v);
+                if (v != 0.) atomic_add_f64(&Dglob[(size_t)dcell*ND+e], v);
             }
         }
         if (!more) break;

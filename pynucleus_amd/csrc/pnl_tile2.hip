@@ -16,6 +16,16 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
     int acc_stride = nUe+1;
     while (acc_stride % 32 != 1) acc_stride++;                      // (other odd residues mod 32 measured: no difference)
     if (fixed+sizeof(double)*(size_t)(nUe+1)*acc_stride > 80*1024) acc_stride = (nUe+1) | 1;
+    // P1: the lane layout of the option PNL_UNI_LANES (pnl_setup.hip).  Its tables come with a row stride that is a multiple of 16
+    // doubles, so that the bank of a sub-block add is the column of the lane's DoF mod 16; 0 (identity) keeps the rule above
+    UniLanes UL{};
+    int lanes_mode = 0;
+    if (DPE == 3) {
+        int st = 0;
+        const int rc = pnl_uni_lanes_ready(ctx, &UL, &lanes_mode, &st);
+        if (rc) return rc;
+        if (st > 0) acc_stride = st;
+    }
     size_t lds = fixed+sizeof(double)*(size_t)(nUe+1)*acc_stride;
     if (lds > 160*1024)
         return fail(ctx, PNL_ERR_UNSUPPORTED, "a block of %d cells touches %d DoFs: LDS sub-block of %zu bytes exceeds 160 KiB", TILE, ctx->nU, lds);
@@ -42,7 +52,7 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
         const size_t tab = sizeof(double)*PNL_POW_TAB_DOUBLES;
         const int per_cu0 = resident(lds);
         if (lds+tab <= 160*1024 && resident(lds+tab) == per_cu0) { lds += tab; pow_flag = 8; }
-        else if (!pnl_tune("PNL_UNI_KEEP_STRIDE")) {
+        else if (lanes_mode == 0 && !pnl_tune("PNL_UNI_KEEP_STRIDE")) {
             // the padded row stride of the sub-block (fewer LDS bank conflicts) or the tables: the tables win (measured)
             const int odd = (nUe+1) | 1;
             const size_t alt = fixed+sizeof(double)*(size_t)(nUe+1)*odd+tab;
@@ -69,6 +79,13 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
     if (pnl_tune("PNL_VERBOSE"))
         fprintf(stderr, "[pnl] uniform tiles of order %d: %d, dpe=%d np=%d kt=%d struct=%d lds=%zu bytes (%d per CU), acc_stride=%d\n", q, ntiles, DPE,
                 NP, KT, (int)STRUCT, lds, per_cu, acc_stride);
+    if (DPE == 3 && pnl_tune("PNL_VERBOSE")) {
+        const std::vector<double> &m = ctx->uni_lanes[lanes_mode].mult;
+        double sum = 0.;
+        for (double v : m) sum += v;
+        fprintf(stderr, "[pnl] lane layout %d: modelled LDS cycles per sub-block add %.3f of the conflict-free ones (mean of %zu blocks), layout of all blocks %.3f s\n",
+                lanes_mode, m.empty() ? 0. : sum/(double)m.size(), m.size(), ctx->uni_lanes_seconds);
+    }
     const int uni_checked = (DPE == 3 && pnl_tune("PNL_UNI_CHECKED")) ? PNL_UNI_FLAG_CHECKED : 0;      // tests: no tile skips the validity test
     int uni_abl = 0;
 #ifdef PNL_DEBUG_ABLATE
@@ -77,7 +94,7 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
     kt_begin(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     hipLaunchKernelGGL(kfun, dim3(grid), dim3(256), lds, ctx->stream, Pt, tiles, tile_cls, (const DevKernel*)ctx->b_kcls.p, ntiles, A,
                        (long long)ldA, Dglob, acc_stride, q, (ctx->run.symflush ? 1 : 0) | uni_abl | pow_flag | uni_checked, (const double*)ctx->b_uni.p+ctx->uni_off[q],
-                       nUe, SO, ctr);
+                       nUe, SO, ctr, UL);
     kt_end(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;

@@ -2,6 +2,12 @@
 // nine addresses per iteration like the cross block of a P1 pair.  Patterns: 0 every lane its own consecutive element (no bank
 // conflict), 1 lane l -> row l of a sub-block with row stride 65 doubles (the tile kernels), 2 the same with pairs of lanes sharing
 // the address (two cells with a common DoF), 3 all lanes one address.
+// Patterns 100+ place lane l at double (row(l)*64 + bank(l)) of the wave's own 1024 doubles, so that the row never changes the
+// bank under any modulus up to 128 dwords; they separate the lane grouping and the conflict cost of ds_add_f64:
+//   100 bank l%16, row l/16: distinct inside each contiguous 16-lane group, lanes l and l+16 on one bank at different addresses
+//   101 bank (l/4)%16, row l%4: 4-way inside contiguous 16-lane groups, free if the groups were strided
+//   102/103/104 2-, 3-, 4-way inside every 16-lane group;  105 two lanes of a group on one address
+//   106 2-way in group 0 only (is the cost the sum over the groups?);  107 bank 2*(l%16): 2-way under mod 32 dwords, free under mod 64
 // build: hipcc --offload-arch=gfx950 -O3 -o lds_atomic_probe lds_atomic_probe.hip ; run: ./lds_atomic_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -19,6 +25,18 @@ __global__ void __launch_bounds__(256) k_probe(double *out, int iters, int patte
     else if (pattern == 1) base = (lane*65+wave) % (NEL-16);
     else if (pattern == 2) base = ((lane >> 1)*65+wave) % (NEL-16);
     else if (pattern == 3) base = wave;
+    else if (pattern >= 100) {
+        const int g = lane >> 4, i = lane & 15;
+        int bank = i, row = g;
+        if (pattern == 101) { bank = (lane >> 2) & 15; row = lane & 3; }
+        if (pattern == 102) { bank = i >> 1; row = (i & 1)+2*g; }
+        if (pattern == 103) { bank = i/3; row = (i % 3)+3*g; }
+        if (pattern == 104) { bank = i >> 2; row = (i & 3)+4*g; }
+        if (pattern == 105) { bank = i >> 1; row = g; }
+        if (pattern == 106) { bank = g == 0 ? (i >> 1) : i; row = (i & 1)+2*g; }
+        if (pattern == 107) { bank = 2*i; row = g; }
+        base = wave*1024+row*64+bank;                          // < 3*1024 + 16*64 + 32, and + 56 below stays inside NEL
+    }
     else base = (lane*(pattern-3)+wave) % (NEL-64);            // pattern 4 + k: lane stride k+1 doubles (bank structure)
     double v = 1.0+tid, acc = 0.;
     float vf = 1.f+tid;
@@ -69,6 +87,10 @@ int main() {
     // lane strides 1, 2, 4, 8, 16, 32, 64 doubles and 3, 5, 17, 33
     const int strides[] = {1, 2, 4, 8, 16, 32, 64, 3, 5, 17, 33};
     for (int k = 0; k < 11; k++) run<0>("ds_add_f64 stride", out, 3+strides[k]);
+    for (int p = 100; p < 108; p++) {
+        run<0>("ds_add_f64", out, p);
+        run<2>("ds_write_b64", out, p);
+    }
     hipFree(out);
     return 0;
 }
