@@ -120,12 +120,6 @@ enum pnl_counter {
  *                     of a settled tile from its codes in every assembly (tests and A/B measurement; read when the plan is made,
  *                     changing it makes a new plan).  The plan does the same by itself where the device has no memory for the lists,
  *   "PNL_NO_OVERLAP", "PNL_NO_FORK"   profiling: no side streams, every phase on the caller's stream one after the other,
- *   "PNL_FOLD_STAGES" dense 2D P1 assembly of one order class: number of far bands of the staged fold (pnl_get_fold_stages); 0: one
- *                     fold of the whole matrix behind all tile kernels (the default),
- *   "PNL_UNI_SPARE"   staged fold: workgroup slots per CU that the uniform-tile launches of the far bands leave to the folds, the
- *                     work list and the touching pairs running beside them,
- *   "PNL_BND_MODE"    where the Omega x Omega^c term starts: 3 on its side stream behind the last tile kernel, 4 behind the tile
- *                     kernels of stage 0 of a staged fold,
  *   "PNL_VERBOSE", "PNL_PLAN_TIMING"   diagnostics on stderr,
  * and returns PNL_ERR_UNSUPPORTED for any other name.  A tuning build (make EXTRA=-DPNL_TUNING; pnl_version says so) accepts every
  * name and falls back to the environment: the A/B switches named in DESIGN.md live there. */
@@ -398,22 +392,8 @@ int pnl_assemble_boundary_masked_pointwise(pnl_context *ctx, int ni, const int32
 int pnl_get_counters(pnl_context *ctx, int64_t *out, int n);
 /* device time of the last assemble call per phase in milliseconds (HIP events on the context's stream):
  * [0] general tile kernel (distant pairs, one per lane), [1] work-list kernels (high orders),
- * [2] singular pairs, [3] boundary term, [4] mirror + diagonal scatter, [5] total, [6] uniform-tile kernel.
- * With a staged fold (pnl_get_fold_stages reports more than one stage) the phases overlap and the slots are intervals of the
- * caller's stream: [6] the uniform tiles of stage 0, [0] the mixed tiles and the uniform tiles of the later stages, [1] what is
- * left of the folds and the work list behind the last tile kernel, [2] what is then left of the touching pairs, [3] of the
- * boundary term, [4] diagonal scatter, [5] total, first launch to last as before. */
+ * [2] singular pairs, [3] boundary term, [4] mirror + diagonal scatter, [5] total, [6] uniform-tile kernel. */
 int pnl_get_phase_ms(pnl_context *ctx, float *out, int n);
-/* Stages of the fold of the resident dense tile plan (2D P1, one order class; the plan is made by the first assembly).  Stage 0: the
- * 32 x 32 images of the matrix that receive anything but uniform-order tiles, with all tiles of these images; stages 1 .. K: the other
- * uniform tiles by bands of block rows, every image in the largest stage of its tiles.  out[5 s + 0 .. 4]: images, uniform tiles of
- * order 2, 3, 4 and mixed tiles of stage s < n.  Returns the number of stages (1: no staging), or an error. */
-int pnl_get_fold_stages(pnl_context *ctx, int64_t *out, int n);
-/* The staged plan itself (tests): images[nimages][3] = (row range, column range, stage) of every image of the upper block triangle,
- * ranges of 32 DoFs; tile_stage / tile_order[ntiles], ntiles = nblocks^2 with nblocks = ceil(cells / pnl_tile_cells): stage of tile
- * (a, b) at a nblocks + b (-1 below the diagonal) and its uniform order 2 .. 4, 0 for the other tiles.  NULL skips an output;
- * PNL_ERR_STATE without stages. */
-int pnl_get_fold_plan(pnl_context *ctx, int32_t *images, int64_t nimages, int8_t *tile_stage, int8_t *tile_order, int64_t ntiles);
 /* The settled tiles of the resident dense tile plan (tests): tiles[i][2] = (block a, block b) of the first ntiles of them, in the order
  * of the launch (most pairs of a 6-point rule first).  Returns their number (0: the plan settles nothing), or an error. */
 int pnl_get_settled_tiles(pnl_context *ctx, int32_t *tiles, int64_t ntiles);
@@ -436,7 +416,7 @@ int pnl_get_settled_lists(pnl_context *ctx, uint16_t *codes, uint16_t *lists, in
 int pnl_uniform_lane_layout(int nc, const int32_t *cells, const int32_t *dofs, int mode, int nthreads, int32_t *sizes, uint8_t *lane_cell,
                             int16_t *lds_col, int8_t *vorder, int16_t *cell_col, double *mult, double *seconds);
 /* device time of the tile kernels of the last assemble call, one HIP-event pair around each launch (milliseconds, 0 if the
- * kernel did not run; a slot that was launched several times -- stages of a staged fold, order classes -- holds the sum over
+ * kernel did not run; a slot that was launched several times -- order classes -- holds the sum over
  * its launches): [0] general tile kernel, [1] uniform tiles of
  * order 2, [2] order 3, [3] order 4, [4] fold + mirror of the block-slot storage, [5] work-list kernels, [6] the launch of the general
  * tile kernel over the settled tiles (part of [0]) */

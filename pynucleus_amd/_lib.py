@@ -27,7 +27,7 @@ PNL_NUM_COUNTERS = 140
 EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_set_stream', 'pnl_synchronize',
            'pnl_upload_mesh', 'pnl_upload_dofmap', 'pnl_set_kernel', 'pnl_set_order_formula', 'pnl_upload_distant_rules',
            'pnl_upload_singular_rule', 'pnl_upload_boundary', 'pnl_assemble_dense', 'pnl_dense_overwrites', 'pnl_block_row_costs', 'pnl_tile_cells',
-           'pnl_assemble_dense_tiles', 'pnl_get_counters', 'pnl_get_phase_ms', 'pnl_get_kernel_ms', 'pnl_get_fold_stages', 'pnl_get_fold_plan', 'pnl_get_settled_tiles', 'pnl_tree_build', 'pnl_tree_build_blocks', 'pnl_tree_build_refined', 'pnl_tree_build_horizon', 'pnl_tree_build_device', 'pnl_tree_destroy', 'pnl_tree_sizes', 'pnl_tree_get', 'pnl_tree_node_cells', 'pnl_h2_transfer_matrices', 'pnl_nfplan_build', 'pnl_nfplan_destroy', 'pnl_nfplan_sizes', 'pnl_nfplan_get', 'pnl_horizon_pattern', 'pnl_near_pattern', 'pnl_pattern_set_max_nnz', 'pnl_set_option', 'pnl_set_cell_order', 'pnl_set_interaction_transform', 'pnl_set_order_vertex_values', 'pnl_h2_get', 'pnl_h2_set', 'pnl_pattern_nnz', 'pnl_pattern_get', 'pnl_pattern_destroy', 'pnl_set_row_slab', 'pnl_diag_blocks_size', 'pnl_get_diag_blocks', 'pnl_slab_matvec', 'pnl_slab_diagonal', 'pnl_gemv', 'pnl_cg_jacobi',
+           'pnl_assemble_dense_tiles', 'pnl_get_counters', 'pnl_get_phase_ms', 'pnl_get_kernel_ms', 'pnl_get_settled_tiles', 'pnl_tree_build', 'pnl_tree_build_blocks', 'pnl_tree_build_refined', 'pnl_tree_build_horizon', 'pnl_tree_build_device', 'pnl_tree_destroy', 'pnl_tree_sizes', 'pnl_tree_get', 'pnl_tree_node_cells', 'pnl_h2_transfer_matrices', 'pnl_nfplan_build', 'pnl_nfplan_destroy', 'pnl_nfplan_sizes', 'pnl_nfplan_get', 'pnl_horizon_pattern', 'pnl_near_pattern', 'pnl_pattern_set_max_nnz', 'pnl_set_option', 'pnl_set_cell_order', 'pnl_set_interaction_transform', 'pnl_set_order_vertex_values', 'pnl_h2_get', 'pnl_h2_set', 'pnl_pattern_nnz', 'pnl_pattern_get', 'pnl_pattern_destroy', 'pnl_set_row_slab', 'pnl_diag_blocks_size', 'pnl_get_diag_blocks', 'pnl_slab_matvec', 'pnl_slab_diagonal', 'pnl_gemv', 'pnl_cg_jacobi',
            'pnl_inv_diagonal', 'pnl_set_classes', 'pnl_select_class', 'pnl_upload_sparsity', 'pnl_upload_sparsity_device', 'pnl_assemble_pairs_masked', 'pnl_assemble_boundary_masked', 'pnl_assemble_clusters_tiled', 'pnl_h2_setup', 'pnl_h2_matvec', 'pnl_h2_upward', 'pnl_h2_interact', 'pnl_h2_downward', 'pnl_h2_sizes', 'pnl_spmv',
            'pnl_assemble_pairs_in_horizon', 'pnl_assemble_pairs_in_horizon_range', 'pnl_set_nonsymmetric', 'pnl_set_order_function', 'pnl_upload_pointwise_rules', 'pnl_assemble_dense_pointwise',
            'pnl_assemble_pairs_masked_pointwise', 'pnl_assemble_boundary_masked_pointwise', 'pnl_get_settled_lists',
@@ -151,8 +151,6 @@ def load():
     L.pnl_get_counters.argtypes = [vp, vp, i32]
     L.pnl_get_phase_ms.argtypes = [vp, vp, i32]
     L.pnl_get_kernel_ms.argtypes = [vp, vp, i32]
-    L.pnl_get_fold_stages.argtypes = [vp, vp, i32]
-    L.pnl_get_fold_plan.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64]
     L.pnl_get_settled_tiles.argtypes = [vp, vp, C.c_int64]
     L.pnl_get_settled_lists.argtypes = [vp, vp, vp, C.c_int64]
     L.pnl_uniform_lane_layout.argtypes = [i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
@@ -626,14 +624,6 @@ class Context:
         return dict(tile_general=float(out[0]), tile_uniform2=float(out[1]), tile_uniform3=float(out[2]), tile_uniform4=float(out[3]),
                     fold_mirror=float(out[4]), worklist=float(out[5]), tile_settled=float(out[6]))
 
-    def fold_stages(self):
-        """stages of the fold of the resident dense tile plan: one dict per stage with the number of images, of uniform tiles per
-        order and of mixed tiles (one stage: no staging)"""
-        out = np.zeros((17, 5), dtype=np.int64)
-        n = self.L.pnl_get_fold_stages(self.h, out.ctypes.data, 17)
-        self.check(min(n, 0))
-        return [dict(images=int(r[0]), uniform={2: int(r[1]), 3: int(r[2]), 4: int(r[3])}, mixed=int(r[4])) for r in out[:n]]
-
     def settled_tiles(self):
         """the settled tiles (block a, block b) of the resident dense tile plan, [n, 2]"""
         n = self.L.pnl_get_settled_tiles(self.h, None, 0)
@@ -656,16 +646,6 @@ class Context:
         lists = np.zeros((n, 4104), dtype=np.uint16)
         self.check(min(self.L.pnl_get_settled_lists(self.h, None, lists.ctypes.data, n), 0))
         return codes, lists
-
-    def fold_plan(self, nblocks):
-        """the staged plan: images[:, 3] = (row range, column range, stage), stage and uniform order (0: none) of tile (a, b) as
-        [nblocks, nblocks] arrays (stage -1 below the diagonal)"""
-        nimg = sum(s['images'] for s in self.fold_stages())
-        images = np.zeros((nimg, 3), dtype=np.int32)
-        stage = np.zeros((nblocks, nblocks), dtype=np.int8)
-        order = np.zeros((nblocks, nblocks), dtype=np.int8)
-        self.check(self.L.pnl_get_fold_plan(self.h, images.ctypes.data, nimg, stage.ctypes.data, order.ctypes.data, nblocks*nblocks))
-        return images, stage, order
 
     def gemv(self, A_ptr, ldA, n, x_ptr, y_ptr, symmetric_half=False):
         self.check(self.L.pnl_gemv(self.h, C.c_void_p(A_ptr), int(ldA), int(n), C.c_void_p(x_ptr), C.c_void_p(y_ptr),

@@ -33,21 +33,21 @@ enum PhaseEvent {
     EV_BOUNDARY_DONE = 4,       // boundary term joined
     EV_END = 5,                 // diagonal blocks scattered
     EV_TILES_DONE = 6,          // last tile kernel (of the last class pass)
-    EV_TILES_UNIFORM_DONE = 7,  // uniform tiles (those of stage 0 with a staged fold)
+    EV_TILES_UNIFORM_DONE = 7,  // uniform tiles
     EV_COUNT = 8
 };
 
 // What one assembly leaves for its own later phases and for pnl_get_counters / pnl_get_phase_ms / pnl_get_kernel_ms, and what means
 // nothing for the next assembly.  pnl_begin_assembly starts every C-ABI assembly call with a fresh record; each path then sets only
-// what it knows.  Plan state that survives assemblies (tile lists, n_settled, stg_K, wl_cap ...) stays in the context.
+// what it knows.  Plan state that survives assemblies (tile lists, n_settled, wl_cap ...) stays in the context.
 struct AssemblyRun {
     bool ev_valid = false;          // the phase events are all recorded: false until the assembly has succeeded
     bool tiles_launched = false, pure_launched = false;     // phases "tiles" / "tiles_uniform" of pnl_get_phase_ms exist
     bool symflush = false;          // PNL_FLAG_SYMMETRIC_FLUSH
     bool tile_cell_filter = true;   // apply [cell_begin, cell_end) to the a-cells of the tiles too (not for a caller's tile list)
     bool full_tile_list = false;    // the tile list is the whole upper block triangle of the cell range (pnl_assemble_dense)
-    // the tile kernels wrote the block-slot storage; ev_fold is recorded behind a fold + mirror pass; the staged sequence runs
-    bool slot_used = false, fold_event_set = false, stg_active = false;
+    // the tile kernels wrote the block-slot storage; ev_fold is recorded behind a fold + mirror pass
+    bool slot_used = false, fold_event_set = false;
     int settled_run = 0;            // tiles taken through k_tile_distant<.., SETTLED>
     int lists_run = 0;              // ... of them through k_tile_distant<.., SETTLED, LISTS> (pair lists of the plan)
     int tile_off = 0, n_mixed = 0, n_pure = 0;      // slice of b_tiles of the class pass being launched (dense P1 / 1D)
@@ -78,10 +78,6 @@ struct pnl_context {
     // recorded behind the fold + mirror pass of a block-slot assembly: from here on A only receives atomic adds, so the touching
     // pairs and the boundary term run on side streams next to the work-list kernels (one order class)
     hipEvent_t ev_fold = nullptr;
-    // staged fold (pnl_hip.hip: launch_tiles): ev_stage[s] behind the last tile kernel of stage s on the caller's stream
-    static constexpr int MAX_STAGES = 16;    // far bands of a staged fold (stage 0 + bands)
-    hipEvent_t ev_stage[MAX_STAGES+1] = {};
-    hipEvent_t ev_bnd = nullptr;             // zero fill of the diagonal-block buffer + class tables of the boundary term are in the stream
     std::string err;
     // host copies
     int dim = 0, nv = 0, nc = 0, dpe = 0, dpv = 0, dped = 0, N = 0, nb = 0, qmax = -1;
@@ -139,19 +135,9 @@ struct pnl_context {
     int n_settled = 0, settled_want = -1, lists_want = -1;
     std::vector<int2> settled_tiles;              // host copy of the settled part of the list (pnl_get_settled_tiles)
     long long code_builds = 0;
-    // staged fold of the 2D P1 one-class path (pnl_setup.hip: stage_plan): blocks that hold a copy of a DoF of every range of 32 DoFs
-    // (CSR, from upload_slot_tables), per stage the packed images (range i << 16 | range j) in b_foldimg, per order and stage the offsets
-    // into the uniform lists; stg_K = 0: no stages (one fold of the whole matrix behind all tiles)
-    std::vector<int32_t> rng_blk_off, rng_blk;
-    DevBuf b_foldimg, b_unictr;
-    int stg_K = 0, stg_want = -1;                 // bands of the resident plan; PNL_FOLD_STAGES the plan was made for
-    std::vector<int> stg_img_off;                 // [stg_K + 2] offsets of the stages in b_foldimg
-    std::vector<int> stg_uni_off[3];              // [stg_K + 2] offsets of the stages in the uniform list of order 2, 3, 4
-    std::vector<unsigned> stg_img;                // host copy of b_foldimg (pnl_get_fold_plan)
-    std::vector<signed char> stg_tile_stage;      // [nblocks][nblocks] stage of tile (a, b), -1 below the diagonal
-    std::vector<unsigned char> stg_tile_q;        // [nblocks][nblocks] order 2 .. 4 of a uniform tile, else 0
     // ticket counters of the uniform-tile launches (b_unictr, UNI_CTRS words): an assembly zeroes all of them at its start and hands
     // them out in turn (AssemblyRun::uni_ctr_fresh left); launches beyond that zero their counter in the stream themselves
+    DevBuf b_unictr;
     static constexpr int UNI_CTRS = 64;
     long long slot_total = 0;         // doubles
     // row slab of a rank (pnl_set_row_slab, pnl_slab.hip)
@@ -223,7 +209,7 @@ struct pnl_context {
     std::vector<BlockAgg> blocks;
     hipEvent_t ev[EV_COUNT] = {};     // the phase events, by PhaseEvent
     // event pair around every tile-kernel launch (pnl_get_kernel_ms); a slot that is launched several times per assembly (the
-    // stages of a staged fold) takes one more pair per launch, created on first use and kept; AssemblyRun::kev_n counts the launches
+    // order classes) takes one more pair per launch, created on first use and kept; AssemblyRun::kev_n counts the launches
     std::vector<hipEvent_t> kev[PNL_NUM_KERNEL_SLOTS];
     AssemblyRun run;                // the assembly in progress or, behind it, the last one (pnl_begin_assembly)
     int ablate = 0;                 // debug: PNL_ABLATE env bits (1 no LDS accumulate, 2 no evaluation)
@@ -468,11 +454,11 @@ int pnl_launch_slab_two_sided(pnl_context *ctx, const double *slab, long long ld
 
 // pnl_tile2.hip
 int pnl2_launch_uniform(pnl_context *ctx, int kt, const DevProblem &Pt, const int2 *tiles, const int *tile_cls, int ntiles, int q,
-                        double *A, int64_t ldA, double *Dglob, const SlotOut &SO, int spare = 0);
+                        double *A, int64_t ldA, double *Dglob, const SlotOut &SO);
 int pnl2_launch_p2(pnl_context *ctx, int kt, const int2 *tiles, const int *tile_cls, int ntiles, double *A, int64_t ldA,
                    int cell_begin, int cell_end, unsigned wl_cap_each, const SlotOut &SO);
 int pnl2_zero_slot_tiles(pnl_context *ctx, const SlotOut &SO);
-int pnl2_fold_mirror(pnl_context *ctx, const SlotOut &SO, double *A, int64_t ldA, const unsigned *images = nullptr, int nimages = 0);
+int pnl2_fold_mirror(pnl_context *ctx, const SlotOut &SO, double *A, int64_t ldA);
 inline SlotOut slot_out(const pnl_context *ctx) {
     SlotOut SO;
     SO.A2 = (double*)ctx->b_slotA.p; SO.rowoff = (const long long*)ctx->b_srowoff.p; SO.colbase = (const int*)ctx->b_scolbase.p;

@@ -229,84 +229,10 @@ int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, 
     return PNL_OK;
 }
 
-// spare workgroup slots per CU of the uniform-tile launches of the stages >= 1 (option PNL_UNI_SPARE)
-#ifndef PNL_UNI_SPARE_DEFAULT
-#define PNL_UNI_SPARE_DEFAULT 1
-#endif
 template <int DIM, int DPE, int TILE, int KT>
 int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell_begin, int cell_end, const SlotOut &SO = SlotOut{}) {
     HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
     ctx->run.pure_launched = false;              // of this class pass
-    // Staged fold (option PNL_FOLD_STAGES > 0; 2D P1, one order class, block-slot storage; the plan: stage_plan in pnl_setup.hip).
-    // Measured at 98,304 cells, s = 1/2 (docs/CHANGELOG_kernels.md, round 6): no gain over the single fold for any number of bands --
-    // what the side kernels do beside the tile kernels, the tile kernels lose -- so the default is 0.  Caller's stream: the uniform
-    // tiles of stage 0, the mixed tiles, event; then per stage s >= 1 its uniform tiles on a grid that leaves `spare` workgroup
-    // slots per CU free, event.  The fold's side stream (aux[2]) folds stage s behind the event of stage s; behind the fold of stage 0
-    // (ev_fold) the work list (aux[3]) and the touching pairs (aux[0], assemble_impl) start on their side streams.  Every image of A that
-    // these add to belongs to stage 0, and the folds of the later stages write other images.  Side streams wait on events only;
-    // the ticket counters of the tile loops hand out work, no workgroup waits for another.  PNL_NO_OVERLAP: the same sequence on the
-    // caller's stream.
-    const bool staged = DIM == 2 && DPE == 3 && SO.A2 && ctx->stg_K > 0 && ctx->cls.size() == 1 && !ctx->nonsym;
-    ctx->run.stg_active = staged;
-    if (staged) {
-        int rc;
-        const int K = ctx->stg_K;
-        const int spare = pnl_tune("PNL_UNI_SPARE") ? atoi(pnl_tune("PNL_UNI_SPARE")) : PNL_UNI_SPARE_DEFAULT;
-        const bool side = !pnl_tune("PNL_NO_OVERLAP");
-        hipStream_t const caller = ctx->stream;
-        hipStream_t const folds = side ? ctx->aux[2] : caller;
-        // the work list on a side stream of its own (aux[3]) behind the fold of stage 0, not on the folds' stream in front of the later
-        // folds.  (Where the runtime maps five streams onto four hardware queues it may still share the queue of the folds' stream;
-        // measured with the work list on the other side streams as well, docs/CHANGELOG_kernels.md round 6: no gain either way)
-        constexpr int wl_aux = 3;
-        hipStream_t const wls = side ? ctx->aux[wl_aux] : caller;
-        const int2 *tiles = (const int2*)ctx->b_tiles.p+ctx->run.tile_off;
-        double *Dt = (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p);
-        unsigned *wlc = (unsigned*)ctx->b_wlcount.p+wl_slot;
-        auto uniform_stage = [&](int s, int spare_s) -> int {
-            int off = ctx->run.n_mixed;
-            for (int q = 2; q <= 4; q++) {
-                const std::vector<int> &so = ctx->stg_uni_off[q-2];
-                const int n = so[s+1]-so[s];
-                int rcu = pnl2_launch_uniform(ctx, KT, tile_problem(ctx), tiles+off+so[s], nullptr, n, q, A, ldA, Dt, SO, spare_s);
-                if (rcu) return rcu;
-                ctx->run.pure_launched = ctx->run.pure_launched || n > 0;
-                off += so[K+1];
-            }
-            return PNL_OK;
-        };
-        auto fold_stage = [&](int s) -> int {
-            if (side) HIPCHK(ctx, hipStreamWaitEvent(folds, ctx->ev_stage[s], 0));
-            StreamScope on(ctx, folds);
-            return pnl2_fold_mirror(ctx, SO, A, ldA, (const unsigned*)ctx->b_foldimg.p+ctx->stg_img_off[s], ctx->stg_img_off[s+1]-ctx->stg_img_off[s]);
-        };
-        if ((rc = uniform_stage(0, 0))) return rc;
-        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
-        if ((rc = launch_mixed_tiles<DIM, DPE, TILE, KT>(ctx, wlc, A, ldA, cell_begin, cell_end, SO))) return rc;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_stage[0], caller));
-        if ((rc = fold_stage(0))) return rc;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_fold, folds));
-        ctx->run.fold_event_set = true;
-        if (side && wls != folds) HIPCHK(ctx, hipStreamWaitEvent(wls, ctx->ev_fold, 0));
-        {
-            StreamScope on(ctx, wls);
-            if ((rc = run_worklist<DIM, DPE, KT>(ctx, (const int4*)ctx->b_wl.p, wlc, ctx->wl_cap_each, A, ldA, true))) return rc;
-        }
-        if (side && wls != folds) HIPCHK(ctx, hipEventRecord(ctx->ev_join[wl_aux], wls));
-        for (int s = 1; s <= K; s++) {
-            if ((rc = uniform_stage(s, spare))) return rc;
-            HIPCHK(ctx, hipEventRecord(ctx->ev_stage[s], caller));
-            if ((rc = fold_stage(s))) return rc;
-        }
-        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_DONE], caller));                        // the last tile kernel is done
-        if (side) {
-            // what is left of the folds and the work list behind the last tile kernel: phase [1]
-            HIPCHK(ctx, hipEventRecord(ctx->ev_join[2], folds));
-            HIPCHK(ctx, hipStreamWaitEvent(caller, ctx->ev_join[2], 0));
-            if (wls != folds) HIPCHK(ctx, hipStreamWaitEvent(caller, ctx->ev_join[wl_aux], 0));
-        }
-        return PNL_OK;
-    }
     if (TILE == 64 && DPE <= 3) {
         int rc;
         // order-2 uniform tiles: 2D P1 the pipelined k_tile_uniform<3, 3> (with three or four workgroups per CU it beats k_tile_pure:
@@ -538,9 +464,6 @@ bool slot_eligible(const pnl_context *ctx, bool full_list, int cell_begin, int c
            !(flags & (PNL_FLAG_NO_MIRROR | PNL_FLAG_SYMMETRIC_FLUSH));
 }
 
-#ifndef PNL_BND_MODE_DEFAULT
-#define PNL_BND_MODE_DEFAULT 3
-#endif
 template <int DIM, int DPE, int TILE>
 int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, int ntiles, int cell_begin, int cell_end, int flags) {
     int rc;
@@ -598,18 +521,12 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
         }
         return PNL_OK;
     };
-    // The boundary term only adds to the per-cell diagonal blocks (b_D, scattered into A at the very end) and never touches A, so
-    // its stream needs nothing but the zero fill of that buffer and the class tables.  PNL_BND_MODE 3 (default): side stream 1 behind
-    // the LAST TILE KERNEL, i.e. next to the fold pass -- the fold is bound by HBM (VALU issue utilisation 0.4), the boundary kernels by
-    // latency and arithmetic, and nothing else can run there (everything else adds into A, which the fold overwrites): P2 39.9 -> 39.3
-    // ms, C5 52.2 -> 51.6, headline 103.3 -> 102.9 in bench.py's queued loop.  0: behind the fold (one class: side stream 1, several:
-    // forked over the class streams), next to the work-list kernels.  1: behind the zero fill, submitted after the tile and
-    // work-list kernels; 2: submitted first.  Measured: as soon as the boundary kernels are READY while the tile kernels still have
-    // workgroups to place, their workgroups take CU slots in front of them and the tile phase loses more than the boundary term
-    // costs (mode 2, P1 s = 0.4: 138 -> 173 ms).  Mode 1 wins 0.5-2 ms when the host waits for every assembly (the launches of the
-    // boundary kernels arrive late) and loses 12 ms of 103 in a loop of assemblies without a host synchronisation in between
-    // (everything is queued ahead, so it behaves like mode 2); a lowest-priority stream recovers half of that.
-    const int bnd_mode = !zero_exterior ? -1 : pnl_tune("PNL_BND_MODE") ? atoi(pnl_tune("PNL_BND_MODE")) : PNL_BND_MODE_DEFAULT;
+    // The boundary term only adds to the per-cell diagonal blocks (b_D, scattered into A at the very end) and never touches A.  Behind a
+    // fold pass it runs on side stream 1 behind the LAST TILE KERNEL, i.e. next to the fold: the fold is bound by HBM, the boundary kernels
+    // by latency and arithmetic, and nothing else can run there (everything else adds into A, which the fold overwrites).  Not earlier:
+    // boundary kernels that are ready while the tile kernels still have workgroups to place take CU slots in front of them, and the tile
+    // phase loses more than the term costs (the placements that lost: docs/CHANGELOG_kernels.md, round 3).  Without a fold pass: on side
+    // stream 1 behind ev_fold, next to the touching pairs (one class and orientation), else on the caller's stream
     bool bnd_side = false;
     auto boundary_side = [&](hipEvent_t after) -> int {
         hipStream_t const side = ctx->aux[1];
@@ -620,11 +537,6 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
         bnd_side = true;
         return PNL_OK;
     };
-    if (bnd_mode > 0) HIPCHK(ctx, hipEventRecord(ctx->ev_bnd, ctx->stream));
-    if (bnd_mode == 2) {
-        if ((rc = boundary_side(ctx->ev_bnd))) return rc;
-        pnl_refresh_tables(ctx);
-    }
     // a piecewise-constant variable order is assembled class by class: every pass sees the kernel, order formula and
     // singular rules of one order value and skips the pairs of the other classes in its classification
     const int norient = ctx->nonsym ? 2 : 1;
@@ -697,13 +609,12 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
     }
     if (overlap) HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
     else HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SINGULAR_DONE], ctx->stream));
-    // 4: as 3, but with a staged fold behind the tile kernels of stage 0, next to the uniform tiles of the later stages (which leave
-    // it a workgroup slot per CU)
-    if ((bnd_mode == 3 || bnd_mode == 4) && ctx->run.fold_event_set)              // next to the fold pass
-        rc = boundary_side(bnd_mode == 4 && ctx->run.stg_active && !pnl_tune("PNL_NO_OVERLAP") ? ctx->ev_stage[0] : ctx->ev[EV_TILES_DONE]);
-    else if (bnd_mode == 1 || ((bnd_mode == 0 || bnd_mode >= 3) && overlap)) rc = boundary_side(bnd_mode == 1 ? ctx->ev_bnd : ctx->ev_fold);
-    else if (bnd_mode == 0 || bnd_mode >= 3) rc = boundary_term(chain);
-    if (rc) return rc;
+    if (zero_exterior) {
+        if (ctx->run.fold_event_set) rc = boundary_side(ctx->ev[EV_TILES_DONE]);      // next to the fold pass
+        else if (overlap) rc = boundary_side(ctx->ev_fold);
+        else rc = boundary_term(chain);
+        if (rc) return rc;
+    }
     if (overlap) {
         HIPCHK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join[0], 0));
         HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SINGULAR_DONE], ctx->stream));

@@ -714,21 +714,7 @@ static int upload_slot_tables(pnl_context *ctx, const CellTables &F) {
                 x.off = cprow[g]; x.ar = (cp[g].x << 5) | (I-q*32); x.cy = cp[g].y;
             }
     }
-    if ((rc = upload(ctx, ctx->b_foldtab, tab.data(), tab.size()))) return rc;
-    // the blocks that hold a copy of a DoF of each range: the tiles of an image (stage_plan)
-    ctx->rng_blk_off.assign(nranges+1, 0);
-    ctx->rng_blk.clear();
-    std::vector<int> bl;
-    for (int q = 0; q < nranges; q++) {
-        bl.clear();
-        for (int g = cpoff[q*32]; g < cpoff[std::min(ctx->N, q*32+32)]; g++) bl.push_back(cp[g].x);
-        std::sort(bl.begin(), bl.end());
-        bl.erase(std::unique(bl.begin(), bl.end()), bl.end());
-        ctx->rng_blk.insert(ctx->rng_blk.end(), bl.begin(), bl.end());
-        ctx->rng_blk_off[q+1] = (int)ctx->rng_blk.size();
-    }
-    ctx->stg_want = -1;                                   // a plan made for other tables does not stay
-    return PNL_OK;
+    return upload(ctx, ctx->b_foldtab, tab.data(), tab.size());
 }
 
 // filling DevProblem
@@ -924,10 +910,7 @@ const char *const k_product_options[] = {"PNL_WL_FRAC", "PNL_FH_NOTILES", "PNL_N
                                          "PNL_NO_OVERLAP", "PNL_NO_FORK",
                                          // tests: at most this many workgroups of a persistent tile kernel (every workgroup then walks
                                          // many tiles at test sizes: the pipelined tile loops against the oracle)
-                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_UNI_CHECKED", "PNL_UNI_LANES", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED", "PNL_SETTLED_CODES",
-                                         // staged fold of the dense 2D P1 assembly: far bands (0: one fold behind all tiles), spare workgroup
-                                         // slots per CU of the far uniform launches, where the boundary term starts (3 / 4)
-                                         "PNL_FOLD_STAGES", "PNL_UNI_SPARE", "PNL_BND_MODE"};
+                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_UNI_CHECKED", "PNL_UNI_LANES", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED", "PNL_SETTLED_CODES"};
 }  // namespace
 
 const char *pnl_tune(const char *name) {
@@ -987,13 +970,10 @@ int pnl_create(int device_id, pnl_context **out) {
         if ((e0 = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) != hipSuccess) { delete ctx; return hiperr("hipStreamCreateWithFlags", e0); }
     if (hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) { delete ctx; return PNL_ERR_HIP; }
     if (hipEventCreateWithFlags(&ctx->ev_fold, hipEventDisableTiming) != hipSuccess) { delete ctx; return PNL_ERR_HIP; }
-    if (hipEventCreateWithFlags(&ctx->ev_bnd, hipEventDisableTiming) != hipSuccess) { delete ctx; return PNL_ERR_HIP; }
     for (auto &e : ctx->ev_join)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { delete ctx; return PNL_ERR_HIP; }
     for (auto &e : ctx->ev)
         if (hipEventCreate(&e) != hipSuccess) { delete ctx; return PNL_ERR_HIP; }
-    for (auto &e : ctx->ev_stage)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { delete ctx; return PNL_ERR_HIP; }
     std::memset(&ctx->P, 0, sizeof(ctx->P));
 #ifdef PNL_DEBUG_ABLATE
     if (const char *e = pnl_tune("PNL_ABLATE")) ctx->ablate = atoi(e);      // result-changing debug switches: debug builds only
@@ -1014,12 +994,10 @@ void pnl_destroy(pnl_context *ctx) {
     for (auto &v : ctx->kev)
         for (auto &e : v)
             if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);
     tile_order_drop(ctx);
     for (auto &st : ctx->aux) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_fold) (void)hipEventDestroy(ctx->ev_fold);
-    if (ctx->ev_bnd) (void)hipEventDestroy(ctx->ev_bnd);
     for (auto *t : ctx->powtabs) delete t;
     ctx->powtabs.clear();
     for (auto &e : ctx->ev_join) if (e) (void)hipEventDestroy(e);
@@ -1379,7 +1357,6 @@ struct TilePlan {
     std::vector<std::vector<int2>> mixed, uni[3];         // per class: tiles of the general kernel / of one order 2, 3, 4
 };
 
-static int fold_stages_wanted();
 // the option PNL_MIXED_UNSETTLED (a product option, read when the plan is made): the plan settles no mixed tile
 static int settled_wanted() { return pnl_tune("PNL_MIXED_UNSETTLED") ? 0 : 1; }
 // the option PNL_SETTLED_CODES (a product option, read when the plan is made): the plan keeps the codes of the settled tiles only, and
@@ -1391,7 +1368,7 @@ static bool tiles_resident(const pnl_context *ctx, const std::vector<int2> &tile
     const std::vector<pnl_order_formula> &forms = R.forms;
     return tiles.size() == ctx->tiles_cached.size() && ctx->b_tiles.p && ctx->tiles_cb == R.cell_begin && ctx->tiles_ce == R.cell_end &&
         forms.size() == ctx->tiles_forms.size() && std::memcmp(forms.data(), ctx->tiles_forms.data(), sizeof(pnl_order_formula)*R.ncls) == 0 &&
-        ctx->tiles_filter == ctx->run.tile_cell_filter && ctx->stg_want == fold_stages_wanted() && ctx->settled_want == settled_wanted() && ctx->lists_want == lists_wanted() &&
+        ctx->tiles_filter == ctx->run.tile_cell_filter && ctx->settled_want == settled_wanted() && ctx->lists_want == lists_wanted() &&
         (tiles.empty() || std::memcmp(tiles.data(), ctx->tiles_cached.data(), tiles.size()*sizeof(int2)) == 0);
 }
 
@@ -1486,148 +1463,6 @@ static int settle_tiles(pnl_context *ctx, const TilePlan &R, const std::vector<i
     }
     std::stable_sort(keep.begin(), keep.end(), [&](size_t x, size_t y) { return stat[x] > stat[y]; });
     for (size_t c : keep) { settled.push_back(cand[c]); is_settled[open_234[c]] = 1; }
-    return PNL_OK;
-}
-
-// ---- staged fold (2D P1, one order class, the whole upper block triangle) ------------------------------------------------------
-// An image is a (range of 32 row DoFs, range of 32 column DoFs) block of the upper block triangle, the work unit of k_fold_mirror;
-// its tiles are all (min(a, b), max(a, b)) with a a block that holds a copy of a row DoF and b one that holds a copy of a column DoF.
-//   stage 0:      the images with a tile that is not in a uniform list (mixed, diagonal, a block that is not full) and all tiles
-//                 of these images: the mixed tiles and a rim of uniform ones.  Every entry the work lists, the touching pairs and
-//                 k_scatter_diag add to lies in such an image (both cells of such a pair have a block in the image's copy lists, and
-//                 their tile is not uniform)
-//   stage 1 + k:  the other uniform tiles by the band k of their block row a (K bands of about equal tile counts); an image
-//                 belongs to the largest stage among its tiles
-// The fold of stage s needs nothing later than the tile kernels of stage s, and nothing else writes its images.
-// The plan keeps every uniform list stably sorted by stage and per stage the packed images in the order of the 8 x 8 super-blocks
-// (k_fold_mirror).  K = 0 (the default: measured, no number of bands gains over the single fold, docs/CHANGELOG_kernels.md round 6),
-// no uniform tile, more than 65,535 ranges: no stages (one fold behind all tiles).
-#ifndef PNL_FOLD_STAGES_DEFAULT
-#define PNL_FOLD_STAGES_DEFAULT 0
-#endif
-static int fold_stages_wanted() {
-    const char *e = pnl_tune("PNL_FOLD_STAGES");
-    return std::max(0, std::min(e ? atoi(e) : PNL_FOLD_STAGES_DEFAULT, (int)pnl_context::MAX_STAGES));
-}
-
-static void stage_plan_drop(pnl_context *ctx) {
-    ctx->stg_K = 0;
-    ctx->stg_img_off.clear(); ctx->stg_img.clear(); ctx->stg_tile_stage.clear(); ctx->stg_tile_q.clear();
-    for (auto &v : ctx->stg_uni_off) v.clear();
-}
-
-static int stage_plan(pnl_context *ctx, TilePlan &R, const std::vector<int2> &tiles, int K) {
-    stage_plan_drop(ctx);
-    const int nb = ctx->nblocks, nr = (ctx->N+31)/32;
-    const size_t nuni = R.ncls == 1 ? R.uni[0][0].size()+R.uni[1][0].size()+R.uni[2][0].size() : 0;
-    if (K <= 0 || !(R.p1 && ctx->dim == 2 && ctx->dpe == 3 && R.ncls == 1 && !ctx->nonsym) || nuni == 0 || nr > 65535 ||
-        (int)ctx->rng_blk_off.size() != nr+1 || tiles.size() != (size_t)nb*(nb+1)/2) return PNL_OK;
-    // stage of every tile: -1 absent, 0 stage 0, 1 + band; order 2 .. 4 of a uniform tile, else 0
-    std::vector<signed char> &tst = ctx->stg_tile_stage;
-    std::vector<unsigned char> &tq = ctx->stg_tile_q;
-    tst.assign((size_t)nb*nb, (signed char)-1);
-    tq.assign((size_t)nb*nb, 0);
-    size_t seen = 0;
-    for (const int2 &t : tiles)
-        if (t.x >= 0 && t.x <= t.y && t.y < nb && tst[(size_t)t.x*nb+t.y] < 0) { tst[(size_t)t.x*nb+t.y] = 0; seen++; }
-    if (seen != tiles.size()) { stage_plan_drop(ctx); return PNL_OK; }            // not the upper block triangle, every tile once
-    for (int u = 0; u < 3; u++)
-        for (const int2 &t : R.uni[u][0]) { tst[(size_t)t.x*nb+t.y] = 1; tq[(size_t)t.x*nb+t.y] = (unsigned char)(2+u); }
-    const int32_t *boff = ctx->rng_blk_off.data(), *blk = ctx->rng_blk.data();
-    auto img_index = [nr](int bi, int bj) { return (size_t)bi*nr-(size_t)bi*(bi-1)/2+(size_t)(bj-bi); };
-    const size_t nimg = (size_t)nr*(nr+1)/2;
-    std::vector<signed char> ist(nimg, 1);
-    // reduce over the tiles of an image
-    auto over_tiles = [&](int bi, int bj, auto &&f) {
-        for (int x = boff[bi]; x < boff[bi+1]; x++)
-            for (int y = boff[bj]; y < boff[bj+1]; y++) {
-                const int a = std::min(blk[x], blk[y]), b = std::max(blk[x], blk[y]);
-                f((size_t)a*nb+b);
-            }
-    };
-    // the images with a tile that is not uniform
-    host_threads([&](int th, int nthr) {
-        for (int bi = th; bi < nr; bi += nthr)
-            for (int bj = bi; bj < nr; bj++) {
-                bool plain = true;
-                over_tiles(bi, bj, [&](size_t t) { plain = plain && tq[t] != 0; });
-                if (!plain) ist[img_index(bi, bj)] = 0;
-            }
-    });
-    // their uniform tiles: the rim
-    for (int bi = 0; bi < nr; bi++)
-        for (int bj = bi; bj < nr; bj++)
-            if (ist[img_index(bi, bj)] == 0) over_tiles(bi, bj, [&](size_t t) { tst[t] = 0; });
-    // bands of block rows with about equal counts of the remaining uniform tiles
-    std::vector<long long> row_n(nb, 0);
-    long long far = 0;
-    for (int a = 0; a < nb; a++) {
-        for (int b = a; b < nb; b++) row_n[a] += tst[(size_t)a*nb+b] == 1;
-        far += row_n[a];
-    }
-    if (far == 0) { stage_plan_drop(ctx); return PNL_OK; }
-    K = (int)std::min<long long>(K, far);
-    long long before = 0;
-    for (int a = 0; a < nb; a++) {
-        const int band = (int)std::min<long long>(K-1, before*K/far);
-        for (int b = a; b < nb; b++) if (tst[(size_t)a*nb+b] == 1) tst[(size_t)a*nb+b] = (signed char)(1+band);
-        before += row_n[a];
-    }
-    host_threads([&](int th, int nthr) {
-        for (int bi = th; bi < nr; bi += nthr)
-            for (int bj = bi; bj < nr; bj++) {
-                signed char &s = ist[img_index(bi, bj)];
-                if (s == 0) continue;
-                int m = 0;
-                over_tiles(bi, bj, [&](size_t t) { m = std::max(m, (int)tst[t]); });
-                s = (signed char)m;
-            }
-    });
-#ifdef PNL_DEBUG_ABLATE
-    // the stage relations: a tile is not later than any image it belongs to, an image of a stage >= 1 holds uniform tiles only
-    for (int bi = 0; bi < nr; bi++)
-        for (int bj = bi; bj < nr; bj++) {
-            const int s = ist[img_index(bi, bj)];
-            over_tiles(bi, bj, [&](size_t t) {
-                if (tst[t] < 0 || tst[t] > s || (s >= 1 && tq[t] == 0)) { fprintf(stderr, "[pnl] stage plan: image (%d, %d) of stage %d against tile stage %d\n", bi, bj, s, (int)tst[t]); abort(); }
-            });
-        }
-#endif
-    // per stage the packed images in the order of the 8 x 8 super-blocks
-    std::vector<int> &ioff = ctx->stg_img_off;
-    ioff.assign(K+2, 0);
-    for (size_t i = 0; i < nimg; i++) ioff[ist[i]+1]++;
-    for (int s = 0; s <= K; s++) ioff[s+1] += ioff[s];
-    std::vector<int> fill(ioff.begin(), ioff.end()-1);
-    ctx->stg_img.assign(nimg, 0u);
-    const int nbs = (nr+7)/8;
-    for (int I = 0; I < nbs; I++)
-        for (int J = I; J < nbs; J++)
-            for (int inner = 0; inner < 64; inner++) {
-                const int bi = 8*I+(inner >> 3), bj = 8*J+(inner & 7);
-                if (bi > bj || bj >= nr) continue;
-                ctx->stg_img[fill[ist[img_index(bi, bj)]]++] = ((unsigned)bi << 16) | (unsigned)bj;
-            }
-    // the uniform lists stably sorted by stage
-    for (int u = 0; u < 3; u++) {
-        std::vector<int2> &list = R.uni[u][0];
-        std::vector<int> &off = ctx->stg_uni_off[u];
-        off.assign(K+2, 0);
-        for (const int2 &t : list) off[tst[(size_t)t.x*nb+t.y]+1]++;
-        for (int s = 0; s <= K; s++) off[s+1] += off[s];
-        std::vector<int> at(off.begin(), off.end()-1);
-        std::vector<int2> sorted(list.size());
-        for (const int2 &t : list) sorted[at[tst[(size_t)t.x*nb+t.y]]++] = t;
-        list.swap(sorted);
-    }
-    int rc;
-    if ((rc = upload(ctx, ctx->b_foldimg, ctx->stg_img.data(), ctx->stg_img.size()))) return rc;
-    ctx->stg_K = K;
-    if (pnl_tune("PNL_VERBOSE"))
-        for (int s = 0; s <= K; s++)
-            fprintf(stderr, "[pnl] fold stage %d: %d images, uniform tiles of order 2/3/4: %d / %d / %d\n", s, ioff[s+1]-ioff[s],
-                    ctx->stg_uni_off[0][s+1]-ctx->stg_uni_off[0][s], ctx->stg_uni_off[1][s+1]-ctx->stg_uni_off[1][s],
-                    ctx->stg_uni_off[2][s+1]-ctx->stg_uni_off[2][s]);
     return PNL_OK;
 }
 
@@ -1760,8 +1595,6 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
     ctx->settled_tiles.clear();
     std::vector<int2> all;
     ctx->single_launch = R.p2;
-    const int stages_wanted = fold_stages_wanted();
-    if ((rc = stage_plan(ctx, R, tiles, stages_wanted))) return rc;
     if (!R.p2) tile_lists_per_class(ctx, R, all);
     else if ((rc = tile_lists_single_launch(ctx, R, tiles, all))) return rc;
     if (pnl_tune("PNL_VERBOSE")) {
@@ -1793,7 +1626,6 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
     ctx->lists_want = lists_wanted();
     ctx->tiles_cached = tiles; ctx->tiles_cb = cell_begin; ctx->tiles_ce = cell_end; ctx->tiles_forms = R.forms;
     ctx->tiles_filter = ctx->run.tile_cell_filter;
-    ctx->stg_want = stages_wanted;
     return PNL_OK;
 }
 
@@ -1993,27 +1825,6 @@ int pnl_get_phase_ms(pnl_context *ctx, float *out, int n) {
     return PNL_OK;
 }
 
-int pnl_get_fold_stages(pnl_context *ctx, int64_t *out, int n) {
-    if (!ctx || n < 0 || (n && !out)) return PNL_ERR_INVALID;
-    if (!ctx->b_tiles.p || ctx->cls_n_mixed.empty()) return fail(ctx, PNL_ERR_STATE, "no tile plan yet");
-    const int K = ctx->stg_K;
-    for (int s = 0; s <= K && s < n; s++) {
-        int64_t *o = out+5*(size_t)s;
-        if (K == 0) {
-            // no stages: everything is stage 0, one fold of the whole upper block triangle
-            const long long nr = (ctx->N+31)/32;
-            o[0] = nr*(nr+1)/2;
-            for (int u = 0; u < 3; u++) { o[1+u] = 0; for (int k : ctx->cls_n_uni[u]) o[1+u] += k; }
-        } else {
-            o[0] = ctx->stg_img_off[s+1]-ctx->stg_img_off[s];
-            for (int u = 0; u < 3; u++) o[1+u] = ctx->stg_uni_off[u][s+1]-ctx->stg_uni_off[u][s];
-        }
-        o[4] = 0;
-        if (s == 0) for (int k : ctx->cls_n_mixed) o[4] += k;
-    }
-    return K+1;
-}
-
 int pnl_get_settled_tiles(pnl_context *ctx, int32_t *tiles, int64_t ntiles) {
     if (!ctx || ntiles < 0 || (ntiles && !tiles)) return PNL_ERR_INVALID;
     if (!ctx->b_tiles.p || ctx->cls_n_mixed.empty()) return fail(ctx, PNL_ERR_STATE, "no tile plan yet");
@@ -2074,27 +1885,6 @@ int pnl_uniform_lane_layout(int nc, const int32_t *cells, const int32_t *dofs, i
     std::copy(R.cell_col.begin(), R.cell_col.end(), cell_col);
     std::copy(R.mult.begin(), R.mult.end(), mult);
     for (size_t i = 0; i < lperm.size(); i++) vorder[i] = (int8_t)lperm[i];
-    return PNL_OK;
-}
-
-int pnl_get_fold_plan(pnl_context *ctx, int32_t *images, int64_t nimages, int8_t *tile_stage, int8_t *tile_order, int64_t ntiles) {
-    if (!ctx) return PNL_ERR_INVALID;
-    if (ctx->stg_K <= 0) return fail(ctx, PNL_ERR_STATE, "the resident tile plan has no fold stages");
-    const int K = ctx->stg_K;
-    const size_t nb2 = (size_t)ctx->nblocks*ctx->nblocks;
-    if (images) {
-        if (nimages != ctx->stg_img_off[K+1]) return fail(ctx, PNL_ERR_INVALID, "the plan has %d images", ctx->stg_img_off[K+1]);
-        for (int s = 0; s <= K; s++)
-            for (int i = ctx->stg_img_off[s]; i < ctx->stg_img_off[s+1]; i++) {
-                images[3*(size_t)i] = (int32_t)(ctx->stg_img[i] >> 16); images[3*(size_t)i+1] = (int32_t)(ctx->stg_img[i] & 0xffffu);
-                images[3*(size_t)i+2] = s;
-            }
-    }
-    if (tile_stage || tile_order) {
-        if ((size_t)ntiles != nb2) return fail(ctx, PNL_ERR_INVALID, "the tile tables have %zu entries", nb2);
-        if (tile_stage) std::memcpy(tile_stage, ctx->stg_tile_stage.data(), nb2);
-        if (tile_order) std::memcpy(tile_order, ctx->stg_tile_q.data(), nb2);
-    }
     return PNL_OK;
 }
 

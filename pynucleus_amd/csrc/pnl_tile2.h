@@ -49,35 +49,27 @@ __host__ __device__ constexpr int uni_rule_size(int dpe, int np) { return 3*np+n
 template <bool NT>
 __global__ void __launch_bounds__(256)
 k_fold_mirror(const double *__restrict__ A2, const FoldEntry *__restrict__ tab, const int *__restrict__ cpoff, const int2 *__restrict__ cp,
-              const long long *__restrict__ cprow, double *__restrict__ A, long long ldA, int N, const unsigned *__restrict__ images) {
+              const long long *__restrict__ cprow, double *__restrict__ A, long long ldA, int N) {
     __shared__ double t1[32][33], t2[32][33];
     __shared__ FoldEntry s_tab[2][PNL_FOLD_TAB+1];
     const unsigned nb = (unsigned)(N+31)/32;
     // 8 x 8 super-blocks of the upper block triangle, 64 consecutive workgroups each: the workgroups in flight share the
     // storage rows of 8 row ranges and 8 column ranges (pages, DRAM rows, L2 lines of the XCD) instead of sweeping one block
     // row against thousands of unrelated column ranges
-    // images: the workgroups take the packed images (bi << 16 | bj) of a list in that order (a stage of a staged fold: the host made
-    // the list in the same traversal order); nullptr: the whole upper block triangle, decoded from the block index
-    unsigned bi, bj;
-    if (images) {
-        const unsigned im = images[blockIdx.x];
-        bi = im >> 16; bj = im & 0xffffu;
-    } else {
-        const unsigned nbs = (nb+7)/8;
-        const unsigned sbid = blockIdx.x >> 6, inner = blockIdx.x & 63;
-        // sbid = I nbs - I (I-1)/2 + (J - I); the grid has less than 2^31 blocks, so 32-bit arithmetic is exact
-        unsigned I;
-        {
-            const float t = 2.f*(float)nbs+1.f;
-            const float fb = (t-sqrtf(fmaxf(t*t-8.f*(float)sbid, 0.f)))*0.5f;
-            I = (unsigned)fmaxf(fb, 0.f);
-            if (I >= nbs) I = nbs-1;
-            while (I > 0 && I*nbs-I*(I-1)/2 > sbid) I--;
-            while (I+1 < nbs && (I+1)*nbs-(I+1)*I/2 <= sbid) I++;
-        }
-        const unsigned J = I+(sbid-(I*nbs-I*(I-1)/2));
-        bi = 8*I+(inner >> 3); bj = 8*J+(inner & 7);
+    const unsigned nbs = (nb+7)/8;
+    const unsigned sbid = blockIdx.x >> 6, inner = blockIdx.x & 63;
+    // sbid = I nbs - I (I-1)/2 + (J - I); the grid has less than 2^31 blocks, so 32-bit arithmetic is exact
+    unsigned I;
+    {
+        const float t = 2.f*(float)nbs+1.f;
+        const float fb = (t-sqrtf(fmaxf(t*t-8.f*(float)sbid, 0.f)))*0.5f;
+        I = (unsigned)fmaxf(fb, 0.f);
+        if (I >= nbs) I = nbs-1;
+        while (I > 0 && I*nbs-I*(I-1)/2 > sbid) I--;
+        while (I+1 < nbs && (I+1)*nbs-(I+1)*I/2 <= sbid) I++;
     }
+    const unsigned J = I+(sbid-(I*nbs-I*(I-1)/2));
+    const unsigned bi = 8*I+(inner >> 3), bj = 8*J+(inner & 7);
     if (bi > bj || bj >= nb) return;                     // lower part of a diagonal super-block, padding of the last one
     const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;     // 32 x 8
     if (tid < 2*(PNL_FOLD_TAB+1)) {

@@ -7,7 +7,7 @@ namespace {
 
 template <int DPE, int NP, int KT, bool STRUCT = false>
 int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, const int *tile_cls, int ntiles, int q, double *A,
-                     int64_t ldA, double *Dglob, const SlotOut &SO, int spare) {
+                     int64_t ldA, double *Dglob, const SlotOut &SO) {
     constexpr int TILE = DPE == 6 ? 32 : 64;
     const int nUe = (ctx->nU+1) & ~1;                     // even: the sub-block follows the int arrays at an 8-byte boundary
     const size_t fixed = uniform_fixed_lds(DPE, NP, TILE, nUe, SO.A2 == nullptr);
@@ -61,9 +61,7 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
     }
     HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int per_cu = resident(lds);
-    // spare: workgroup slots per CU this launch leaves to kernels of other streams (P1: the ticketed tile loop does not care how
-    // many workgroups share the tiles)
-    const int grid = pnl_grid_cap(std::min(ntiles, 256*std::max(1, per_cu-(DPE == 3 ? std::max(spare, 0) : 0))));
+    const int grid = pnl_grid_cap(std::min(ntiles, 256*std::max(1, per_cu)));
     // P1: the ticket counter of this launch, one of those the assembly zeroed at its start (assemble_impl), else zeroed in the stream
     // here; every launch has its own, so that no launch depends on more than the order of its own stream
     unsigned *ctr = nullptr;
@@ -102,17 +100,17 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
 
 template <int DPE, int NP>
 int launch_uniform_kt(pnl_context *ctx, int kt, const DevProblem &Pt, const int2 *tiles, const int *tile_cls, int ntiles, int q,
-                      double *A, int64_t ldA, double *Dglob, const SlotOut &SO, int spare) {
+                      double *A, int64_t ldA, double *Dglob, const SlotOut &SO) {
     if constexpr (DPE == 3) {
         if (ctx->uni_struct[q] && !pnl_tune("PNL_UNI_GENERIC")) {
-            if (kt == 2) return launch_uniform_t<DPE, NP, 2, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
-            if (kt == 1) return launch_uniform_t<DPE, NP, 1, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
-            return launch_uniform_t<DPE, NP, 0, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+            if (kt == 2) return launch_uniform_t<DPE, NP, 2, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+            if (kt == 1) return launch_uniform_t<DPE, NP, 1, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+            return launch_uniform_t<DPE, NP, 0, true>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
         }
     }
-    if (kt == 2) return launch_uniform_t<DPE, NP, 2>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
-    if (kt == 1) return launch_uniform_t<DPE, NP, 1>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
-    return launch_uniform_t<DPE, NP, 0>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+    if (kt == 2) return launch_uniform_t<DPE, NP, 2>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+    if (kt == 1) return launch_uniform_t<DPE, NP, 1>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+    return launch_uniform_t<DPE, NP, 0>(ctx, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
 }
 
 template <int KT>
@@ -147,14 +145,14 @@ int launch_p2_t(pnl_context *ctx, const int2 *tiles, const int *tile_cls, int nt
 
 // uniform tiles of one order; Pt / Dglob: the cell tables (and diagonal-block buffer) the tile kernels use
 int pnl2_launch_uniform(pnl_context *ctx, int kt, const DevProblem &Pt, const int2 *tiles, const int *tile_cls, int ntiles, int q,
-                        double *A, int64_t ldA, double *Dglob, const SlotOut &SO, int spare) {
+                        double *A, int64_t ldA, double *Dglob, const SlotOut &SO) {
     if (ntiles <= 0) return PNL_OK;
     if (q < 2 || q > 4 || ctx->uni_off[q] < 0) return fail(ctx, PNL_ERR_STATE, "no uniform-tile rule for order %d", q);
     const int np = ctx->uni_np[q];
-    if (ctx->dpe == 6 && np == 3) return launch_uniform_kt<6, 3>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
-    if (ctx->dpe == 6 && np == 6) return launch_uniform_kt<6, 6>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
-    if (ctx->dpe == 3 && np == 6) return launch_uniform_kt<3, 6>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
-    if (ctx->dpe == 3 && np == 3) return launch_uniform_kt<3, 3>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO, spare);
+    if (ctx->dpe == 6 && np == 3) return launch_uniform_kt<6, 3>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+    if (ctx->dpe == 6 && np == 6) return launch_uniform_kt<6, 6>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+    if (ctx->dpe == 3 && np == 6) return launch_uniform_kt<3, 6>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
+    if (ctx->dpe == 3 && np == 3) return launch_uniform_kt<3, 3>(ctx, kt, Pt, tiles, tile_cls, ntiles, q, A, ldA, Dglob, SO);
     return fail(ctx, PNL_ERR_UNSUPPORTED, "uniform tiles: dpe=%d with %d points", ctx->dpe, np);
 }
 
@@ -174,17 +172,15 @@ int pnl2_zero_slot_tiles(pnl_context *ctx, const SlotOut &SO) {
     return PNL_OK;
 }
 
-// images / nimages: the packed images of one stage (device), nullptr: the whole upper block triangle
-int pnl2_fold_mirror(pnl_context *ctx, const SlotOut &SO, double *A, int64_t ldA, const unsigned *images, int nimages) {
+int pnl2_fold_mirror(pnl_context *ctx, const SlotOut &SO, double *A, int64_t ldA) {
     const long long nb = (ctx->N+31)/32, nbs = (nb+7)/8;
     if (nbs*(nbs+1)/2*64 >= (1ll << 31)) return fail(ctx, PNL_ERR_UNSUPPORTED, "fold pass: %d DoFs exceed the grid size", ctx->N);
-    if (images && nimages <= 0) return PNL_OK;
-    const unsigned grid = images ? (unsigned)nimages : (unsigned)(nbs*(nbs+1)/2*64);
+    const unsigned grid = (unsigned)(nbs*(nbs+1)/2*64);
     kt_begin(ctx, PNL_K_FOLD_MIRROR);
     // the matrix is written once and not read again by this pass: non-temporal stores (10.9 -> 10.4 ms at 48,769 DoFs; non-temporal
     // LOADS of the storage cost 50 %: the 8-byte gathers of neighbouring threads share lines)
     hipLaunchKernelGGL(k_fold_mirror<true>, dim3(grid), dim3(256), 0, ctx->stream, (const double*)SO.A2, (const FoldEntry*)ctx->b_foldtab.p, (const int*)ctx->b_cpoff.p,
-                       (const int2*)ctx->b_cpslot.p, (const long long*)ctx->b_cprow.p, A, (long long)ldA, ctx->N, images);
+                       (const int2*)ctx->b_cpslot.p, (const long long*)ctx->b_cprow.p, A, (long long)ldA, ctx->N);
     kt_end(ctx, PNL_K_FOLD_MIRROR);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;

@@ -92,6 +92,11 @@ def test_options_are_explicit_not_environment(monkeypatch):
     # the planner's thread count is an option like the others
     assert L.pnl_set_option(b'PNL_PLAN_THREADS', b'2') == 0
     assert L.pnl_set_option(b'PNL_PLAN_THREADS', None) == 0
+    # the staged fold and the boundary-mode switch are gone: no option selects another launch sequence, no entry point reports one
+    for name in (b'PNL_FOLD_STAGES', b'PNL_UNI_SPARE', b'PNL_BND_MODE'):
+        assert L.pnl_set_option(name, b'1') == _lib.PNL_ERR_UNSUPPORTED, name
+    for name in ('pnl_get_fold_stages', 'pnl_get_fold_plan'):
+        assert not hasattr(L, name), name
     # no getenv with a literal name anywhere in the product sources (pnl_tune's fallback of the tuning builds takes a variable)
     import glob
     for fn in glob.glob(os.path.join(ROOT, 'pynucleus_amd', 'csrc', '*.h*')):

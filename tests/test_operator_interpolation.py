@@ -620,7 +620,7 @@ def _check_interval(name, i, with_solvers):
     x = rng.standard_normal(n)
     # (a) is formed from the node operators' own blocks, each downloaded by its Dense_LinearOperator.  Separately assembled operators at
     # the same nodes are NOT the same bits: the work-list and touching-pair kernels of the assembly add with atomics, whose order differs
-    # from run to run (tests/test_staged_fold.py: bounded by TOL_ORDER = 1e-13 max|A|), which is 500 times the rounding bound of (R); they
+    # from run to run (tests/test_run_state.py: bounded by TOL_ORDER = 1e-13 max|A|), which is 500 times the rounding bound of (R); they
     # are held to that documented bound instead
     op.assure_constructed()
     mats = [o.toarray().copy() for o in op.ops]
@@ -739,7 +739,7 @@ def test_generic_path(fmt, horizon):
     x = np.random.default_rng(4).standard_normal(dm.num_dofs)
     # The products y_k = op_k.matvec(x) that A.matvec combines are recorded on the way: the SSS and H2 products add with atomics, so a
     # second call of op_k.matvec(x) does not give the same bits (the order of the additions differs from run to run, as in the
-    # assembly: tests/test_staged_fold.py), and the rounding bound of the combination can only hold against the y_k it was given.
+    # assembly: tests/test_run_state.py), and the rounding bound of the combination can only hold against the y_k it was given.
     # Separately computed products are held to the 1e-13 of that test instead.
     ys = []
 

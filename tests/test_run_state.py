@@ -121,3 +121,36 @@ def test_gpu_failed_assembly_leaves_no_timers_and_no_state():
         assert cnt[key] == cnt0[key], (key, cnt[key], cnt0[key])
     assert cnt['numBoundaryPairs'] > 0
     assert err <= TOL_ATOMIC
+
+
+TOL_ORDER = 1e-13           # the same terms summed in another order
+
+COUNTER_KEYS = ('numCellPairs', 'numAssembledCellPairs', 'numIntegrations', 'numBoundaryPairs', 'numBoundaryIntegrations', 'orders',
+                'singular')
+
+
+@pytest.mark.gpu
+def test_queued_assemblies():
+    """two assemblies queued on one context without a host synchronisation in between, into two matrices: block-slot storage, work
+    lists and ticket counters are reused by the second while the first is still running.  The reference is one ordinary getDense()"""
+    import torch
+    from pynucleus_amd import disc, P1_DoFMap, PHYSICAL
+    b = _builder(P1_DoFMap(disc(5), PHYSICAL), 0.5)
+    ref = b.getDense()
+    A0, cnt0 = ref.toarray(), ref.info['counters']
+    ctx = b.context()
+    N, nc = b.dm.num_dofs, b.mesh.num_cells
+    ldA = (N+7) & ~7
+    dev = torch.device('cuda', ctx.device)
+    mats = [torch.full((N, ldA), float('nan'), dtype=torch.float64, device=dev) for _ in range(2)]
+    for M in mats:
+        ctx.assemble_dense(M.data_ptr(), ldA, True, 0, nc)
+    ctx.synchronize()
+    torch.cuda.synchronize()
+    cnt = ctx.counters()
+    for key in COUNTER_KEYS:
+        assert cnt[key] == cnt0[key], (key, cnt[key], cnt0[key])
+    scale = np.abs(A0).max()
+    for M in mats:
+        Ah = M[:, :N].cpu().numpy()
+        assert np.abs(Ah-A0).max() <= TOL_ORDER*scale

@@ -1,17 +1,10 @@
 #!/usr/bin/env python3
 """Register / scratch / static-LDS budget of the kernels in the built objects (csrc/build/*.o): the table of DESIGN.md section 4.
-usage: kernel_resources.py [--slot N] [substring ...]   (no GPU needed: reads the gfx950 code objects with llvm-readelf)
---slot N: also say whether a wave of the kernel fits a slot of N registers per lane (VGPR + AGPR in allocation units of 8), e.g. the 128
-a SIMD has left beside three workgroups of the 128-register uniform-tile kernel (spare slot of the staged fold)"""
+usage: kernel_resources.py [substring ...]   (no GPU needed: reads the gfx950 code objects with llvm-readelf)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = '/opt/rocm/lib/llvm/bin'
 want = sys.argv[1:]
-slot = None
-if '--slot' in want:
-    i = want.index('--slot')
-    slot = int(want[i+1])
-    del want[i:i+2]
 with tempfile.TemporaryDirectory() as tmp:
     for obj in sorted(os.listdir(os.path.join(ROOT, 'pynucleus_amd', 'csrc', 'build'))):
         if not obj.endswith('.o'):
@@ -32,9 +25,5 @@ with tempfile.TemporaryDirectory() as tmp:
             short = re.sub(r'\(.*', '', d.replace('(anonymous namespace)::', '')).replace('void ', '')
             if want and not any(w in short for w in want):
                 continue
-            fits = ''
-            if slot is not None:
-                need = (int(r[1])+int(r[2])+7)//8*8
-                fits = '  {} a {}-register slot ({})'.format('fits' if need <= slot else 'exceeds', slot, need)
-            print('{:14s} {:60s} vgpr {:>3s} agpr {:>3s} scratch {:>4s} B  static LDS {:>6s} B{}'.format(obj, short[:60], r[1], r[2], r[3], r[4], fits))
+            print('{:14s} {:60s} vgpr {:>3s} agpr {:>3s} scratch {:>4s} B  static LDS {:>6s} B'.format(obj, short[:60], r[1], r[2], r[3], r[4]))
         os.remove(co)

@@ -5,7 +5,7 @@ python3 tools/launch_paths.py` in the tree of either build, then `launch_paths.p
 compare: the multiset of (kernel name, grid, workgroup, LDS bytes) and the order of the launches within every queue must be equal;
 it prints both totals and exits 1 on a difference.
 
-Paths: dense 2D P1 with and without zero exterior and with PNL_FOLD_STAGES=3, dense 2D P2, 1D, three order classes (label blocks off: one
+Paths: dense 2D P1 with and without zero exterior, dense 2D P2, 1D, three order classes (label blocks off: one
 context), a non-symmetric class table, a row slab, the H2 near field (cluster tiles), finite-horizon getSparse with and without
 PNL_FH_NOTILES, pointwise dense and pointwise near field.  Several of them run on one context one after the other."""
 import collections
@@ -42,12 +42,9 @@ def run():
         rp = b.getH2RefinementParams()
         return clusters.getNearFieldClusters(b.dm, rp['eta'], rp['minSize'], rp['maxLevels'])[1]
 
-    # one context: dense with settled tiles, the staged fold, the near field of cluster tiles, dense again
+    # one context: dense with settled tiles, the near field of cluster tiles, dense again
     b = builder(disc(5), 0.5)
     path('dense 2D P1, zero exterior', b.getDense)
-    _lib.set_option('PNL_FOLD_STAGES', 3)
-    path('dense 2D P1, PNL_FOLD_STAGES=3', b.getDense)
-    _lib.set_option('PNL_FOLD_STAGES', None)
     path('H2 near field (cluster tiles)', lambda: b.assembleClusters(near(b), forceUnsymmetricMatrix=True))
     path('dense 2D P1 after the near field', b.getDense)
     path('row slab', lambda: DistributedSlab_LinearOperator.assemble(b, 0, 2, None))
