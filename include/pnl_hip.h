@@ -332,6 +332,30 @@ int pnl_h2_sizes(pnl_context *ctx, int32_t *out2);
  * one after the other.  _get copies them to the host, _set replaces what pnl_h2_setup computed (an operator read from a file) */
 int pnl_h2_get(pnl_context *ctx, int which, double *dst_host);
 int pnl_h2_set(pnl_context *ctx, int which, const double *src_host);
+/* The far field for a block of vectors, free of floating-point atomics (csrc/pnl_h2_block.hip).  Vectors are stored one per row as in
+ * pnl_gemv_block: vector v is X_dev[v*ldx .. v*ldx + N), its result Y_dev[v*ldy .. v*ldy + N), N the number of DoFs.  Coefficient
+ * blocks cupB / cdownB are [nnodes][M][16] doubles with the vector index fastest.  The mathematics is that of the single-vector phases:
+ *   pnl_h2_upward_block    cupB is OVERWRITTEN: 0; leaves of the plan: cupB[leaf][.][v] = V^T X[v]; then level by level from the deepest
+ *                          cupB[parent] += T_child cupB[child].  X is read at the DoFs of the plan's leaves only (partial_leaves).
+ *   pnl_h2_interact_block  cdownB is OVERWRITTEN: cdownB[n1] = sum over the plan's pairs (n1, n2) of K_pair cupB[n2]; 0 without a pair.
+ *   pnl_h2_downward_block  cdownB is MODIFIED IN PLACE: level by level from the root cdownB[child] += T_child^T cdownB[parent]; then
+ *                          Y[v][dofs of the leaf] += V cdownB[leaf][.][v].  Y is ADDED to, at the DoFs of the plan's leaves only.
+ *   pnl_h2_matvec_block    the three phases on the context's own cupB / cdownB (grown once): Y[v] += far field of X[v].  Any nvec >= 1,
+ *                          in groups of at most 16, one pass over K, T and V per group (nvec = 17 costs two passes).
+ * The slots v >= nvec of cupB and cdownB are zero after the calls.  The padding of X and Y (ld > N) is neither read into a sum nor
+ * written.  The contraction runs on v_mfma_f64_16x16x4_f64, 16 rows of an M x M block being the A operand and the vectors the 16-wide
+ * B operand (vectors that do not exist are zero operands).  One workgroup per DESTINATION node, NO floating-point atomics: every sum
+ * has a shape fixed by the plan -- a leaf adds its DoFs in ascending order, a parent its children in ascending node number, n1 its
+ * pairs in ascending pair index, and every child and every leaf DoF has one writer.  The bits of Y[v] depend on the plan, on K, V, T,
+ * X[v] and the old Y[v] only: not on nvec, not on the position v, not on the other vectors, not on the call.  (They are not the bits
+ * of pnl_h2_matvec, whose sums have another shape and an order left to the atomics.)  pnl_h2_set feeds these calls as it feeds
+ * pnl_h2_matvec: they read the same K and V.  Asynchronous on the context's stream.
+ * PNL_ERR_STATE without pnl_h2_setup.  PNL_ERR_INVALID, before any launch, for null pointers, nvec < 1, nvec > 16 in the three phase
+ * calls, ldx < N, ldy < N, X_dev == Y_dev (cupB_dev == cdownB_dev in pnl_h2_interact_block). */
+int pnl_h2_matvec_block(pnl_context *ctx, int nvec, const double *X_dev, int64_t ldx, double *Y_dev, int64_t ldy);
+int pnl_h2_upward_block(pnl_context *ctx, int nvec, const double *X_dev, int64_t ldx, double *cupB_dev);
+int pnl_h2_interact_block(pnl_context *ctx, const double *cupB_dev, double *cdownB_dev);
+int pnl_h2_downward_block(pnl_context *ctx, int nvec, double *cdownB_dev, double *Y_dev, int64_t ldy);
 
 /* y = A x for the uploaded pattern (CSR: diag_dev NULL; SSS: lower triangle + diagonal, y = (L + D + L^T) x):
  * CSR_LinearOperator.matvec / SSS_LinearOperator.matvec */

@@ -34,7 +34,8 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_gemv_axpby', 'pnl_csr_matvec', 'pnl_mg_create', 'pnl_mg_destroy', 'pnl_mg_cycle', 'pnl_mg_solve', 'pnl_mg_cg', 'pnl_theta_step', 'pnl_selftest',
            'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs',
            'pnl_csr_cg_jacobi', 'pnl_fe_space_create', 'pnl_fe_space_destroy', 'pnl_assemble_nonlinearity', 'pnl_imex_create',
-           'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi', 'pnl_gemv_block', 'pnl_spmv_block', 'pnl_uniform_lane_layout']
+           'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi', 'pnl_gemv_block', 'pnl_spmv_block', 'pnl_uniform_lane_layout',
+           'pnl_h2_matvec_block', 'pnl_h2_upward_block', 'pnl_h2_interact_block', 'pnl_h2_downward_block']
 
 PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
 PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
@@ -228,6 +229,10 @@ def load():
     L.pnl_h2_interact.argtypes = [vp, vp, vp]
     L.pnl_h2_downward.argtypes = [vp, vp, vp]
     L.pnl_h2_sizes.argtypes = [vp, vp]
+    L.pnl_h2_matvec_block.argtypes = [vp, i32, vp, i64, vp, i64]
+    L.pnl_h2_upward_block.argtypes = [vp, i32, vp, i64, vp]
+    L.pnl_h2_interact_block.argtypes = [vp, vp, vp]
+    L.pnl_h2_downward_block.argtypes = [vp, i32, vp, vp, i64]
     L.pnl_assemble_pairs_in_horizon.argtypes = [vp, vp, vp]
     L.pnl_assemble_pairs_in_horizon_range.argtypes = [vp, vp, vp, i32, i32]
     L.pnl_set_order_function.argtypes = [vp, C.POINTER(pnl_order_function), vp, vp, dbl, dbl, dbl, dbl]
@@ -692,6 +697,11 @@ class Context:
         """Y[v] = A X[v] for the uploaded pattern (CSR: diag_ptr 0; SSS: lower triangle + diagonal)"""
         self.check(self.L.pnl_spmv_block(self.h, C.c_void_p(data_ptr) if data_ptr else None, C.c_void_p(diag_ptr) if diag_ptr else None, int(nvec),
                                          C.c_void_p(X_ptr) if X_ptr else None, int(ldx), C.c_void_p(Y_ptr) if Y_ptr else None, int(ldy)))
+
+    def h2_matvec_block(self, nvec, X_ptr, ldx, Y_ptr, ldy):
+        """Y[v] += far field of X[v] for the H2 operator set up in the context, without float atomics (pnl_h2_block.hip)"""
+        self.check(self.L.pnl_h2_matvec_block(self.h, int(nvec), C.c_void_p(X_ptr) if X_ptr else None, int(ldx),
+                                              C.c_void_p(Y_ptr) if Y_ptr else None, int(ldy)))
 
     def csr_matvec(self, nrows, indptr_ptr, indices_ptr, data_ptr, x_ptr, alpha, beta, y_ptr):
         self.check(self.L.pnl_csr_matvec(self.h, int(nrows), C.c_void_p(indptr_ptr), C.c_void_p(indices_ptr), C.c_void_p(data_ptr),

@@ -876,7 +876,8 @@ class nonlocalBuilder:
                     self._geom_cache['h2plan_key'], self._geom_cache['h2plan'] = pkey, plan
             if getattr(Anear, '_finish', None) is not None:
                 Anear._finish()
-            h2 = H2Matrix(Anear, plan, self.context(), root, Pfar)
+            # params['farField']: 'atomic' (default) or 'ordered' (fixed-order sums, block products in one pass; H2Matrix.farField)
+            h2 = H2Matrix(Anear, plan, self.context(), root, Pfar, farField=self.params.get('farField', 'atomic'))
         out = (h2,)
         if returnNearField:
             out += (Pnear,)

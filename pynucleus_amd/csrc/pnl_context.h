@@ -116,7 +116,7 @@ struct pnl_context {
         b_foff, b_fbary, b_fw, b_bvid, b_bv, b_bgeo, b_counters, b_D, b_tiles,
         b_vec[6], b_clabel, b_blabel, b_clsof, b_scal, b_wl, b_wlcount, b_tilectr, b_ttn, b_ttoff, b_tttab, b_ttwphi, b_wlsorted, b_wlaux,
         b_vertices, b_sp_indptr, b_sp_indices, b_mp_pairs, b_mp_masks, b_mp_wl, b_mp_sorted, b_mp_aux, b_bi_cells, b_bi_facets,
-        b_bi_masks, b_cp[28], b_cpD, b_wlds, b_wlpair, b_h2[20];
+        b_bi_masks, b_cp[28], b_cpD, b_wlds, b_wlpair, b_h2[27];
     // second-generation tile kernels (pnl_tile2.h): per-class kernel / order-formula tables, rules of the uniform-order tiles,
     // class word of every tile entry (2 class + orientation), w and w phi of the packed rules
     DevBuf b_kcls, b_fcls, b_uni, b_tilecls, b_ttwphif;
@@ -179,6 +179,9 @@ struct pnl_context {
     std::vector<std::vector<int>> h2_levels;   // nodes of every level >= 1
     long long h2_vtot = 0;                    // doubles of the leaf values V (pnl_h2_get / _set)
     std::vector<size_t> h2_level_off;
+    // block far field (pnl_h2_block.hip): b_h2[20 .. 24] = pairs per n1 (ptr, idx), children per node (ptr, idx), parents by level
+    // with h2_par_off [nlevels + 1] into that list; b_h2[25], [26] = the context's own cupB / cdownB [nnodes][M][16]
+    std::vector<size_t> h2_par_off;
     std::vector<int32_t> rule_off, frule_off;   // host copies of the distant-rule offsets (cell points, facet points) per order
     int sp_nnz = -1;                // near-field sparsity pattern (pnl_upload_sparsity)
     unsigned wl_cap = 0;
@@ -441,6 +444,9 @@ void pnl_scatter_diag(pnl_context *ctx, const DevProblem &P, const double *D, do
 int pnl_tile_uniform_order(const pnl_context *ctx, const pnl_order_formula &F, int ta, int tb, int qlimit);
 // pnl_sparse.hip: pnl_assembly_ready, the uploaded pattern and the output checked, pnl_refresh_tables, S filled in -- in that order
 int pnl_sparse_ready(pnl_context *ctx, double *data, double *diag, SparseOut &S);
+
+// pnl_h2_block.hip, for pnl_h2_setup once it has validated the plan: the index structures of the block far field
+int pnl_h2_block_plan(pnl_context *ctx, const pnl_h2_plan *pl);
 
 // pnl_setup.hip / pnl_pwnear.hip: kernels with an order per quadrature point
 int pnl_pw_prepare(pnl_context *ctx, int need_boundary);

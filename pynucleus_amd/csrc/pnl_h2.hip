@@ -1,5 +1,5 @@
 // H2 far field of the nonlocal operators (gfx950 only): kernels and host code of pnl_h2_setup, pnl_h2_matvec and its three phases,
-// pnl_h2_get / _set / _sizes.  The near field of an H2 operator is assembled by pnl_hip.hip (pnl_assemble_clusters_tiled).
+// pnl_h2_get / _set / _sizes.  The atomic-free far field for blocks of vectors is pnl_h2_block.hip.  The near field of an H2 operator is assembled by pnl_hip.hip (pnl_assemble_clusters_tiled).
 //
 // Reference (clusterMethodCy.pyx): Chebyshev interpolation of the kernel on admissible cluster pairs
 // (assembleFarFieldInteractions :2153-2238, factor -2 for the (u(x)-u(y))(v(x)-v(y)) form), leaf values
@@ -283,6 +283,7 @@ int pnl_h2_setup(pnl_context *ctx, const pnl_h2_plan *pl) {
     }
     ctx->h2_level_off[pl->nlevels] = cat.size();
     if ((rc = upload(ctx, B[17], cat.data(), cat.size()))) return rc;
+    if ((rc = pnl_h2_block_plan(ctx, pl))) return rc;
     HIPCHK(ctx, hipMemsetAsync(H.V, 0, sizeof(double)*(size_t)std::max<long long>(vtot, 1), ctx->stream));
     const double *qb = (const double*)B[14].p, *qw = (const double*)B[15].p, *qp = (const double*)B[16].p;
     if ((rc = with_shape(ctx, [&](auto D, auto E) {

@@ -3,7 +3,8 @@
 Mirrors /root/reference/nl/PyNucleus_nl/clusterMethodCy.pyx: H2Matrix :2240-2320 (matvec = near field + upward pass +
 far-field interactions + downward pass), tree_node.prepareTransferOperators :1071-1090 with transferMatrixBuilder
 :2004-2073, the interpolation order of getH2RefinementParams (nonlocalAssembly_{SCALAR}.pxi:2990-3000).  The kernel
-interpolants, the leaf values and the three passes run in libpnl_hip.so (pnl_h2_setup / pnl_h2_matvec); the transfer
+interpolants, the leaf values and the three passes run in libpnl_hip.so (pnl_h2_setup / pnl_h2_matvec, or pnl_h2_matvec_block
+for blocks of vectors without float atomics: H2Matrix.farField = 'ordered'); the transfer
 matrices (pure geometry, a few hundred M x M blocks) are built here.
 """
 import ctypes as C
@@ -133,10 +134,31 @@ class h2Plan:
 
 
 class H2Matrix(blockProducts):
-    """y = Anear x + (far field through the cluster tree); clusterMethodCy.pyx:2240-2295.  ``matvec_multi`` / ``dotMV`` loop
-    ``matvec`` over the vectors (blockProducts): a uniform API with the bits of ``matvec``; a multi-vector far field is a follow-up."""
+    """y = Anear x + (far field through the cluster tree); clusterMethodCy.pyx:2240-2295.
 
-    def __init__(self, Anear, plan, ctx, root, Pfar):
+    ``farField`` selects how the far field is summed.
+    'atomic' (the default): one wave per child / admissible pair, merged with float atomics (pnl_h2_matvec); ``matvec_multi`` /
+    ``dotMV`` loop ``matvec`` over the vectors (blockProducts), a uniform API with the bits of ``matvec``.
+    'ordered': one workgroup per destination node adds its sources in the order of the plan, up to 16 vectors in one pass over K, T and
+    V (pnl_h2_matvec_block), the near field through ``Anear.matvec_multi`` (pnl_spmv_block).  ``matvec`` is the one-vector case of
+    ``matvec_multi``, so with the default CSR near field ``matvec_multi(X)[v]`` has the bits of ``matvec(X[v])`` and repeated products
+    give identical bits.  With an SSS near field (``forceUnsymmetric=False``) only the far field is ordered: the mirrored entries of the
+    near field still go through atomics.  The two modes agree to rounding, not bit for bit."""
+
+    FAR_FIELD_MODES = ('atomic', 'ordered')
+
+    @property
+    def farField(self):
+        return self._farField
+
+    @farField.setter
+    def farField(self, mode):
+        if mode not in self.FAR_FIELD_MODES:
+            raise ValueError('farField is one of {}, not {!r}'.format(self.FAR_FIELD_MODES, mode))
+        self._farField = mode
+
+    def __init__(self, Anear, plan, ctx, root, Pfar, farField='atomic'):
+        self.farField = farField
         self.Anear, self.plan, self.ctx = Anear, plan, ctx
         self.tree, self.Pfar = root, Pfar
         self.num_rows, self.num_columns = Anear.num_rows, Anear.num_columns
@@ -154,6 +176,13 @@ class H2Matrix(blockProducts):
         from .linear_operators import _as_dev, _ndim
         if _ndim(x) == 2:
             return self._dot_2d(x, y)
+        if self.farField == 'ordered':
+            # the one-vector case of the block path: the same kernels, the same bits
+            out = self.matvec_multi(x[None, :] if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)[None, :])[0]
+            if y is not None and not isinstance(x, torch.Tensor):
+                y[:] = out
+                return y
+            return out
         self._ensure_setup()
         xd = _as_dev(x, self.device)
         yd = self.Anear.matvec(xd)
@@ -170,6 +199,21 @@ class H2Matrix(blockProducts):
 
     __mul__ = matvec
     dot = matvec
+
+    def matvec_multi(self, X, Y=None):
+        """Y[v] = A X[v] for the rows of X.  'atomic': a loop of ``matvec``.  'ordered': near field through ``Anear.matvec_multi``, far
+        field through pnl_h2_matvec_block, K, T and V read once per 16 vectors"""
+        from .linear_operators import _as_block, _block_out, matvec_multi_loop
+        if self.farField != 'ordered':
+            return matvec_multi_loop(self, X, Y)
+        self._ensure_setup()
+        Xd = _as_block(X, self.device)
+        k = Xd.shape[0]
+        assert k >= 1 and Xd.shape[1] == self.num_columns, (tuple(Xd.shape), self.num_columns)
+        Yd = self.Anear.matvec_multi(Xd)
+        self.ctx.h2_matvec_block(k, Xd.data_ptr(), max(int(Xd.stride(0)), self.num_columns), Yd.data_ptr(), int(Yd.stride(0)))
+        self.ctx.synchronize()
+        return _block_out(X, Yd, Y)
 
     @property
     def diagonal(self):
@@ -340,10 +384,18 @@ class H2Matrix(blockProducts):
         return op
 
     def toarray(self):
-        """dense image through N matvecs (tests only)"""
+        """dense image through N matvecs, 16 unit vectors per pass in 'ordered' mode (tests only)"""
         import torch
         N = self.num_columns
         A = np.zeros((self.num_rows, N))
+        if self.farField == 'ordered':
+            E = torch.zeros((16, N), dtype=torch.float64, device=self.device)
+            for j0 in range(0, N, 16):
+                k = min(16, N-j0)
+                E.zero_()
+                E[torch.arange(k), torch.arange(j0, j0+k)] = 1.
+                A[:, j0:j0+k] = self.matvec_multi(E[:k]).cpu().numpy().T
+            return A
         e = torch.zeros(N, dtype=torch.float64, device=self.device)
         for j in range(N):
             e.zero_()

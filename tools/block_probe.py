@@ -2,11 +2,14 @@
 
   pnl_gemv_block for nvec in {1, 2, 4, 8, 16, 32} against the same number of pnl_gemv mode-0 calls on a random N x N block with the
   builder's row padding; 8 N^2 / t per pass over the block in TB/s (k_gemv: 6.05 TB/s at N = 48,769) and the ratio loop / block;
-  pnl_spmv_block against repeated pnl_spmv on the near-field pattern of the H2 configuration of bench.py (disc, s = 0.75, eta = 3).
+  pnl_spmv_block against repeated pnl_spmv on the near-field pattern of the H2 configuration of bench.py (disc, s = 0.75, eta = 3);
+  the H2 operator of that configuration: matvec_multi of 1, 2, 16 and 17 vectors with farField = 'ordered' against as many looped
+  matvec calls with farField = 'atomic', the single-vector ratio ordered / atomic, and the far field alone (pnl_h2_matvec_block against
+  looped pnl_h2_matvec) with the bytes of K, T and V and the resulting GB/s.
 
 Device events around a window of >= 0.2 s after three warm-up calls of every shape; block and loop alternate, three rounds, the
 median is reported.  Prints one JSON line.
-usage: block_probe.py [--n N ...] [--nvec K ...] [--h2-noref R | --no-spmv]      (defaults: --n 12097 48769 --h2-noref 7)"""
+usage: block_probe.py [--n N ...] [--nvec K ...] [--h2-noref R] [--no-spmv] [--no-h2]      (defaults: --n 12097 48769 --h2-noref 7)"""
 import argparse
 import json
 import os
@@ -104,12 +107,67 @@ def sparse(noref):
     return out
 
 
+def h2(noref):
+    """the H2 operator of bench.py's H2 configuration: matvec_multi in 'ordered' mode (pnl_spmv_block + pnl_h2_matvec_block) against
+    looped matvec calls in 'atomic' mode (pnl_spmv + pnl_h2_matvec), the two single-vector products, and the far field alone with the
+    bytes of K, T and V it reads per pass (T and V twice: upward and downward)"""
+    from pynucleus_amd import disc, P1_DoFMap, PHYSICAL, getFractionalKernel
+    from pynucleus_amd.builder import nonlocalBuilder
+    dm = P1_DoFMap(disc(noref), PHYSICAL)
+    b = nonlocalBuilder(dm, getFractionalKernel(2, 0.75), {'target_order': 0.5, 'eta': 3.}, zeroExterior=True)
+    H = b.getH2()
+    ctx, N, pl = H.ctx, H.num_rows, H.plan
+    g = torch.Generator(device='cuda'); g.manual_seed(3)
+    X = torch.rand((17, N), dtype=torch.float64, device='cuda', generator=g)
+    Y = torch.zeros((17, N), dtype=torch.float64, device='cuda')
+    Y1 = torch.zeros_like(Y)
+    nbytes = dict(K=8*int(pl.far.shape[0])*pl.M*pl.M, T=8*len(pl.nodes)*pl.M*pl.M, V=8*int(pl.leaf_dof_off[-1])*pl.M)
+    per_pass = nbytes['K']+2*nbytes['T']+2*nbytes['V']
+    out = dict(N=N, M=pl.M, nnodes=len(pl.nodes), nfar=int(pl.far.shape[0]), nlevels=int(pl.nlevels), bytes=nbytes, bytes_per_pass=per_pass,
+               nvec={}, far_only={})
+
+    def mode(m):
+        H.farField = m
+        H._ensure_setup()
+    for k in (1, 2, 16, 17):
+        def block():
+            H.matvec_multi(X[:k])
+
+        def loop():
+            for v in range(k):
+                H.matvec(X[v])
+        tb, tl = [], []
+        for _ in range(3):
+            mode('ordered'); tb.append(timed(ctx, block))
+            mode('atomic'); tl.append(timed(ctx, loop))
+        tb, tl = statistics.median(tb), statistics.median(tl)
+        mode('ordered'); yo = H.matvec_multi(X[:k])
+        mode('atomic'); ya = torch.stack([H.matvec(X[v]) for v in range(k)])
+        out['nvec'][k] = dict(ordered_block_ms=1e3*tb, atomic_loop_ms=1e3*tl, loop_over_block=tl/tb,
+                              max_rel_diff=float((yo-ya).abs().max()/ya.abs().max()))
+        # the far field alone, without the operator's synchronisations
+        def fblock():
+            ctx.h2_matvec_block(k, X.data_ptr(), N, Y.data_ptr(), N)
+
+        def floop():
+            for v in range(k):
+                ctx.check(ctx.L.pnl_h2_matvec(ctx.h, X[v].data_ptr(), Y1[v].data_ptr()))
+        fb, fl = median_pair(ctx, fblock, floop)
+        passes = (k+15)//16
+        out['far_only'][k] = dict(block_ms=1e3*fb, loop_ms=1e3*fl, loop_over_block=fl/fb, block_GBps=passes*per_pass/fb/1e9,
+                                  loop_GBps=k*per_pass/fl/1e9)
+    out['single_ordered_over_atomic'] = out['nvec'][1]['ordered_block_ms']/out['nvec'][1]['atomic_loop_ms']
+    out['loop16_over_block16'] = out['nvec'][16]['loop_over_block']
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, nargs='*', default=[12097, 48769])
     ap.add_argument('--nvec', type=int, nargs='*', default=list(NVECS))
     ap.add_argument('--h2-noref', type=int, default=7)
     ap.add_argument('--no-spmv', action='store_true')
+    ap.add_argument('--no-h2', action='store_true')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'block_probe.py needs a GPU'
     ctx = _lib.Context(0)
@@ -118,6 +176,8 @@ def main():
     ctx.close()
     if not a.no_spmv:
         res['spmv_block'] = sparse(a.h2_noref)
+    if not a.no_h2:
+        res['h2_block'] = h2(a.h2_noref)
     print(json.dumps(res))
 
 
