@@ -744,6 +744,52 @@ int pnl_gemv_block(pnl_context *ctx, const double *A_dev, int64_t ldA, int nrows
 int pnl_spmv_block(pnl_context *ctx, const double *data_dev, const double *diag_dev, int nvec, const double *X_dev, int64_t ldx,
                    double *Y_dev, int64_t ldy);
 
+/* ---- Jacobi-preconditioned CG for a block of right-hand sides (csrc/pnl_cg_block.hip): cg_solver.solve + jacobi_solver
+ *      (base/PyNucleus_base/solvers.pyx:363-444, 229-245) for A X = B with several right-hand sides at once. --------------------------
+ * Up to PNL_CGB_MAXVEC = 16 right-hand sides ("columns", stored one per row as in pnl_gemv_block) are solved together.  Every column
+ * runs its OWN recurrence of pnl_cg_jacobi (its own alpha, beta and convergence; not a block Krylov method) and the columns share the
+ * operator product, one pass over the operator per iteration.  The loop is that of pnl_cg_jacobi: update order x, r, (refresh),
+ * z = D^-1 r, beta, p; a column has converged when sqrt(r . D^-1 r) <= tol (absolute); the residual is recomputed from b - A x when
+ * the counter reaches 50, for every active column of the group at once; a column that converges in the first pass of the loop reports
+ * 0 iterations, one that never converges reports maxiter.  A column that has converged is FROZEN: its x, r and reported residual are
+ * no longer written.  A column whose r . D^-1 r is 0 at the start (b = 0 with x0 = 0) is frozen at once, with 0 iterations and
+ * residual 0.  More than 16 columns are taken as consecutive groups of 16, each with a loop of its own.
+ * No floating-point atomics: every dot product is summed in a shape that depends on n only.  With a product whose bits are independent
+ * per vector (pnl_gemv_block; pnl_spmv_block on CSR; pnl_h2_matvec_block) the bits of X[v], iters[v] and residuals[v] depend neither
+ * on the number of columns nor on the position v nor on the other columns, and two calls repeat bit for bit.  The scalars stay on the
+ * device; the host reads the state of the group back once per iteration.  Nothing is allocated per call beyond growing buffers of the
+ * context once.  The padding of B and X (ld > n) is neither read into a sum nor written.
+ *
+ * pnl_cg_jacobi_block: A dense, symmetric positive definite, row-major n x n, read in full by pnl_gemv_block (no half-read as
+ * pnl_cg_jacobi).  X_dev holds the initial guesses and the results; iters[nrhs] and residuals[nrhs] on the host (either may be NULL).
+ * Synchronous.  PNL_ERR_INVALID, before any launch, for a null ctx, A, B or X; n or nrhs < 1; ldA, ldb or ldx < n; maxiter < 0;
+ * B_dev == X_dev. */
+#define PNL_CGB_MAXVEC 16
+int pnl_cg_jacobi_block(pnl_context *ctx, const double *A_dev, int64_t ldA, int n, int nrhs, const double *B_dev, int64_t ldb, double *X_dev,
+                        int64_t ldx, double tol, int maxiter, int *iters, double *residuals);
+/* The steps of that loop on caller-owned device blocks [nvec][ld], nvec <= 16, for operators whose product is not a dense block
+ * (pnl_cg_jacobi_block is these calls around pnl_gemv_block).  dinv_dev: 1 / diagonal, n doubles; NULL: the unit diagonal (no
+ * preconditioner).  state_dev: PNL_CGB_STATE doubles per column, column v at state_dev[v * PNL_CGB_STATE]:
+ *   [0] betaOld = r . z of the pass before   [1] p . Ap   [2] beta = r . z   [3] conv = sqrt(beta)   [4] active (1 or 0)   [5 .. 7] 0
+ *   pnl_cgb_init       R = B - AX (AX_dev NULL: X is zero, R = B), P = dinv R, betaOld = beta = R . P, conv, active = conv > tol and
+ *                      beta != 0; writes the whole state of the columns v < nvec
+ *   pnl_cgb_update     active columns: alpha = betaOld / (P . AP); X += alpha P; R -= alpha AP; Z = dinv R; beta = R . Z; conv
+ *   pnl_cgb_refresh    active columns: R = B - AX, Z = dinv R, beta = R . Z, conv      (the recomputation every 50 iterations)
+ *   pnl_cgb_direction  active columns: conv <= tol: active = 0, nothing else is written; else P = Z + (beta / betaOld) P, betaOld = beta
+ * A pass of the loop is: AP = A P; update; every 50th pass AX = A X and refresh; direction; read the state.  Columns that are not
+ * active are neither read nor written.  Asynchronous on the context's stream.  PNL_ERR_INVALID, before any launch, for a null
+ * pointer (but dinv_dev, and AX_dev in pnl_cgb_init), n < 1, nvec < 1, nvec > 16, a leading dimension below n, two blocks that are
+ * written or read and written being the same. */
+#define PNL_CGB_STATE 8
+int pnl_cgb_init(pnl_context *ctx, int n, int nvec, const double *dinv_dev, const double *B_dev, int64_t ldb, const double *AX_dev, int64_t ldax,
+                 double *R_dev, int64_t ldr, double *P_dev, int64_t ldp, double tol, double *state_dev);
+int pnl_cgb_update(pnl_context *ctx, int n, int nvec, const double *dinv_dev, const double *P_dev, int64_t ldp, const double *AP_dev, int64_t ldap,
+                   double *X_dev, int64_t ldx, double *R_dev, int64_t ldr, double *Z_dev, int64_t ldz, double *state_dev);
+int pnl_cgb_refresh(pnl_context *ctx, int n, int nvec, const double *dinv_dev, const double *B_dev, int64_t ldb, const double *AX_dev, int64_t ldax,
+                    double *R_dev, int64_t ldr, double *Z_dev, int64_t ldz, double *state_dev);
+int pnl_cgb_direction(pnl_context *ctx, int n, int nvec, const double *Z_dev, int64_t ldz, double *P_dev, int64_t ldp, double tol,
+                      double *state_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,12 +35,14 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_potrf', 'pnl_potrs', 'pnl_getrf', 'pnl_getrs',
            'pnl_csr_cg_jacobi', 'pnl_fe_space_create', 'pnl_fe_space_destroy', 'pnl_assemble_nonlinearity', 'pnl_imex_create',
            'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi', 'pnl_gemv_block', 'pnl_spmv_block', 'pnl_uniform_lane_layout',
-           'pnl_h2_matvec_block', 'pnl_h2_upward_block', 'pnl_h2_interact_block', 'pnl_h2_downward_block']
+           'pnl_h2_matvec_block', 'pnl_h2_upward_block', 'pnl_h2_interact_block', 'pnl_h2_downward_block',
+           'pnl_cg_jacobi_block', 'pnl_cgb_init', 'pnl_cgb_update', 'pnl_cgb_refresh', 'pnl_cgb_direction']
 
 PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
 PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
 PNL_IMEX_MAX_STAGES, PNL_IMEX_MAX_COMP = 4, 2
 PNL_INTERP_MAX_OPS = 21
+PNL_CGB_MAXVEC, PNL_CGB_STATE = 16, 8
 
 
 def source_sha16():
@@ -214,6 +216,11 @@ def load():
     L.pnl_gemv_multi.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, dbl, dbl, vp, vp]
     L.pnl_gemv_block.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, dbl, dbl, vp, i64, vp, i64]
     L.pnl_spmv_block.argtypes = [vp, vp, vp, i32, vp, i64, vp, i64]
+    L.pnl_cg_jacobi_block.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, i64, dbl, i32, vp, vp]
+    L.pnl_cgb_init.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, dbl, vp]
+    L.pnl_cgb_update.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.pnl_cgb_refresh.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.pnl_cgb_direction.argtypes = [vp, i32, i32, vp, i64, vp, i64, dbl, vp]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
     L.pnl_upload_sparsity_device.argtypes = [vp, i32, vp, vp]
     L.pnl_set_classes.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -301,6 +308,11 @@ def selftest(op, x, path=0, dim=1, boundary=False, param=None):
     if rc != PNL_OK:
         raise PnlError('pnl_selftest(op={}, path={}) failed: {}'.format(op, path, rc))
     return out
+
+
+def _vp(ptr):
+    """a device or host address as a pointer argument; 0 / None: the null pointer"""
+    return C.c_void_p(ptr) if ptr else None
 
 
 def _hp(a, dtype):
@@ -697,6 +709,34 @@ class Context:
         """Y[v] = A X[v] for the uploaded pattern (CSR: diag_ptr 0; SSS: lower triangle + diagonal)"""
         self.check(self.L.pnl_spmv_block(self.h, C.c_void_p(data_ptr) if data_ptr else None, C.c_void_p(diag_ptr) if diag_ptr else None, int(nvec),
                                          C.c_void_p(X_ptr) if X_ptr else None, int(ldx), C.c_void_p(Y_ptr) if Y_ptr else None, int(ldy)))
+
+    # -- Jacobi-CG for a block of right-hand sides (pnl_cg_block.hip): column v is B[v*ldb .. v*ldb + n) ---
+    def cg_jacobi_block(self, A_ptr, ldA, n, nrhs, B_ptr, ldb, X_ptr, ldx, tol, maxiter):
+        """every column its own Jacobi-CG recurrence, one pnl_gemv_block pass per iteration and group of 16; X holds the initial guesses
+        and the results.  Returns (iterations [nrhs] int32, residuals [nrhs])"""
+        its, res = np.zeros(max(int(nrhs), 1), dtype=np.int32), np.zeros(max(int(nrhs), 1))
+        self.check(self.L.pnl_cg_jacobi_block(self.h, _vp(A_ptr), int(ldA), int(n), int(nrhs), _vp(B_ptr), int(ldb), _vp(X_ptr), int(ldx),
+                                              float(tol), int(maxiter), its.ctypes.data, res.ctypes.data))
+        return its, res
+
+    def cgb_init(self, n, nvec, dinv_ptr, B_ptr, ldb, AX_ptr, ldax, R_ptr, ldr, P_ptr, ldp, tol, state_ptr):
+        """R = B - AX (AX_ptr 0: R = B), P = dinv R, the state of every column (include/pnl_hip.h)"""
+        self.check(self.L.pnl_cgb_init(self.h, int(n), int(nvec), _vp(dinv_ptr), _vp(B_ptr), int(ldb), _vp(AX_ptr), int(ldax), _vp(R_ptr), int(ldr),
+                                       _vp(P_ptr), int(ldp), float(tol), _vp(state_ptr)))
+
+    def cgb_update(self, n, nvec, dinv_ptr, P_ptr, ldp, AP_ptr, ldap, X_ptr, ldx, R_ptr, ldr, Z_ptr, ldz, state_ptr):
+        """active columns: alpha = betaOld / P.AP, X += alpha P, R -= alpha AP, Z = dinv R, beta = R.Z, conv"""
+        self.check(self.L.pnl_cgb_update(self.h, int(n), int(nvec), _vp(dinv_ptr), _vp(P_ptr), int(ldp), _vp(AP_ptr), int(ldap), _vp(X_ptr), int(ldx),
+                                         _vp(R_ptr), int(ldr), _vp(Z_ptr), int(ldz), _vp(state_ptr)))
+
+    def cgb_refresh(self, n, nvec, dinv_ptr, B_ptr, ldb, AX_ptr, ldax, R_ptr, ldr, Z_ptr, ldz, state_ptr):
+        """active columns: R = B - AX, Z = dinv R, beta = R.Z, conv"""
+        self.check(self.L.pnl_cgb_refresh(self.h, int(n), int(nvec), _vp(dinv_ptr), _vp(B_ptr), int(ldb), _vp(AX_ptr), int(ldax), _vp(R_ptr), int(ldr),
+                                          _vp(Z_ptr), int(ldz), _vp(state_ptr)))
+
+    def cgb_direction(self, n, nvec, Z_ptr, ldz, P_ptr, ldp, tol, state_ptr):
+        """active columns: frozen where conv <= tol, else P = Z + (beta / betaOld) P and betaOld = beta"""
+        self.check(self.L.pnl_cgb_direction(self.h, int(n), int(nvec), _vp(Z_ptr), int(ldz), _vp(P_ptr), int(ldp), float(tol), _vp(state_ptr)))
 
     def h2_matvec_block(self, nvec, X_ptr, ldx, Y_ptr, ldy):
         """Y[v] += far field of X[v] for the H2 operator set up in the context, without float atomics (pnl_h2_block.hip)"""

@@ -1,0 +1,349 @@
+// Jacobi-preconditioned CG for a block of right-hand sides (gfx950 only): pnl_cg_jacobi_block for a dense symmetric positive definite
+// block, and the steps of its loop (pnl_cgb_init / _update / _refresh / _direction) for operators whose product is made elsewhere.
+//
+// Reference: cg_solver.solve (base/PyNucleus_base/solvers.pyx:363-444) with the Jacobi preconditioner (:229-245), as pnl_cg_jacobi
+// (pnl_solver.hip) restates it: update order x, r, (refresh), z = D^-1 r, beta, p; convergence on sqrt(r . D^-1 r) <= tol; the residual
+// recomputed from b - A x when the counter reaches 50.
+//
+// Up to CGB_NV = 16 right-hand sides ("columns", stored one per row as in pnl_gemv_block) are solved together.  Every column runs its
+// OWN recurrence -- its own alpha, beta and convergence; this is not O'Leary's block CG -- and the columns share the operator
+// product: one pnl_gemv_block pass over the matrix per iteration.  A column that has converged is frozen: its x, r, z, p and its
+// state are no longer written (the product still carries it along; its result is not used).
+//
+// Kernels, all over [nvec][n] blocks with ONE grid rule, cgb_blocks(n) = min(CGB_MAXBLK, ceil(n / 256)) workgroups of 256 threads,
+// element i of every column in thread (i mod 256) of workgroup (i / 256) mod blocks:
+//   k_cgb_pap        partial sums of p . Ap per column and workgroup                                         -> part[0][wg][16]
+//   k_cgb_update     every workgroup adds those partials (cgb_totals) to get alpha = betaOld / p.Ap, then x += alpha p,
+//                    r -= alpha Ap, z = dinv r and the partial sums of r . z                                  -> part[1][wg][16]
+//   k_cgb_residual   r = b - Ax, out = dinv r (out = p at the start, z in a refresh), partial sums of r . out  -> part[1][wg][16]
+//   k_cgb_finish     one workgroup: adds the partials of part[1] and writes beta and conv (at the start: betaOld, conv, active)
+//   k_cgb_direction  p = z + (beta / betaOld) p for the columns that go on
+//   k_cgb_advance    one workgroup: betaOld = beta, or active = 0 where conv <= tol
+// The scalars stay on the device (state: PNL_CGB_STATE doubles per column); the driver reads the state back once per iteration.
+//
+// No floating-point atomics.  A dot product is summed in a fixed shape that depends on n only: per thread in ascending i (fma), the
+// 64 lanes in the DPP tree of wave_sum, the four waves in ascending order, the workgroups in 16 interleaved runs in ascending order
+// and those 16 in ascending order (cgb_totals).  With a product whose bits are independent per vector (pnl_gemv_block,
+// pnl_spmv_block on CSR, the ordered H2 far field) the bits of X[v], its iteration count and its residual therefore depend neither
+// on nvec nor on the position v nor on the other columns, and two calls repeat bit for bit.  The redundant final adds cost
+// 16 x blocks loads per workgroup, which the cap CGB_MAXBLK bounds at 4096.
+#include "pnl_context.h"
+#include "pnl_common.h"
+
+namespace {
+
+constexpr int CGB_NV = PNL_CGB_MAXVEC;     // columns per group = vectors per pass of the block products
+constexpr int CGB_THREADS = 256;
+constexpr int CGB_MAXBLK = 256;            // workgroups per launch at most (one per CU)
+constexpr int CGB_PART = CGB_MAXBLK*CGB_NV;
+static_assert(CGB_NV == 16 && CGB_THREADS == 16*CGB_NV, "cgb_totals: 16 runs of partial sums x 16 columns");
+
+// slots of the per-column state (include/pnl_hip.h)
+enum { ST_BETA_OLD = 0, ST_PAP = 1, ST_BETA = 2, ST_CONV = 3, ST_ACTIVE = 4 };
+
+inline int cgb_blocks(int n) { return std::min(CGB_MAXBLK, (n+CGB_THREADS-1)/CGB_THREADS); }
+
+// bit v: column v < nv is active
+__device__ __forceinline__ unsigned cgb_active_mask(const double *__restrict__ state, int nv) {
+    unsigned m = 0;
+    for (int v = 0; v < nv; v++) m |= state[v*PNL_CGB_STATE+ST_ACTIVE] != 0. ? 1u << v : 0u;
+    return m;
+}
+
+// the workgroup's sums of the thread values s[v] for the columns of mask (0 for the others) -> row[0 .. 16)
+__device__ __forceinline__ void cgb_block_sums(const double (&s)[CGB_NV], unsigned mask, double *__restrict__ row) {
+    __shared__ double sw[CGB_THREADS/64][CGB_NV];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+    for (int v = 0; v < CGB_NV; v++) {
+        if ((mask >> v) & 1) {                     // uniform over the workgroup
+            const double t = wave_sum(s[v]);
+            if (lane == 0) sw[wv][v] = t;
+        }
+    }
+    __syncthreads();
+    if (tid < CGB_NV) row[tid] = ((mask >> tid) & 1) ? ((sw[0][tid]+sw[1][tid])+sw[2][tid])+sw[3][tid] : 0.;
+}
+
+// tot[v] = sum of part[k][v] over the nb workgroups, v < 16: thread (j, v) adds the run k = j, j + 16, ... in ascending order, then
+// the 16 runs are added in ascending j.  Ends with a barrier: every thread may read tot.
+__device__ __forceinline__ void cgb_totals(const double *__restrict__ part, int nb, double *tot) {
+    __shared__ double sp[CGB_NV][CGB_NV+1];
+    const int tid = threadIdx.x, v = tid & 15, j = tid >> 4;
+    double s = 0.;
+    for (int k = j; k < nb; k += 16) s += part[k*CGB_NV+v];
+    sp[j][v] = s;
+    __syncthreads();
+    if (tid < CGB_NV) {
+        double t = sp[0][tid];
+#pragma unroll
+        for (int jj = 1; jj < 16; jj++) t += sp[jj][tid];
+        tot[tid] = t;
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(CGB_THREADS)
+k_cgb_pap(int n, int nv, const double *__restrict__ P, long long ldp, const double *__restrict__ AP, long long ldap,
+          const double *__restrict__ state, double *__restrict__ part) {
+    const unsigned mask = cgb_active_mask(state, nv);
+    double s[CGB_NV];
+#pragma unroll
+    for (int v = 0; v < CGB_NV; v++) s[v] = 0.;
+    for (int i = blockIdx.x*CGB_THREADS+threadIdx.x; i < n; i += gridDim.x*CGB_THREADS) {
+#pragma unroll
+        for (int v = 0; v < CGB_NV; v++)
+            if ((mask >> v) & 1) s[v] = __builtin_fma(P[v*ldp+i], AP[v*ldap+i], s[v]);
+    }
+    cgb_block_sums(s, mask, part+(size_t)blockIdx.x*CGB_NV);
+}
+
+// dinv == nullptr: the unit diagonal
+__global__ void __launch_bounds__(CGB_THREADS)
+k_cgb_update(int n, int nv, const double *__restrict__ dinv, const double *__restrict__ P, long long ldp, const double *__restrict__ AP,
+             long long ldap, double *__restrict__ X, long long ldx, double *__restrict__ R, long long ldr, double *__restrict__ Z, long long ldz,
+             double *state, const double *__restrict__ part_pap, double *__restrict__ part_rz) {
+    __shared__ double tot[CGB_NV], al[CGB_NV];
+    const unsigned mask = cgb_active_mask(state, nv);
+    cgb_totals(part_pap, (int)gridDim.x, tot);
+    if (threadIdx.x < CGB_NV) {
+        const int v = threadIdx.x;
+        const bool on = (mask >> v) & 1;
+        al[v] = on ? state[v*PNL_CGB_STATE+ST_BETA_OLD]/tot[v] : 0.;
+        if (on && blockIdx.x == 0) state[v*PNL_CGB_STATE+ST_PAP] = tot[v];       // a slot that no workgroup of this launch reads
+    }
+    __syncthreads();
+    double s[CGB_NV];
+#pragma unroll
+    for (int v = 0; v < CGB_NV; v++) s[v] = 0.;
+    for (int i = blockIdx.x*CGB_THREADS+threadIdx.x; i < n; i += gridDim.x*CGB_THREADS) {
+        const double di = dinv ? dinv[i] : 1.;
+#pragma unroll
+        for (int v = 0; v < CGB_NV; v++) {
+            if ((mask >> v) & 1) {
+                const double alpha = al[v];
+                X[v*ldx+i] = __builtin_fma(alpha, P[v*ldp+i], X[v*ldx+i]);
+                const double ri = __builtin_fma(-alpha, AP[v*ldap+i], R[v*ldr+i]);
+                const double zi = dinv ? di*ri : ri;
+                R[v*ldr+i] = ri;
+                Z[v*ldz+i] = zi;
+                s[v] = __builtin_fma(ri, zi, s[v]);
+            }
+        }
+    }
+    cgb_block_sums(s, mask, part_rz+(size_t)blockIdx.x*CGB_NV);
+}
+
+// r = b - Ax (AX == nullptr: r = b), out = dinv r, partial sums of r . out.  START: every column v < nv; else the active ones
+template <bool START>
+__global__ void __launch_bounds__(CGB_THREADS)
+k_cgb_residual(int n, int nv, const double *__restrict__ dinv, const double *__restrict__ B, long long ldb, const double *__restrict__ AX,
+               long long ldax, double *__restrict__ R, long long ldr, double *__restrict__ Out, long long ldo, const double *__restrict__ state,
+               double *__restrict__ part) {
+    const unsigned mask = START ? (1u << nv)-1u : cgb_active_mask(state, nv);
+    double s[CGB_NV];
+#pragma unroll
+    for (int v = 0; v < CGB_NV; v++) s[v] = 0.;
+    for (int i = blockIdx.x*CGB_THREADS+threadIdx.x; i < n; i += gridDim.x*CGB_THREADS) {
+        const double di = dinv ? dinv[i] : 1.;
+#pragma unroll
+        for (int v = 0; v < CGB_NV; v++) {
+            if ((mask >> v) & 1) {
+                const double ri = AX ? B[v*ldb+i]-AX[v*ldax+i] : B[v*ldb+i];
+                const double oi = dinv ? di*ri : ri;
+                R[v*ldr+i] = ri;
+                Out[v*ldo+i] = oi;
+                s[v] = __builtin_fma(ri, oi, s[v]);
+            }
+        }
+    }
+    cgb_block_sums(s, mask, part+(size_t)blockIdx.x*CGB_NV);
+}
+
+// one workgroup.  START: betaOld = beta = r . p, conv, active = conv > tol (a zero residual is never active: no 0 / 0 later);
+// else, for the active columns, beta = r . z and conv
+template <bool START>
+__global__ void __launch_bounds__(CGB_THREADS)
+k_cgb_finish(int nb, int nv, const double *__restrict__ part, double tol, double *state) {
+    __shared__ double tot[CGB_NV];
+    cgb_totals(part, nb, tot);
+    const int v = threadIdx.x;
+    if (v >= nv) return;
+    double *st = state+v*PNL_CGB_STATE;
+    const double conv = sqrt(tot[v]);
+    if (START) {
+        st[ST_BETA_OLD] = tot[v]; st[ST_PAP] = 0.; st[ST_BETA] = tot[v]; st[ST_CONV] = conv;
+        st[ST_ACTIVE] = (conv > tol && tot[v] != 0.) ? 1. : 0.;
+        for (int k = ST_ACTIVE+1; k < PNL_CGB_STATE; k++) st[k] = 0.;
+    } else if (st[ST_ACTIVE] != 0.) {
+        st[ST_BETA] = tot[v]; st[ST_CONV] = conv;
+    }
+}
+
+// p = z + (beta / betaOld) p for the active columns with conv > tol (the others are frozen by k_cgb_advance behind this launch)
+__global__ void __launch_bounds__(CGB_THREADS)
+k_cgb_direction(int n, int nv, const double *__restrict__ Z, long long ldz, double *__restrict__ P, long long ldp, double tol,
+                const double *__restrict__ state) {
+    __shared__ double tq[CGB_NV];
+    unsigned mask = 0;
+    for (int v = 0; v < nv; v++) {
+        const double *st = state+v*PNL_CGB_STATE;
+        if (st[ST_ACTIVE] != 0. && !(st[ST_CONV] <= tol)) mask |= 1u << v;
+    }
+    if (threadIdx.x < CGB_NV) {
+        const double *st = state+threadIdx.x*PNL_CGB_STATE;
+        tq[threadIdx.x] = ((mask >> threadIdx.x) & 1) ? st[ST_BETA]/st[ST_BETA_OLD] : 0.;
+    }
+    __syncthreads();
+    for (int i = blockIdx.x*CGB_THREADS+threadIdx.x; i < n; i += gridDim.x*CGB_THREADS) {
+#pragma unroll
+        for (int v = 0; v < CGB_NV; v++)
+            if ((mask >> v) & 1) P[v*ldp+i] = __builtin_fma(tq[v], P[v*ldp+i], Z[v*ldz+i]);
+    }
+}
+
+__global__ void k_cgb_advance(int nv, double tol, double *state) {
+    const int v = threadIdx.x;
+    if (v >= nv) return;
+    double *st = state+v*PNL_CGB_STATE;
+    if (st[ST_ACTIVE] == 0.) return;
+    if (st[ST_CONV] <= tol) st[ST_ACTIVE] = 0.;
+    else st[ST_BETA_OLD] = st[ST_BETA];
+}
+
+// the context's scratch for the partial sums: [2][CGB_MAXBLK][16]
+int cgb_part(pnl_context *ctx, double **part) {
+    if (int rc = ensure(ctx, ctx->b_cgb_part, sizeof(double)*2*CGB_PART)) return rc;
+    *part = (double*)ctx->b_cgb_part.p;
+    return PNL_OK;
+}
+
+int cgb_finish(pnl_context *ctx, bool start, int n, int nv, const double *part, double tol, double *state) {
+    if (start) hipLaunchKernelGGL((k_cgb_finish<true>), dim3(1), dim3(CGB_THREADS), 0, ctx->stream, cgb_blocks(n), nv, part, tol, state);
+    else hipLaunchKernelGGL((k_cgb_finish<false>), dim3(1), dim3(CGB_THREADS), 0, ctx->stream, cgb_blocks(n), nv, part, tol, state);
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+
+bool cgb_bad_block(const void *p, int64_t ld, int n) { return !p || ld < n; }
+
+}  // namespace
+
+extern "C" {
+
+int pnl_cgb_init(pnl_context *ctx, int n, int nvec, const double *dinv_dev, const double *B_dev, int64_t ldb, const double *AX_dev, int64_t ldax,
+                 double *R_dev, int64_t ldr, double *P_dev, int64_t ldp, double tol, double *state_dev) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (n < 1 || nvec < 1 || nvec > CGB_NV || cgb_bad_block(B_dev, ldb, n) || cgb_bad_block(R_dev, ldr, n) || cgb_bad_block(P_dev, ldp, n) ||
+        (AX_dev && ldax < n) || !state_dev || R_dev == P_dev || B_dev == R_dev || B_dev == P_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cgb_init: bad arguments (n=%d nvec=%d)", n, nvec);
+    double *part;
+    if (int rc = cgb_part(ctx, &part)) return rc;
+    hipLaunchKernelGGL((k_cgb_residual<true>), dim3(cgb_blocks(n)), dim3(CGB_THREADS), 0, ctx->stream, n, nvec, dinv_dev, B_dev, (long long)ldb,
+                       AX_dev, (long long)ldax, R_dev, (long long)ldr, P_dev, (long long)ldp, (const double*)state_dev, part+CGB_PART);
+    HIPCHK(ctx, hipGetLastError());
+    return cgb_finish(ctx, true, n, nvec, part+CGB_PART, tol, state_dev);
+}
+
+int pnl_cgb_update(pnl_context *ctx, int n, int nvec, const double *dinv_dev, const double *P_dev, int64_t ldp, const double *AP_dev, int64_t ldap,
+                   double *X_dev, int64_t ldx, double *R_dev, int64_t ldr, double *Z_dev, int64_t ldz, double *state_dev) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (n < 1 || nvec < 1 || nvec > CGB_NV || cgb_bad_block(P_dev, ldp, n) || cgb_bad_block(AP_dev, ldap, n) || cgb_bad_block(X_dev, ldx, n) ||
+        cgb_bad_block(R_dev, ldr, n) || cgb_bad_block(Z_dev, ldz, n) || !state_dev || X_dev == R_dev || X_dev == Z_dev || R_dev == Z_dev ||
+        P_dev == X_dev || P_dev == R_dev || P_dev == Z_dev || AP_dev == X_dev || AP_dev == R_dev || AP_dev == Z_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cgb_update: bad arguments (n=%d nvec=%d)", n, nvec);
+    double *part;
+    if (int rc = cgb_part(ctx, &part)) return rc;
+    const dim3 grid(cgb_blocks(n));
+    hipLaunchKernelGGL(k_cgb_pap, grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, P_dev, (long long)ldp, AP_dev, (long long)ldap,
+                       (const double*)state_dev, part);
+    hipLaunchKernelGGL(k_cgb_update, grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, dinv_dev, P_dev, (long long)ldp, AP_dev, (long long)ldap,
+                       X_dev, (long long)ldx, R_dev, (long long)ldr, Z_dev, (long long)ldz, state_dev, (const double*)part, part+CGB_PART);
+    HIPCHK(ctx, hipGetLastError());
+    return cgb_finish(ctx, false, n, nvec, part+CGB_PART, 0., state_dev);
+}
+
+int pnl_cgb_refresh(pnl_context *ctx, int n, int nvec, const double *dinv_dev, const double *B_dev, int64_t ldb, const double *AX_dev, int64_t ldax,
+                    double *R_dev, int64_t ldr, double *Z_dev, int64_t ldz, double *state_dev) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (n < 1 || nvec < 1 || nvec > CGB_NV || cgb_bad_block(B_dev, ldb, n) || cgb_bad_block(AX_dev, ldax, n) || cgb_bad_block(R_dev, ldr, n) ||
+        cgb_bad_block(Z_dev, ldz, n) || !state_dev || R_dev == Z_dev || B_dev == R_dev || B_dev == Z_dev || AX_dev == R_dev || AX_dev == Z_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cgb_refresh: bad arguments (n=%d nvec=%d)", n, nvec);
+    double *part;
+    if (int rc = cgb_part(ctx, &part)) return rc;
+    hipLaunchKernelGGL((k_cgb_residual<false>), dim3(cgb_blocks(n)), dim3(CGB_THREADS), 0, ctx->stream, n, nvec, dinv_dev, B_dev, (long long)ldb,
+                       AX_dev, (long long)ldax, R_dev, (long long)ldr, Z_dev, (long long)ldz, (const double*)state_dev, part+CGB_PART);
+    HIPCHK(ctx, hipGetLastError());
+    return cgb_finish(ctx, false, n, nvec, part+CGB_PART, 0., state_dev);
+}
+
+int pnl_cgb_direction(pnl_context *ctx, int n, int nvec, const double *Z_dev, int64_t ldz, double *P_dev, int64_t ldp, double tol, double *state_dev) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (n < 1 || nvec < 1 || nvec > CGB_NV || cgb_bad_block(Z_dev, ldz, n) || cgb_bad_block(P_dev, ldp, n) || !state_dev || Z_dev == P_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cgb_direction: bad arguments (n=%d nvec=%d)", n, nvec);
+    hipLaunchKernelGGL(k_cgb_direction, dim3(cgb_blocks(n)), dim3(CGB_THREADS), 0, ctx->stream, n, nvec, Z_dev, (long long)ldz, P_dev, (long long)ldp,
+                       tol, (const double*)state_dev);
+    hipLaunchKernelGGL(k_cgb_advance, dim3(1), dim3(64), 0, ctx->stream, nvec, tol, state_dev);
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+
+int pnl_cg_jacobi_block(pnl_context *ctx, const double *A_dev, int64_t ldA, int n, int nrhs, const double *B_dev, int64_t ldb, double *X_dev,
+                        int64_t ldx, double tol, int maxiter, int *iters, double *residuals) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (!A_dev || !B_dev || !X_dev || n < 1 || nrhs < 1 || ldA < n || ldb < n || ldx < n || maxiter < 0 || B_dev == X_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cg_jacobi_block: bad arguments (n=%d nrhs=%d ldA=%lld ldb=%lld ldx=%lld maxiter=%d)", n, nrhs,
+                    (long long)ldA, (long long)ldb, (long long)ldx, maxiter);
+    // work: dinv [n]; R, P, AP, Z [16][ld]; the state [16][PNL_CGB_STATE]
+    const int64_t ld = ((int64_t)n+1) & ~(int64_t)1;
+    const int gmax = std::min(nrhs, CGB_NV);
+    int rc;
+    if ((rc = ensure(ctx, ctx->b_cgb_work, sizeof(double)*(size_t)(ld+4*gmax*ld+CGB_NV*PNL_CGB_STATE)))) return rc;
+    double *dinv = (double*)ctx->b_cgb_work.p, *R = dinv+ld, *P = R+gmax*ld, *AP = P+gmax*ld, *Z = AP+gmax*ld, *state = Z+gmax*ld;
+    hipStream_t st = ctx->stream;
+    if ((rc = pnl_inv_diagonal(ctx, A_dev, ldA, n, dinv))) return rc;
+    double hs[CGB_NV*PNL_CGB_STATE];
+    for (int v0 = 0; v0 < nrhs; v0 += CGB_NV) {
+        const int nv = std::min(CGB_NV, nrhs-v0);
+        const double *B = B_dev+(int64_t)v0*ldb;
+        double *X = X_dev+(int64_t)v0*ldx;
+        auto product = [&](const double *V, int64_t ldv) { return pnl_gemv_block(ctx, A_dev, ldA, n, n, nv, V, ldv, 1., 0., nullptr, 0, AP, ld); };
+        bool active[CGB_NV];
+        int nactive = 0;
+        // the columns that are active on the host and no longer on the device have converged in pass `it`
+        auto read_state = [&](int it) -> int {
+            HIPCHK(ctx, hipMemcpyAsync(hs, state, sizeof(double)*nv*PNL_CGB_STATE, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            for (int v = 0; v < nv; v++) {
+                if (it >= 0 && !active[v]) continue;
+                if (residuals) residuals[v0+v] = hs[v*PNL_CGB_STATE+ST_CONV];
+                const bool on = hs[v*PNL_CGB_STATE+ST_ACTIVE] != 0.;
+                if (it < 0) { active[v] = on; nactive += on; if (iters) iters[v0+v] = 0; }
+                else if (!on) { active[v] = false; nactive--; if (iters) iters[v0+v] = it; }
+            }
+            return PNL_OK;
+        };
+        if ((rc = product(X, ldx))) return rc;
+        if ((rc = pnl_cgb_init(ctx, n, nv, dinv, B, ldb, AP, ld, R, ld, P, ld, tol, state))) return rc;
+        if ((rc = read_state(-1))) return rc;
+        int k = 0;
+        for (int it = 0; it < maxiter && nactive > 0; it++) {
+            if ((rc = product(P, ld))) return rc;
+            if ((rc = pnl_cgb_update(ctx, n, nv, dinv, P, ld, AP, ld, X, ldx, R, ld, Z, ld, state))) return rc;
+            if (k == 50) {
+                // recalculate the residual to limit rounding drift (solvers.pyx:412-415), for every active column of the group at once
+                if ((rc = product(X, ldx))) return rc;
+                if ((rc = pnl_cgb_refresh(ctx, n, nv, dinv, B, ldb, AP, ld, R, ld, Z, ld, state))) return rc;
+                k = 0;
+            }
+            if ((rc = pnl_cgb_direction(ctx, n, nv, Z, ld, P, ld, tol, state))) return rc;
+            if ((rc = read_state(it))) return rc;
+            k++;
+        }
+        for (int v = 0; v < nv; v++)
+            if (active[v] && iters) iters[v0+v] = maxiter;
+    }
+    return PNL_OK;
+}
+
+}  // extern "C"

@@ -184,6 +184,26 @@ class Dense_LinearOperator(blockProducts):
             return xd, its, res
         return xd.cpu().numpy(), its, res
 
+    def solve_cg_jacobi_block(self, B, X0=None, tol=1e-8, maxiter=1000):
+        """Jacobi-preconditioned CG for the rows of B [nrhs, n] at once (pnl_cg_jacobi_block): every row its own recurrence, one pass
+        over the block per iteration and 16 rows.  Returns (X, iterations[nrhs], residuals[nrhs] in the preconditioner norm); torch
+        in, torch out, else numpy.  The block is read in full (no half-read as ``solve_cg_jacobi``); no float atomics: the bits of a
+        row do not depend on the other rows."""
+        dev = self.A.device
+        assert self.num_rows == self.num_columns
+        Bd = _as_block(B, dev)
+        k = Bd.shape[0]
+        assert k >= 1 and Bd.shape[1] == self.num_rows, (tuple(Bd.shape), self.num_rows)
+        Xd = torch.zeros((k, self.num_rows), dtype=torch.float64, device=dev) if X0 is None else _as_block(X0, dev).clone(
+            memory_format=torch.contiguous_format)
+        assert Xd.shape == Bd.shape, (tuple(Xd.shape), tuple(Bd.shape))
+        torch.cuda.current_stream(dev).synchronize()
+        its, res = self.ctx.cg_jacobi_block(self.A.data_ptr(), max(int(self.A.stride(0)), self.num_rows), self.num_rows, k,
+                                            Bd.data_ptr(), max(int(Bd.stride(0)), self.num_rows), Xd.data_ptr(), self.num_rows, tol, maxiter)
+        if isinstance(B, torch.Tensor):
+            return Xd, its, res
+        return Xd.cpu().numpy(), its, res
+
     def solve_direct(self, b):
         """x with A x = b through the Cholesky factor (solvers.chol; a symmetric operator) or the pivoted LU factors (solvers.plu; any
         other square one) of a device copy of the block, computed on the first call and kept until invalidate() / refresh() or until

@@ -5,6 +5,8 @@ is whatever ``A.matvec`` does (GEMV, SpMV, H2 passes, all-reduce).
 residual norm sqrt(r.Br) as convergence criterion, the residual recomputed from scratch every 50 iterations, update order
 x, r, (refresh), Br, beta, p.  ``jacobi`` = the reference's jacobi_solver as a preconditioner (solvers.pyx:229-245).
 The dense operator additionally has this loop as one library call (pnl_cg_jacobi, Dense_LinearOperator.solve_cg_jacobi).
+``cg_multi`` is that loop for a 2-D block of right-hand sides: every row its own recurrence, the operator product shared
+(matvec_multi); the dense operator has it as one library call (pnl_cg_jacobi_block), the others run it over the library's steps.
 ``gmres`` follows gmres_solver.solve (solvers.pyx:504-659; the drivers' gmres-jacobi / gmres-mg for non-symmetric orders):
 left (default) or right preconditioner, modified Gram-Schmidt, Givens rotations, the rotated right-hand side as residual
 estimate, restarts; the Krylov basis stays in HBM, the small Hessenberg problem lives on the host.
@@ -23,7 +25,9 @@ def _dev_vector(v, device):
 
 def cg(A, b, x0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
     """Solve A x = b for a symmetric positive definite operator.  Returns (x, iterations, residuals); x is a torch tensor
-    on the operator's device if b is one, else a numpy array."""
+    on the operator's device if b is one, else a numpy array.  A 2-D b [nrhs, n] is a block of right-hand sides: ``cg_multi``."""
+    if getattr(b, 'ndim', None) == 2 or (not hasattr(b, 'ndim') and np.ndim(b) == 2):
+        return cg_multi(A, b, x0, tol, maxiter, preconditioner)
     import torch
     device = getattr(A, 'device', None)
     if device is None:
@@ -81,6 +85,105 @@ def cg(A, b, x0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
     if isinstance(b, _t.Tensor):
         return x, its, residuals
     return x.cpu().numpy(), its, residuals
+
+
+def _cg_group(A, ctx, dinv, B, X, have_x0, tol, maxiter, its, res):
+    """the loop of pnl_cg_jacobi_block (csrc/pnl_cg_block.hip) for at most 16 rows of B, with ``A.matvec_multi`` as the product and the
+    library's step calls on device blocks; X [nv, n] contiguous holds the guesses and the results, its / res are filled"""
+    import torch
+    from ._lib import PNL_CGB_STATE
+    nv, n = B.shape
+    dev = B.device
+    R, P, Z = (torch.empty((nv, n), dtype=torch.float64, device=dev) for _ in range(3))
+    state = torch.zeros(nv*PNL_CGB_STATE, dtype=torch.float64, device=dev)
+    dp = dinv.data_ptr() if dinv is not None else 0
+    ldb = max(int(B.stride(0)), n)
+
+    def product(V):
+        ctx.synchronize()
+        W = A.matvec_multi(V)
+        torch.cuda.current_stream(dev).synchronize()
+        return W
+
+    def read_state():
+        ctx.synchronize()
+        return state.cpu().numpy().reshape(nv, PNL_CGB_STATE)
+
+    AX = product(X) if have_x0 else None
+    torch.cuda.current_stream(dev).synchronize()
+    ctx.cgb_init(n, nv, dp, B.data_ptr(), ldb, AX.data_ptr() if AX is not None else 0, n, R.data_ptr(), n, P.data_ptr(), n, tol, state.data_ptr())
+    st = read_state()
+    res[:] = st[:, 3]
+    its[:] = 0
+    active = st[:, 4] != 0.
+    k = 0
+    for it in range(maxiter):
+        if not active.any():
+            break
+        AP = product(P)
+        ctx.cgb_update(n, nv, dp, P.data_ptr(), n, AP.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, Z.data_ptr(), n, state.data_ptr())
+        if k == 50:
+            AX = product(X)                             # recalculate the residual to avoid rounding errors
+            ctx.cgb_refresh(n, nv, dp, B.data_ptr(), ldb, AX.data_ptr(), n, R.data_ptr(), n, Z.data_ptr(), n, state.data_ptr())
+            k = 0
+        ctx.cgb_direction(n, nv, Z.data_ptr(), n, P.data_ptr(), n, tol, state.data_ptr())
+        st = read_state()
+        res[active] = st[active, 3]
+        done = active & (st[:, 4] == 0.)
+        its[done] = it
+        active &= ~done
+        k += 1
+    its[active] = maxiter
+
+
+def cg_multi(A, B, X0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
+    """Solve A X[v] = B[v] for the rows of a 2-D B [nrhs, n], A symmetric positive definite.  Every row runs the recurrence of ``cg``
+    on its own (own step lengths, own convergence test sqrt(r.Br) <= tol, frozen once it has converged) and the rows share the
+    operator product: one ``matvec_multi`` per iteration and 16 rows.  A symmetric Dense_LinearOperator on one GPU with the Jacobi
+    preconditioner is one library call (pnl_cg_jacobi_block); any other operator with ``matvec_multi`` and ``diagonal`` (CSR, SSS, H2,
+    interpolated) runs the same loop here over the library's step calls.  ``preconditioner``: 'jacobi' or None (the unit diagonal).
+    Returns (X, iterations[nrhs], residuals[nrhs]): the final sqrt(r.Br) of every row; X is a torch tensor on the operator's device if
+    B is one, else a numpy array."""
+    import torch
+    from ._lib import PNL_CGB_MAXVEC
+    from .linear_operators import Dense_LinearOperator, _as_block
+    if callable(preconditioner):
+        raise NotImplementedError('cg_multi: a callable preconditioner (multigrid) for a block of right-hand sides is not built')
+    if preconditioner not in ('jacobi', None):
+        raise NotImplementedError(preconditioner)
+    from .linear_operators import DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator
+    from .distributed_h2 import DistributedH2Matrix_localData
+    if isinstance(A, (DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator,
+                      DistributedH2Matrix_localData)):
+        raise NotImplementedError('cg_multi: the block products of the distributed operators loop their matvec; solve row by row with cg')
+    if not hasattr(A, 'matvec_multi'):
+        raise NotImplementedError('cg_multi needs an operator with matvec_multi; got {!r}'.format(A))
+    if isinstance(A, Dense_LinearOperator) and A.symmetric and preconditioner == 'jacobi':
+        return A.solve_cg_jacobi_block(B, X0, tol, maxiter)
+    if hasattr(A, 'assure_constructed'):
+        A.assure_constructed()
+    ctx = A.ctx if hasattr(A, 'ctx') else A.ops[0].ctx
+    device = getattr(A, 'device', None)
+    if device is None:
+        device = A.A.device if hasattr(A, 'A') else A._device()
+    Bd = _as_block(B, device)
+    nrhs, n = Bd.shape
+    assert nrhs >= 1 and n == A.num_rows == A.num_columns, (tuple(Bd.shape), A.shape)
+    X = torch.zeros((nrhs, n), dtype=torch.float64, device=device) if X0 is None else _as_block(X0, device).clone(
+        memory_format=torch.contiguous_format)
+    assert X.shape == Bd.shape, (tuple(X.shape), tuple(Bd.shape))
+    dinv = None
+    if preconditioner == 'jacobi':
+        d = A.diagonal
+        d = d() if callable(d) else d
+        dinv = 1./_dev_vector(d, device)
+    its, res = np.zeros(nrhs, dtype=np.int32), np.zeros(nrhs)
+    for v0 in range(0, nrhs, PNL_CGB_MAXVEC):
+        v1 = min(nrhs, v0+PNL_CGB_MAXVEC)
+        _cg_group(A, ctx, dinv, Bd[v0:v1], X[v0:v1], X0 is not None, tol, maxiter, its[v0:v1], res[v0:v1])
+    if isinstance(B, torch.Tensor):
+        return X, its, res
+    return X.cpu().numpy(), its, res
 
 
 def gmres(A, b, x0=None, tol=1e-8, maxiter=50, restarts=1, preconditioner=None, left=True):
