@@ -5,10 +5,12 @@ order; the matrices differ by the order of the LDS additions across waves only, 
 test_gpu_uniform_tiles_structured_and_generic_evaluators_agree bounds by 1e-13 max|A| for two summation orders of the same terms.
 The option PNL_MIXED_UNSETTLED makes the plan settle nothing.
 
-No test of settled tiles against the oracle: the plans of the disc at noRef 4 (1536 cells, the largest size of the oracle tests) and of
-the 12-sector fan at noRef 4 (3072 cells) settle no tile, noRef 5 (6144 cells) settles 1659, and the oracle takes 3.8 s at 3072 cells and
-four times that at 6144: too long for a test.  The
-classifying path is held to the oracle by the existing tests; the settled path is held to the classifying path here.
+Settled tiles against the oracle: the plans of the disc at noRef 4 (1536 cells, the largest size of the whole-matrix oracle tests) and
+of the 12-sector fan at noRef 4 (3072 cells) settle no tile, noRef 5 (6144 cells) settles 1659, and the whole oracle takes too long
+there.  tests/test_graded_tiles.py holds single entries of the production run at 6144 cells (graded discs, 2691 and 1629 settled
+tiles) to sums of the oracle's cell-pair contributions, more than 1000 sampled entries per case fed by a settled tile, each within
+its own relative bound (1e-12 for most), and the order histogram of that run to the oracle's formula over all cell pairs.  Here the
+settled path is held to the classifying path, matrix against matrix.
 """
 import os
 
