@@ -97,7 +97,7 @@ enum pnl_counter {
 #define PNL_NUM_COUNTERS 140
 
 /* Options (process-wide).  The library reads no environment variable on its assembly path; an option exists once it has been
- * set here (value NULL removes it).  A product build accepts
+ * set here (value NULL removes it).  The library accepts
  *   "PNL_WL_FRAC"     capacity of the device work lists as a fraction of the candidate pairs (tests force the overflow report),
  *   "PNL_FH_NOTILES"  finite horizon: every pair through the per-pair pipeline instead of the block tiles,
  *   "PNL_NO_POWTAB"   general exponent: exp(e ln x) instead of the table-driven power,
@@ -114,15 +114,14 @@ enum pnl_counter {
  *   "PNL_MIXED_GENERIC" mixed tiles: the evaluators for arbitrary rules also for the pairs whose rule has that orbit structure
  *                     (tests: both evaluators against each other),
  *   "PNL_MIXED_UNSETTLED" the tile plan settles no mixed tile: every mixed tile is classified pair by pair in every assembly
- *                     (tests: both paths against each other; read when the plan is made, changing it makes a new plan).  Tiles are
- *                     settled only where the plan computes exact order ranges: a tuning build's PNL_NO_EXACT_TILES settles nothing too,
+ *                     (tests: both paths against each other; read when the plan is made, changing it makes a new plan),
  *   "PNL_SETTLED_CODES" the tile plan keeps the pair codes of the settled tiles but not their pair lists: the tile kernel builds the lists
  *                     of a settled tile from its codes in every assembly (tests and A/B measurement; read when the plan is made,
  *                     changing it makes a new plan).  The plan does the same by itself where the device has no memory for the lists,
  *   "PNL_NO_OVERLAP", "PNL_NO_FORK"   profiling: no side streams, every phase on the caller's stream one after the other,
  *   "PNL_VERBOSE", "PNL_PLAN_TIMING"   diagnostics on stderr,
- * and returns PNL_ERR_UNSUPPORTED for any other name.  A tuning build (make EXTRA=-DPNL_TUNING; pnl_version says so) accepts every
- * name and falls back to the environment: the A/B switches named in DESIGN.md live there. */
+ * and returns PNL_ERR_UNSUPPORTED for any other name: these are all the run-time switches there are.  The A/B switches of the
+ * measurements in docs/CHANGELOG_kernels.md were resolved to the side that won; no build of the library reads them. */
 int pnl_set_option(const char *name, const char *value);
 
 /* Test hook (tests/test_device_math.py): the device functions of the kernel values and of the quadrature order, evaluated on

@@ -397,16 +397,11 @@ __device__ __forceinline__ int quad_order_fast(const DevFormula &F, double h1, d
 }
 
 // stores into the block-slot storage (written once by the tile kernels, read once by the fold pass) and of the fold pass into A
-#ifndef PNL_SLOT_NT
-#define PNL_SLOT_NT 0
-#endif
-__device__ __forceinline__ void slot_store(double *p, double v) {
-    if (PNL_SLOT_NT) __builtin_nontemporal_store(v, p); else *p = v;
-}
+__device__ __forceinline__ void slot_store(double *p, double v) { *p = v; }
 __device__ __forceinline__ void slot_store2(double *p, double x, double y) {
     typedef double pnl_d2 __attribute__((ext_vector_type(2)));
     const pnl_d2 v = {x, y};
-    if (PNL_SLOT_NT) __builtin_nontemporal_store(v, (pnl_d2*)p); else *(pnl_d2*)p = v;
+    *(pnl_d2*)p = v;
 }
 
 // workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every global atomic / store of the wave
@@ -530,12 +525,8 @@ struct PairAcc {
 // the caller pads the rule copy to n4 = a multiple of four points with ZERO-WEIGHT copies of point 0 (finite kernel values that
 // enter nothing).  Work per point pair for P2: 14 + kernel value + about 5 amortised, against 56 + kernel value.
 // POWTAB: fractional kernel with the LDS power tables and no horizon -- no branch per evaluation.
-#ifndef PNL_WL_JB
-#define PNL_WL_JB 16        // columns per block (column sums in registers)
-#endif
-#ifndef PNL_WL_JG
-#define PNL_WL_JG 4         // columns per guarded group (1, 2 or 4: the rule copy is padded to a multiple of four points)
-#endif
+constexpr int PNL_WL_JB = 16;       // columns per block (column sums in registers)
+constexpr int PNL_WL_JG = 4;        // columns per guarded group (the rule copy is padded to a multiple of four points)
 // CM: where the column sums of a finished block go.  0: straight into S2 (the accumulators of S2 are live in the hot loop: fine for
 // P1).  P2 carries 78 accumulators per lane, more than the hot loop leaves room for in 256 VGPRs, and the register allocator then
 // serialises every LDS read of the loop behind a wait (measured: issue utilisation 0.14); so the column sums leave through LDS and

@@ -201,7 +201,6 @@ struct pnl_context {
     std::vector<pnl_order_formula> tiles_forms;
     pnl_order_formula tiles_form;
     bool tiles_filter = true;
-    bool use_pure = true;             // debug: PNL_PURE=0 sends every tile through the general kernel
     // tables of the general power (pnl_pow_tab, pnl_common.h), one per (exponent, scale) seen by this context
     struct PowTab { double exponent, scale; DevBuf buf; };
     std::vector<PowTab*> powtabs;
@@ -216,8 +215,6 @@ struct pnl_context {
     // order classes) takes one more pair per launch, created on first use and kept; AssemblyRun::kev_n counts the launches
     std::vector<hipEvent_t> kev[PNL_NUM_KERNEL_SLOTS];
     AssemblyRun run;                // the assembly in progress or, behind it, the last one (pnl_begin_assembly)
-    int ablate = 0;                 // debug: PNL_ABLATE env bits (1 no LDS accumulate, 2 no evaluation)
-    bool wl_lane = true;            // debug: PNL_WL_LANE=0 sends every work-list order to the 16-lanes-per-pair kernel
 };
 
 // once per C-ABI assembly call, where its arguments have been checked and before anything of the run is set
@@ -318,10 +315,10 @@ inline DevFormula to_dev(const pnl_order_formula &f) {
     return d;
 }
 
-// Options of the library.  The product build reads NO environment variable on the assembly path: an option exists only after
-// pnl_set_option(name, value) named it (include/pnl_hip.h lists the options a product build accepts -- the hooks the parity
-// tests use to reach the alternative code paths).  Tuning builds (make EXTRA=-DPNL_TUNING) accept every name and fall back to the
-// environment, which is how the A/B measurements of DESIGN.md were made.  Returns the value string or nullptr.
+// Options of the library.  It reads NO environment variable on the assembly path: an option exists only after
+// pnl_set_option(name, value) named it, and pnl_set_option accepts the names of k_product_options (pnl_setup.hip; listed in
+// include/pnl_hip.h) only -- the hooks the parity tests use to reach the alternative code paths, and the diagnostics.  Call it with
+// a literal name: tests/test_abi.py holds the call sites against that table.  Returns the value string or nullptr.
 const char *pnl_tune(const char *name);
 // grid of a persistent tile kernel, capped by the option PNL_TILE_WGS (tests)
 inline int pnl_grid_cap(int grid) {
@@ -330,19 +327,15 @@ inline int pnl_grid_cap(int grid) {
     return cap > 0 ? std::max(1, std::min(grid, cap)) : grid;
 }
 
-// row stride of the LDS sub-block: nU + 1 columns (+1: trash column / row for boundary DoFs); PNL_ACC_PAD=m rounds it up
-// to 1 mod m so that consecutive rows start in different LDS banks
+// row stride of the LDS sub-block: nU + 1 columns (+1: trash column / row for boundary DoFs), rounded up to 1 mod 32 doubles:
+// rows that start in different LDS banks see fewer conflicts in the ds_add_f64 of the cross blocks (measured: -0.4 ms at
+// noRef 6), if the bigger sub-block still leaves two workgroups per CU
 inline int acc_stride_of(int nU, size_t fixed_bytes = 0) {
-    int st = nU+1;
-    // rows that start in different LDS banks (stride = 1 mod 32 doubles) see fewer conflicts in the ds_add_f64 of the
-    // cross blocks (measured: -0.4 ms at noRef 6), if the bigger sub-block still leaves two workgroups per CU
-    const int m = pnl_tune("PNL_ACC_PAD") ? atoi(pnl_tune("PNL_ACC_PAD")) : 32;
-    if (m > 1) {
-        int padded = st;
-        while (padded % m != 1) padded++;
-        if (fixed_bytes+sizeof(double)*(size_t)(nU+1)*padded <= 80*1024) st = padded;
-        else if (st % 2 == 0 && fixed_bytes+sizeof(double)*(size_t)(nU+1)*(st+1) <= 80*1024) st++;    // at least an odd stride
-    }
+    constexpr int m = 32;
+    int st = nU+1, padded = st;
+    while (padded % m != 1) padded++;
+    if (fixed_bytes+sizeof(double)*(size_t)(nU+1)*padded <= 80*1024) st = padded;
+    else if (st % 2 == 0 && fixed_bytes+sizeof(double)*(size_t)(nU+1)*(st+1) <= 80*1024) st++;    // at least an odd stride
     return st;
 }
 

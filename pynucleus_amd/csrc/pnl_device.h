@@ -102,9 +102,7 @@ struct DevProblem {
 // cell j = tid % tile of block b and visits in its k-th sweep the row r of the wrapped diagonals, pair p = r tile + j, whose cell of
 // block a is i = (r + PNL_DIAG_MULT j) mod tile.  The pair codes of a settled tile (pnl_context::b_codes) follow from it: 2 bits per pair,
 // the pair of sweep k in bits 2 k, 2 k + 1 of the 16-bit word codes[tile index][tid] (64 x 64 pairs, 512 threads: 8 sweeps)
-#ifndef PNL_DIAG_MULT
-#define PNL_DIAG_MULT 21
-#endif
+constexpr int PNL_DIAG_MULT = 21;
 // The pair lists of a settled tile (pnl_context::b_lists), one record of PNL_LIST_STRIDE 16-bit words per tile: words 0 .. 2 the
 // numbers n4, n3, n2 of pairs of order 4, 3, 2, then from word PNL_LIST_HEAD on the n4 + n3 + n2 <= 4096 entries p | (q - 2) << 12, the
 // pairs of order 4 first, then order 3, then order 2 -- the order in which the chunk queue of the tile kernel evaluates them --, ascending

@@ -66,14 +66,10 @@ int launch_pure(pnl_context *ctx, double *A, int64_t ldA, const SlotOut &SO) {
     if (g.rc) return g.rc;
     if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] uniform tiles=%d of %d, lds=%zu bytes, occupancy API: %d blocks/CU\n", ctx->run.n_pure,
                                        ctx->run.n_pure+ctx->run.n_mixed, lds, g.per_cu);
-    int pure_abl = 0;
-#ifdef PNL_DEBUG_ABLATE
-    pure_abl = pnl_tune("PNL_PURE_ABL") ? atoi(pnl_tune("PNL_PURE_ABL")) : 0;
-#endif
     kt_begin(ctx, PNL_K_TILE_UNIFORM2);
     hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(PNL_NTHREADS), lds, ctx->stream, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->run.tile_off+ctx->run.n_mixed,
                        ctx->run.n_pure, A, (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), acc_stride, 2,
-                       (ctx->run.symflush ? 1 : 0) | pure_abl, SO);
+                       ctx->run.symflush ? 1 : 0, SO);
     kt_end(ctx, PNL_K_TILE_UNIFORM2);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
@@ -139,13 +135,7 @@ int run_worklist(pnl_context *ctx, const int4 *wl, const unsigned *wlc, unsigned
     const int4 *wlsorted = (const int4*)ctx->b_wlsorted.p+(size_t)region*cap;
     WlBins B;
     if ((rc = pnl_wl_sort(ctx, wl, wlc, cap, (unsigned*)ctx->b_wlaux.p+(size_t)region*4*(PNL_WL_BINS+1), (int4*)wlsorted, B))) return rc;
-    int dbg = 0;
-#ifdef PNL_DEBUG_ABLATE
-    dbg = pnl_tune("PNL_WL_DBG") ? atoi(pnl_tune("PNL_WL_DBG")) : 0;
-#endif
-    const int nmin = ctx->wl_lane ? PNL_WL_LANE_MAXPTS+1 : 0;
-    return worklist_eval<DIM, DPE, KT, false>(ctx, "PNL_WL_LDS_KB", 18, wlsorted, B, A, ldA, (double*)ctx->b_D.p, SparseOut{}, ClusterTiles{},
-                                              PNL_WL_BINS-1, nmin | (sym ? 1 << 16 : 0), ctx->wl_lane, dbg | (sym ? 8 : 0));
+    return worklist_eval<DIM, DPE, KT, false>(ctx, WL_RULE_KB, wlsorted, B, A, ldA, (double*)ctx->b_D.p, SparseOut{}, ClusterTiles{}, PNL_WL_BINS-1, sym);
 }
 
 // work list for the orders that are integrated one pair per wave: `regions` regions of equal capacity, sized generously;
@@ -204,8 +194,7 @@ int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, 
             ctx->run.lists_run = ns;
         }
     }
-    const int grid_mult = pnl_tune("PNL_GRID_MULT") ? atoi(pnl_tune("PNL_GRID_MULT")) : 1;
-    const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT), lds, ntiles, 2, grid_mult);
+    const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE), lds, ntiles, 2);
     if (g.rc) return g.rc;
     if (pnl_tune("PNL_VERBOSE"))
         fprintf(stderr, "[pnl] %stiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", SETTLED ? "settled " : "", ntiles, ctx->nU, lds, g.per_cu);
@@ -215,10 +204,10 @@ int launch_mixed_tiles(pnl_context *ctx, unsigned *wlc, double *A, int64_t ldA, 
     kt_begin(ctx, PNL_K_TILE_GENERAL);
     if (SETTLED) kt_begin(ctx, PNL_K_TILE_SETTLED);
     if (g.grid > 0)
-        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)),
+        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE)), lds, ctx->stream, with_mixed_rules(ctx, tile_problem(ctx)),
                            (const int2*)ctx->b_tiles.p+ctx->run.tile_off+first, A,
                            (long long)ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), cell_begin, cell_end, acc_stride, (int4*)ctx->b_wl.p,
-                           wlc, ctx->wl_cap_each, ctx->ablate | (ctx->run.symflush ? 256 : 0), ntiles, ClusterTiles{},
+                           wlc, ctx->wl_cap_each, ctx->run.symflush ? 256 : 0, ntiles, ClusterTiles{},
                            ctr, SOk, codes);
     if (SETTLED) kt_end(ctx, PNL_K_TILE_SETTLED);
     kt_end(ctx, PNL_K_TILE_GENERAL);
@@ -236,8 +225,8 @@ int launch_tiles(pnl_context *ctx, int wl_slot, double *A, int64_t ldA, int cell
     if (TILE == 64 && DPE <= 3) {
         int rc;
         // order-2 uniform tiles: 2D P1 the pipelined k_tile_uniform<3, 3> (with three or four workgroups per CU it beats k_tile_pure:
-        // 41.3 against 45.5 ms at 98,304 cells, s = 1/2; PNL_PURE_V1=1 keeps k_tile_pure), 1D k_tile_pure
-        if (DIM == 2 && DPE == 3 && !pnl_tune("PNL_PURE_V1") && ctx->uni_off[2] >= 0 && ctx->uni_np[2] == 3)
+        // 41.3 against 45.5 ms at 98,304 cells, s = 1/2), where the order-2 rule has its three points; else and in 1D k_tile_pure
+        if (DIM == 2 && DPE == 3 && ctx->uni_off[2] >= 0 && ctx->uni_np[2] == 3)
             rc = pnl2_launch_uniform(ctx, KT, tile_problem(ctx), (const int2*)ctx->b_tiles.p+ctx->run.tile_off+ctx->run.n_mixed, nullptr, ctx->run.n_pure, 2,
                                      A, ldA, (double*)(ctx->have_tile_order ? ctx->b_Dt.p : ctx->b_D.p), SO);
         else rc = launch_pure<DIM, (DPE <= 3 ? DPE : 3), KT>(ctx, A, ldA, SO);
@@ -296,24 +285,20 @@ int launch_boundary(pnl_context *ctx, int cell_begin, int cell_end, int what = 3
     // small facet chunks: many waves in flight hide the latency of the per-facet dependent chain
     // a rank's share of the cells may be small: shrink the facet chunks until the grid has a few thousand workgroups
     // (measured at 98,304 cells x 768 facets: 16 per chunk 5.4 ms, 32 per chunk 4.5 ms, 64 the same; 8: 6.9 ms, 1: 33.6 ms)
-    int per = pnl_tune("PNL_BND_PER") ? atoi(pnl_tune("PNL_BND_PER")) : 32;
+    int per = 32;
     while (per > 1 && (long long)gx*((ctx->nb+per-1)/per) < 4096) per >>= 1;
     const int chunks = (ctx->nb+per-1)/per;
     if (what & 1) {
         // pairs with more than `defer` point pairs are integrated one per wave (k_boundary_items) instead of by one lane; the
         // list holds at least 64 items per facet -- pairs that do not fit are integrated in place
-        const int defer = pnl_tune("PNL_BND_DEFER") ? atoi(pnl_tune("PNL_BND_DEFER")) : 48;
-        const bool use_list = defer > 0;
+        constexpr int defer = 48;
         const unsigned cap = (unsigned)std::min<long long>(std::max<long long>(65536, 64ll*ctx->nb), 1ll << 24);
-        int *dcells = nullptr, *dfacets = nullptr, *dcls = nullptr;
-        unsigned *dslots = nullptr, *dcount = nullptr;
-        if (use_list) {
-            int rc;
-            if ((rc = ensure(ctx, ctx->b_bdefer, sizeof(int)*(size_t)cap*(3+DIM)+sizeof(unsigned)))) return rc;
-            dcells = (int*)ctx->b_bdefer.p; dfacets = dcells+cap; dslots = (unsigned*)(dfacets+(size_t)cap*DIM); dcls = (int*)(dslots+cap);
-            dcount = (unsigned*)(dcls+cap);
-            HIPCHK(ctx, hipMemsetAsync(dcount, 0, sizeof(unsigned), ctx->stream));
-        }
+        if (int rc = ensure(ctx, ctx->b_bdefer, sizeof(int)*(size_t)cap*(3+DIM)+sizeof(unsigned))) return rc;
+        int *dcells = (int*)ctx->b_bdefer.p, *dfacets = dcells+cap;
+        unsigned *dslots = (unsigned*)(dfacets+(size_t)cap*DIM);
+        int *dcls = (int*)(dslots+cap);
+        unsigned *dcount = (unsigned*)(dcls+cap);
+        HIPCHK(ctx, hipMemsetAsync(dcount, 0, sizeof(unsigned), ctx->stream));
         const bool fast = bkcls ? all_fast : (ctx->P.bkn.fast != 0);
         bool tiled = false;
         if constexpr (DIM == 2) {
@@ -327,7 +312,7 @@ int launch_boundary(pnl_context *ctx, int cell_begin, int cell_end, int what = 3
                 if (lds <= 64*1024) {
                     // facet blocks: enough workgroups to fill the chip (a rank's share of the cells may be small), whole chunks of 64
                     const int nfb = (ctx->nb+PNL_BT_FB-1)/PNL_BT_FB;
-                    const int want = pnl_tune("PNL_BT_WG") ? atoi(pnl_tune("PNL_BT_WG")) : 2048;
+                    constexpr int want = 2048;
                     const int gy = std::max(1, std::min(nfb, (want+gx-1)/gx));
                     const int per_block = ((nfb+gy-1)/gy)*PNL_BT_FB;
                     const int gyy = (ctx->nb+per_block-1)/per_block;
@@ -347,7 +332,7 @@ int launch_boundary(pnl_context *ctx, int cell_begin, int cell_end, int what = 3
                                (double*)ctx->b_D.p, cell_begin, cell_end, per, bkcls, bfcls, defer, dcells, dfacets, dslots, dcount, cap, dcls);
             return PNL_OK;
         });
-        if (use_list) with_kt(fast, [&](auto kt) {
+        with_kt(fast, [&](auto kt) {
             hipLaunchKernelGGL((k_boundary_items<DIM, DPE, decltype(kt)::value>), dim3(256*4), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P,
                                (const double*)ctx->b_vertices.p, (const int*)dcells, (const int*)dfacets, (const unsigned*)dslots, (int)cap, 1.,
                                SparseOut{}, (double*)ctx->b_D.p, (const unsigned*)dcount, bkcls ? (const int*)dcls : nullptr, bkcls, bfcls);
@@ -376,7 +361,7 @@ int launch_boundary(pnl_context *ctx, int cell_begin, int cell_end, int what = 3
 
 // block-slot storage of the one-sided operator (pnl_tile2.h): allocated when the device has room for it next to the caller's matrix
 bool slot_storage_ready(pnl_context *ctx) {
-    if (ctx->nonsym || pnl_tune("PNL_NO_SLOT")) return false;
+    if (ctx->nonsym) return false;
     size_t free_b = 0, total_b = 0;
     const size_t need = sizeof(double)*(size_t)ctx->slot_total;
     if (ctx->b_slotA.bytes >= need) return true;
@@ -401,7 +386,7 @@ int launch_tiles_single(pnl_context *ctx, double *A, int64_t ldA, int cell_begin
         all_fast = all_fast && ctx->P.k.fast;
         all_half = all_half && ctx->P.k.fast && ctx->P.k.qm == 6;
     }
-    const int kt = (all_half && !pnl_tune("PNL_NO_KT2")) ? 2 : (all_fast ? 1 : 0);
+    const int kt = all_half ? 2 : (all_fast ? 1 : 0);
     if (kt == 0)
         // three layers with s = 0.3 .. 0.7: the class s = 1/2 (half of the pairs) is a "fast" kernel without tables of its own
         for (int k = 0; k < ncls; k++)
@@ -459,7 +444,7 @@ int launch_tiles_single(pnl_context *ctx, double *A, int64_t ldA, int cell_begin
 // the whole upper block triangle is assembled by this call (full_list: the tile list is that of pnl_assemble_dense) and mirrored afterwards
 bool slot_eligible(const pnl_context *ctx, bool full_list, int cell_begin, int cell_end, int flags) {
     // P2: every tile list (several order classes: multi-visit tiles accumulate); P1: one class, every tile visited by one kernel
-    const bool elem = ctx->dpe == 6 || (ctx->dpe == 3 && ctx->cls.size() == 1 && !ctx->nonsym && ctx->use_pure && !pnl_tune("PNL_NO_SLOT_P1"));
+    const bool elem = ctx->dpe == 6 || (ctx->dpe == 3 && ctx->cls.size() == 1 && !ctx->nonsym);
     return ctx->dim == 2 && elem && full_list && ctx->slab_rows == 0 && cell_begin == 0 && cell_end == ctx->nc &&
            !(flags & (PNL_FLAG_NO_MIRROR | PNL_FLAG_SYMMETRIC_FLUSH));
 }
@@ -483,7 +468,7 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
     // variable order, zero exterior: the distant (cell, facet) pairs of ALL classes run in one launch with per-class kernel /
     // order-formula tables; the tables go up now, ahead of the tile kernels, so that the launch needs nothing from the
     // caller's stream later than the fold
-    const bool bnd_one_pass = zero_exterior && ncls > 1 && ctx->nlab > 0 && !pnl_tune("PNL_BND_PER_CLASS");
+    const bool bnd_one_pass = zero_exterior && ncls > 1 && ctx->nlab > 0;
     bool bnd_all_fast = true;
     if (bnd_one_pass) {
         std::vector<DevKernel> &bk = ctx->bkcls_host;
@@ -565,7 +550,7 @@ int assemble_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, i
             if (ctx->run.n_mixed+ctx->run.n_pure+ctx->cls_n_uni[1][k]+ctx->cls_n_uni[2][k] == 0) continue;
             const int tb0 = ctx->run.tile_cell_filter ? cell_begin : 0, tb1 = ctx->run.tile_cell_filter ? cell_end : ctx->nc;
             // s = 1/2 in 2D (exponent -6/4) has its own instantiation: branch-free evaluations
-            if (ctx->P.k.fast && ctx->P.k.qm == 6 && DPE == 3 && !pnl_tune("PNL_NO_KT2")) rc = launch_tiles<DIM, DPE, TILE, (DPE == 3 ? 2 : 1)>(ctx, ko, A, ldA, tb0, tb1, SO);
+            if (ctx->P.k.fast && ctx->P.k.qm == 6 && DPE == 3) rc = launch_tiles<DIM, DPE, TILE, (DPE == 3 ? 2 : 1)>(ctx, ko, A, ldA, tb0, tb1, SO);
             else rc = with_kt(ctx->P.k.fast, [&](auto kt) { return launch_tiles<DIM, DPE, TILE, decltype(kt)::value>(ctx, ko, A, ldA, tb0, tb1, SO); });
             if (rc) return rc;
         }
@@ -680,11 +665,11 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
     }
     if (pl->ntiles > 0) {
         auto kfun = k_tile_distant<DIM, DPE, TILE, KT, true>;
-        const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT), lds, pl->ntiles, 2);
+        const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE), lds, pl->ntiles, 2);
         if (g.rc) return g.rc;
         if (pnl_tune("PNL_VERBOSE")) fprintf(stderr, "[pnl] cluster tiles=%d nU=%d lds=%zu bytes, occupancy API: %d blocks/CU\n", pl->ntiles,
                                            pl->chunk_stride, lds, g.per_cu);
-        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT)), lds, ctx->stream, with_mixed_rules(ctx, ctx->P), (const int2*)nullptr, (double*)nullptr, 0ll,
+        hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE)), lds, ctx->stream, with_mixed_rules(ctx, ctx->P), (const int2*)nullptr, (double*)nullptr, 0ll,
                            (double*)nullptr, 0, ctx->nc, acc_stride, (int4*)ctx->b_wl.p, (unsigned*)ctx->b_wlcount.p, ctx->wl_cap, 0,
                            pl->ntiles, CT, (unsigned*)ctx->b_tilectr.p, SlotOut{}, (const unsigned short*)nullptr);
         HIPCHK(ctx, hipGetLastError());
@@ -707,9 +692,8 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
         WlBins B;
         if ((rc = pnl_wl_sort(ctx, (const int4*)ctx->b_wl.p, (const unsigned*)ctx->b_wlcount.p, ctx->wl_cap, (unsigned*)ctx->b_wlaux.p,
                           (int4*)ctx->b_wlsorted.p, B))) return rc;
-        // the lane kernel whatever the option PNL_WL_LANE says, and with it nmin: a difference from the other two paths that is kept, not decided
-        if ((rc = worklist_eval<DIM, DPE, KT, false>(ctx, "PNL_WL_CL_KB", 18, (const int4*)ctx->b_wlsorted.p, B, nullptr, 0, nullptr, SparseOut{},
-                                                     CT, PNL_WL_BINS-1, PNL_WL_LANE_MAXPTS+1, true, 0))) return rc;
+        if ((rc = worklist_eval<DIM, DPE, KT, false>(ctx, WL_RULE_KB, (const int4*)ctx->b_wlsorted.p, B, nullptr, 0, nullptr, SparseOut{},
+                                                     CT, PNL_WL_BINS-1, false))) return rc;
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[EV_WORKLIST_DONE], ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[EV_MIRROR_DONE], ctx->stream));
@@ -737,21 +721,18 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
         // few cells (those of cellsInter), many facets each: small facet chunks give the parallelism
         // (measured at C4, 9.9e6 pairs / 5.0e8 point pairs: all in place 9.0 ms; list for > 48 point pairs 4.7 ms, > 200: 4.1 ms,
         // > 200 with 4 facets per chunk 3.2 ms, > 1000: 5.4 ms)
-        const int per = pnl_tune("PNL_CB_PER") ? atoi(pnl_tune("PNL_CB_PER")) : 4;
+        constexpr int per = 4;
         const dim3 grid((pl->num_dslots+PNL_NTHREADS-1)/PNL_NTHREADS, (maxf+per-1)/per);
         const double *verts = (const double*)ctx->b_vertices.p;
         // (cell, facet) pairs with more than `defer` point pairs: list of items for k_boundary_items (one per wave); pairs that do
         // not fit into the list are integrated in place
-        const int defer = pnl_tune("PNL_CB_DEFER") ? atoi(pnl_tune("PNL_CB_DEFER")) : 200;
-        const unsigned cap = defer > 0 ? 1u << 22 : 0u;
-        int *dcells = nullptr, *dfacets = nullptr;
-        unsigned *dslots = nullptr, *dcount = nullptr;
-        if (cap) {
-            if ((rc = ensure(ctx, ctx->b_bdefer, sizeof(int)*(size_t)cap*(3+DIM)+sizeof(unsigned)))) return rc;
-            dcells = (int*)ctx->b_bdefer.p; dfacets = dcells+cap; dslots = (unsigned*)(dfacets+(size_t)cap*DIM);
-            dcount = (unsigned*)((int*)(dslots+cap)+cap);
-            HIPCHK(ctx, hipMemsetAsync(dcount, 0, sizeof(unsigned), ctx->stream));
-        }
+        constexpr int defer = 200;
+        constexpr unsigned cap = 1u << 22;
+        if ((rc = ensure(ctx, ctx->b_bdefer, sizeof(int)*(size_t)cap*(3+DIM)+sizeof(unsigned)))) return rc;
+        int *dcells = (int*)ctx->b_bdefer.p, *dfacets = dcells+cap;
+        unsigned *dslots = (unsigned*)(dfacets+(size_t)cap*DIM);
+        unsigned *dcount = (unsigned*)((int*)(dslots+cap)+cap);
+        HIPCHK(ctx, hipMemsetAsync(dcount, 0, sizeof(unsigned), ctx->stream));
         // items of k_boundary_items, one per wave: the deferred pairs (count on the device) and the touching (cell, facet) pairs
         auto items = [&](auto kt, int g, const int *cells, const int *facets, const unsigned *slots, int n, const unsigned *count) {
             hipLaunchKernelGGL((k_boundary_items<DIM, DPE, decltype(kt)::value>), dim3(g), dim3(PNL_NTHREADS), 0, ctx->stream, ctx->P, verts, cells,
@@ -763,10 +744,8 @@ int clusters_tiled_impl(pnl_context *ctx, const pnl_cluster_plan *pl, ClusterTil
             return PNL_OK;
         });
         HIPCHK(ctx, hipGetLastError());
-        if (cap) {
-            with_kt(ctx->P.bkn.fast, [&](auto kt) { items(kt, 256*8, dcells, dfacets, dslots, (int)cap, dcount); return PNL_OK; });
-            HIPCHK(ctx, hipGetLastError());
-        }
+        with_kt(ctx->P.bkn.fast, [&](auto kt) { items(kt, 256*8, dcells, dfacets, dslots, (int)cap, dcount); return PNL_OK; });
+        HIPCHK(ctx, hipGetLastError());
         if (pl->n_btouch > 0) {
             for (int s = 0; s < DIM; s++)
                 if (!ctx->C().have_sing[1][s]) return fail(ctx, PNL_ERR_STATE, "boundary singular rule for %d common vertices not uploaded", s+1);
@@ -992,7 +971,6 @@ int pnl_assemble_dense(pnl_context *ctx, double *A, int64_t ldA, int zero_exteri
     // pairs visited by the reference loop: c1 in [begin,end), c2 in [c1, nc)
     for (long long c = cell_begin; c < cell_end; c++)
         if (ctx->real_from[c] != ctx->real_from[c+1]) ctx->run.visited_pairs += (unsigned long long)ctx->real_from[c];      // zero-volume padding cells do not count
-    if (pnl_tune("PNL_FORCE_SYMFLUSH")) flags |= PNL_FLAG_SYMMETRIC_FLUSH;     // debug: both sides written by the flush, no mirror pass
     return dispatch(ctx, A, ldA, zero_exterior, (int)tiles.size(), cell_begin, cell_end, flags);
 }
 
@@ -1000,7 +978,6 @@ int pnl_dense_overwrites(pnl_context *ctx, int cell_begin, int cell_end, int fla
     if (!ctx) return PNL_ERR_INVALID;
     int rc;
     if ((rc = pnl_assembly_ready(ctx))) return rc;
-    if (pnl_tune("PNL_FORCE_SYMFLUSH")) return 0;
     return slot_eligible(ctx, true, cell_begin, cell_end, flags) && slot_storage_ready(ctx) ? 1 : 0;      // true: what pnl_assemble_dense sets
 }
 

@@ -456,9 +456,6 @@ __device__ __forceinline__ bool pair_has(const ClusterTiles &CT, int k, int I, i
 // atomics per pair: 3.8 ms of which 2.5 ms are the atomics.)  Only higher orders go to the global work list.
 // lanes walk the tile along generalised diagonals i = (s + m*j) mod TILE (m odd): distinct a- and b-cells per lane, and
 // neighbouring b-cells are paired with non-neighbouring a-cells, which keeps same-address LDS atomics rare
-#ifndef PNL_DIAG_MULT
-#define PNL_DIAG_MULT 21
-#endif
 template <int DIM, int DPE, int TILE, bool POW = false>
 struct TileSmem {
     static constexpr int NV = DIM+1, NC = NV*DIM, ND = DPE*(DPE+1)/2;
@@ -516,15 +513,9 @@ __device__ __forceinline__ int wave_bucket_add(int *counters, int q, bool fetch)
 
 // number of points of a distant rule the tile kernel integrates one pair per lane (fully unrolled);
 // every other order goes to the global work list and is integrated one pair per wave.
-#ifdef PNL_ONLY_N3
-__device__ __forceinline__ bool tile_eligible(int n) { return n == 3; }
-#else
 __device__ __forceinline__ bool tile_eligible(int n) { return n == 2 || n == 3 || n == 4 || n == 6 || n == 7; }
-#endif
 
-#ifndef PNL_PURE_WAVES
-#define PNL_PURE_WAVES 4
-#endif
+constexpr int PNL_PURE_WAVES = 4;       // waves per SIMD k_tile_pure is register-limited to
 // finite horizon (defined further down): relative position of two simplices, sorted-list keys of cut pairs
 #define PNL_CUT_SHIFT 60        // sorted-list bin of a cut pair = order + PNL_CUT_SHIFT (orders <= 60)
 #define PNL_INTERACT 0
@@ -546,7 +537,7 @@ __device__ __forceinline__ unsigned eval_distant_cut(const DevProblem &P, const 
 template <int DIM, int TILE, class Between>
 __device__ __forceinline__ int tile_pair_order(const DevFormula &qo, bool sel, int2 cfa, int2 cfb, const double *s_cen, const double (&cenb)[DIM],
                                                const int *s_vid, const float *s_lh, float lhb, float Llb, const double *s_h, const double *s_Ld,
-                                               int i, int j, bool order2, Between &&between) {
+                                               int i, int j, Between &&between) {
     constexpr int NV = DIM+1;
     if (!((cfa.x & cfb.x & 1) && sel)) return 0;
     const bool any_dof = ((cfa.x | cfb.x) & 2) != 0;
@@ -567,7 +558,6 @@ __device__ __forceinline__ int tile_pair_order(const DevFormula &qo, bool sel, i
         }
     }
     if (!between(any_dof, shared) || !any_dof || shared) return 0;
-    if (order2) return 2;
     int q = quad_order_try(qo, s_lh[i], lhb, s_lh[TILE+i], Llb, d2);
     if (q < 0) q = quad_order_exact(qo, s_h[i], s_h[TILE+j], s_Ld[i], s_Ld[TILE+j], sqrt(d2));
     return q;
@@ -577,24 +567,14 @@ __device__ __forceinline__ int tile_pair_order(const DevFormula &qo, bool sel, i
 // workgroup size: 512 threads at <= 128 VGPRs give 4 waves per SIMD (the unrolled 6-point evaluator stays spill-free because
 // its loop-invariant rule constants live in SGPRs); measured at noRef 7: 256 x 2 waves 69.7 ms, 384 x 3 101.6 ms (spills in
 // the hot loop), 512 x 4 59.9 ms.
-#ifndef PNL_TILE_THREADS
-#define PNL_TILE_THREADS 512  // threads of a tile workgroup (P1 / P0)
-#endif
-#ifndef PNL_TILE_WAVES
-#define PNL_TILE_WAVES 4      // waves per SIMD the tile kernel is register-limited to
-#endif
+constexpr int PNL_TILE_THREADS = 512;   // threads of a tile workgroup (P1 / P0)
+constexpr int PNL_TILE_WAVES = 4;       // waves per SIMD the tile kernel is register-limited to
 // P2 (78 local entries per pair) needs more than 256 VGPRs: one wave per SIMD without spills beats two with 600 B of scratch,
-// hence 256 threads per workgroup there; the general-exponent kernel (KT = 0: exp / log chains) spills at 128 VGPRs (57 ms against
-// 31 ms at noRef 6, s = 0.4) and keeps 256 threads x 2 waves as well
-// (the finite-horizon variant carries the sub-simplex loops of the cut pairs: 256 threads x 2 waves as well)
-// general exponent (KT == 0): 256 threads x 2 waves per SIMD while exp(e ln x) needed the registers (57 against 31 ms at 128
-// VGPRs); with the table-driven power (pnl_pow_tab) the 512 x 4 configuration of the other kernels is faster again (P1, s = 0.4,
-// 98,304 cells: 46.5 -> 35.6 ms).  -DPNL_KT0_WIDE=0 restores the narrow one.
-#ifndef PNL_KT0_WIDE
-#define PNL_KT0_WIDE 1
-#endif
-__host__ __device__ constexpr int tile_threads(int dpe, int kt, bool fh = false) { return (dpe > 3 || (kt == 0 && !PNL_KT0_WIDE) || fh) ? 256 : PNL_TILE_THREADS; }
-__host__ __device__ constexpr int tile_waves(int dpe, int kt, bool fh = false) { return dpe > 3 ? 1 : (((kt == 0 && !PNL_KT0_WIDE) || fh) ? 2 : PNL_TILE_WAVES); }
+// hence 256 threads per workgroup there; the finite-horizon variant carries the sub-simplex loops of the cut pairs: 256 threads x
+// 2 waves.  The general exponent (KT == 0) takes the 512 x 4 configuration like the other kernels: with the table-driven power
+// (pnl_pow_tab) it beats 256 x 2 (P1, s = 0.4, 98,304 cells: 46.5 -> 35.6 ms), so KT does not enter the choice.
+__host__ __device__ constexpr int tile_threads(int dpe, bool fh = false) { return (dpe > 3 || fh) ? 256 : PNL_TILE_THREADS; }
+__host__ __device__ constexpr int tile_waves(int dpe, bool fh = false) { return dpe > 3 ? 1 : (fh ? 2 : PNL_TILE_WAVES); }
 // SETTLED (dense 2D P1, tiles the plan has settled: pnl_setup.hip, k_tile_pair_codes): every pair of the tile is absent or a distant
 // pair of order 2, 3 or 4 with a packed rule, and the plan has recorded which: the first pass of the classification is a 16-bit load
 // per thread (codes[tile index][thread], layout: pnl_device.h) and the cell data only it reads is not staged.  Lists, chunk queue,
@@ -605,23 +585,17 @@ __host__ __device__ constexpr int tile_waves(int dpe, int kt, bool fh = false) {
 // come from the header, and the two passes over the codes, the reservations and the sort of list C are not compiled.  Evaluators,
 // flush and the ticket counter are the same code.
 template <int DIM, int DPE, int TILE, int KT, bool CLUSTER, bool FH = false, bool SETTLED = false, bool LISTS = false>
-__global__ void __launch_bounds__(tile_threads(DPE, KT, FH), tile_waves(DPE, KT, FH))
+__global__ void __launch_bounds__(tile_threads(DPE, FH), tile_waves(DPE, FH))
 k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__restrict__ A, long long ldA,
                double *__restrict__ Dglob, int cell_begin, int cell_end, int acc_stride, int4 *__restrict__ worklist,
-               unsigned *__restrict__ wl_count, unsigned wl_cap, int ablate, int ntiles, const ClusterTiles CT,
+               unsigned *__restrict__ wl_count, unsigned wl_cap, int flags, int ntiles, const ClusterTiles CT,
                unsigned *__restrict__ tile_ctr, const SlotOut SO, const unsigned short *__restrict__ codes) {
     static_assert(!LISTS || SETTLED, "pair lists: settled tiles only");
-    static_assert(!SETTLED || (!CLUSTER && !FH && DIM == 2 && DPE == 3 && TILE*TILE == 8*tile_threads(DPE, KT, FH)),
+    static_assert(!SETTLED || (!CLUSTER && !FH && DIM == 2 && DPE == 3 && TILE*TILE == 8*tile_threads(DPE, FH)),
                   "settled tiles: dense 2D P1, eight pairs per thread");
-    // debug switches that skip work (evaluation, accumulation, flush) exist only in PNL_DEBUG_ABLATE builds; bit 256 is
-    // PNL_FLAG_SYMMETRIC_FLUSH
-#ifdef PNL_DEBUG_ABLATE
-    const int abl = ablate;
-#else
-    const int abl = ablate & 256;
-#endif
+    const int symflush = flags & 256;                   // flags: bit 256 is PNL_FLAG_SYMMETRIC_FLUSH, the only one
     using S = TileSmem<DIM, DPE, TILE, KT == 0>;
-    constexpr int NV = S::NV, NC = S::NC, ND = S::ND, NT = tile_threads(DPE, KT, FH);
+    constexpr int NV = S::NV, NC = S::NC, ND = S::ND, NT = tile_threads(DPE, FH);
     constexpr int PAIRS = TILE*TILE, PER_THREAD = (PAIRS+NT-1)/NT;
     extern __shared__ double smem[];
     double *s_dbl = smem;
@@ -725,7 +699,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     // issued (a load issued behind the stores / atomics would wait for all of them), the flush zeroes the accumulators it has
     // read, and the barriers order the LDS only -- no wave waits for the flush of a tile to retire.  (Not with
     // PNL_FLAG_SYMMETRIC_FLUSH, whose second sweep reads the sub-block again.)
-    const bool pipe = !(abl & 256);
+    const bool pipe = !symflush;
     if (pipe) {
         for (int t = tid; t < ((CLUSTER ? CT.chunk_stride : SO.nU)+1)*acc_stride; t += NT) s_acc[t] = 0.;
         for (int t = tid; t < 2*TILE*ND; t += NT) s_D[t] = 0.;
@@ -801,8 +775,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         // dense: upper triangle of the cell pairs, a-cells of the caller's range.  Cluster tiles: n1 == n2 -> unordered pairs
         // once (chunk pair a <= b); n1 != n2 -> every ordered pair (X in n1.cells, Y in n2.cells); identical cells share all
         // vertices and are left to the touching-pair lists like every other touching pair
-        bool sel = !(abl & 8) &&
-                   (CLUSTER ? (!sym || ta < tb || i < j) : ((ta < tb || i < j || (fh && i == j)) && (ca >= cell_begin) && (ca < cell_end)));
+        bool sel = CLUSTER ? (!sym || ta < tb || i < j) : ((ta < tb || i < j || (fh && i == j)) && (ca >= cell_begin) && (ca < cell_end));
         // variable order: this launch assembles the pairs of one order class only
         if (!CLUSTER && P.cur_class >= 0 && sel) {
             const int la = P.clabel[ca];
@@ -812,7 +785,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         // sorted sparse pipeline through the far list (keys order + PNL_CUT_SHIFT / 121 + shared vertices - 1, like
         // k_fh_pairs), pairs inside the horizon are integrated here
         int rel = PNL_INTERACT;
-        q = tile_pair_order<DIM, TILE>(P.qo, sel, s_cf[i], cfb, s_cen, cenb, s_vid, s_lh, lhb, Llb, s_h, s_Ld, i, j, (abl & 16) != 0,
+        q = tile_pair_order<DIM, TILE>(P.qo, sel, s_cf[i], cfb, s_cen, cenb, s_vid, s_lh, lhb, Llb, s_h, s_Ld, i, j,
                                        [&](bool any_dof, bool shared) {
             if (!CLUSTER && fh && any_dof) {
                 if (shared) {
@@ -845,10 +818,8 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         const int key = fkey ? fkey : q;
         const int cls = !key ? 0 : (fkey ? 4 : (q == qA0 ? 1 : (q == qB0 ? 2 : (nq > 0 ? 3 : 4))));
         const int qs = (fh && cls == 4) ? 0 : q;         // finite horizon: the sparse pipeline counts what it is handed
-        if (!(abl & 32)) {
         cnt234[0] += __popcll(__ballot(qs == 2)); cnt234[1] += __popcll(__ballot(qs == 3)); cnt234[2] += __popcll(__ballot(qs == 4));
         if (!SETTLED) wave_bucket_add(s_cnt, qs > 4 ? qs : 0, false);
-        }
         nw0 += __popcll(__ballot(cls == 1)); nw1 += __popcll(__ballot(cls == 2));
         if (!SETTLED) nw2 += __popcll(__ballot(cls == 4));
         nw3 += __popcll(__ballot(cls == 3));
@@ -863,7 +834,6 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         if (lane < 4 && mine) mybase = atomicAdd(&s_misc[lane], mine);
         int bA = __builtin_amdgcn_readlane(mybase, 0), bB = __builtin_amdgcn_readlane(mybase, 1);
         int bF = __builtin_amdgcn_readlane(mybase, 2), bC = __builtin_amdgcn_readlane(mybase, 3);
-        if (!(abl & 128))
 #pragma unroll
         for (int g = 0; g < NG; g++)
 #pragma unroll
@@ -907,7 +877,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     // list C: counting sort by order into the free middle of the 32-bit list (behind list B, before the far list), chunks of 64
     // pairs of ONE order, highest order first.  s_cnt[0] = number of these chunks, s_cnt[1] = the chunk queue of the evaluation
     const int nC = LISTS ? 0 : __builtin_amdgcn_readfirstlane(s_misc[3]), nBl = LISTS ? 0 : __builtin_amdgcn_readfirstlane(s_misc[1]);
-    if (nC && tid == 64 && !(abl & 2)) {
+    if (nC && tid == 64) {
         int run = 0, nch = 0;
         for (int q = min(17, P.qmax); q >= 2; q--) {
             const int nq = s_ttn[q], c = s_cnt[q];
@@ -990,17 +960,6 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     auto accumulate = [&](const PairAcc<DIM, DPE> &R, int i, int j) {
         // NA:1405-1410: symmetric cell pairs count twice
         const double vv = 2.*s_vol[i]*s_vol[TILE+j]*kern_scale<KT>(P.k);
-        if (abl & 1) {
-            double keep = 0.;
-#pragma unroll
-            for (int a = 0; a < DPE; a++)
-#pragma unroll
-                for (int b = 0; b < DPE; b++) keep += R.G[a][b];
-#pragma unroll
-            for (int e2 = 0; e2 < ND; e2++) keep += R.S1[e2]+R.S2[e2];
-            if (keep == 1.2345e300) s_D[0] = keep*vv;
-            return;
-        }
         int e = 0;
 #pragma unroll
         for (int a = 0; a < DPE; a++) {
@@ -1017,15 +976,15 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
                     const int dA = s_dslot[i], dB = s_dslot[TILE+j];
                     if (dA >= 0) lds_add_f64(&s_D[(0*TILE+i)*ND+e], vv*R.S1[e]);
                     if (dB >= 0 && (sym || dA < 0)) lds_add_f64(&s_D[(1*TILE+j)*ND+e], vv*R.S2[e]);
-                } else if (!(abl & 64)) {
+                } else {
                     lds_add_f64(&s_D[(0*TILE+i)*ND+e], vv*R.S1[e]);
                     lds_add_f64(&s_D[(1*TILE+j)*ND+e], vv*R.S2[e]);
-                } else if (R.S1[e]+R.S2[e] == 1.2345e300) s_D[0] = 1.;
+                }
                 e++;
             }
         }
     };
-    if (nC && !(abl & 2)) {
+    if (nC) {
         if (!published) lds_barrier();
         for (int t = tid; t < nC; t += NT) {
             const int ent = s_list[PAIRS-1-t];
@@ -1037,7 +996,6 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     // One queue of 64-pair chunks for the three lists, the expensive ones first (list C from its highest order down, then list B,
     // then list A); a wave takes the next chunk when it is done with its last one -- no barrier between the lists, and the few
     // chunks of high orders no longer decide when the tile ends
-    if (!(abl & 2))
     kern_dispatch<KT, fh>(P.k, lpow, [&](auto ktag) {
     constexpr int KTE = decltype(ktag)::value;              // KT, or 3: the branch-free general power (pnl_common.h)
     // lists of the record: order 4, 3, 2 (n4, n3, n2 entries, one behind the other); else list C, B, A
@@ -1148,7 +1106,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
             for (int t = tid; t < 2*TILE*ND; t += NT) {
                 const double v = s_D[t];
                 s_D[t] = 0.;
-                if (v != 0. && !(abl & 4)) {
+                if (v != 0.) {
                     const int side = t/(TILE*ND), rem = t-side*TILE*ND;
                     if (CLUSTER) {
                         const int ds = s_dslot[side*TILE+rem/ND];
@@ -1175,7 +1133,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
             const int r = (int)__umulhi((unsigned)t, inv), c = t-r*acc_stride;
             const double v = s_acc[t];
             s_acc[t] = 0.;
-            if (r < nA && c < nB && !(abl & 4)) {
+            if (r < nA && c < nB) {
                 if (slots) slot_store(base+(long long)r*W+c, v);
                 else if (v != 0.) {
                     if (CLUSTER || fh) {
@@ -1191,7 +1149,6 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     } else {
     const int *__restrict__ dofA = CLUSTER ? CT.chunk_dofs+(size_t)ta*CT.chunk_stride : P.blk_dofs+(size_t)ta*P.blk_stride;
     const int *__restrict__ dofB = CLUSTER ? CT.chunk_dofs+(size_t)tb*CT.chunk_stride : P.blk_dofs+(size_t)tb*P.blk_stride;
-    if (!(abl & 4)) {
     if (!CLUSTER && !fh && SO.A2) {
         // block-slot storage (pnl_tile2.h): this tile owns its nA x nB sub-block of the storage, plain stores of every entry
         const int ca = SO.colbase[ta], W = SO.S-ca;
@@ -1219,7 +1176,7 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         }
     }
     // PNL_FLAG_SYMMETRIC_FLUSH (no mirror pass): the transposed image in its own sweep, consecutive threads along a row of A
-    if (!CLUSTER && (abl & 256))
+    if (!CLUSTER && symflush)
         for (int t = tid; t < nA*nB; t += NT) {
             const int c = t/nA, r = t-c*nA;
             const double v = s_acc[r*acc_stride+c];
@@ -1237,7 +1194,6 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
                 atomic_add_f64(&Dglob[(size_t)c*ND+rem%ND], v);
             }
         }
-    }
     }
     }
     lds_barrier();
@@ -1264,9 +1220,6 @@ template <int DIM, int DPE, int KT>
 __global__ void __launch_bounds__(PNL_NTHREADS, PNL_PURE_WAVES)
 k_tile_pure(const DevProblem P, const int2 *__restrict__ tiles, int ntiles, double *__restrict__ A, long long ldA,
             double *__restrict__ Dglob, int acc_stride, int q_uniform, int symflush, const SlotOut SO) {
-#ifndef PNL_DEBUG_ABLATE
-    symflush &= 1;                                      // the other bits skip work (debug builds only)
-#endif
     constexpr int TILE = 64, NV = DIM+1, NC = NV*DIM, ND = DPE*(DPE+1)/2, NP = (DIM == 2) ? 3 : 2, ST = 4+DPE;
     constexpr int JW = TILE/(PNL_NTHREADS/64);          // cells j per wave
     extern __shared__ double smem[];
@@ -1405,14 +1358,12 @@ k_tile_pure(const DevProblem P, const int2 *__restrict__ tiles, int ntiles, doub
             }
             // cross block -> LDS sub-block of A'
             const double vv = scale2*vola*volb;
-            if (!(symflush & 16)) {
 #pragma unroll
-                for (int b = 0; b < DPE; b++) {
-                    const int sb = s_slotb[j*DPE+b];
+            for (int b = 0; b < DPE; b++) {
+                const int sb = s_slotb[j*DPE+b];
 #pragma unroll
-                    for (int a = 0; a < DPE; a++) lds_add_f64(&s_acc[sa[a]+sb], -vv*G[a][b]);
-                }
-            } else if (G[0][0] == 1.2345e300) s_acc[0] = vv;
+                for (int a = 0; a < DPE; a++) lds_add_f64(&s_acc[sa[a]+sb], -vv*G[a][b]);
+            }
             // diagonal block of cell j: column sums over all cells i of the wave
             const double wa = valid ? vola : 0.;
             double cw[NP];
@@ -1462,14 +1413,14 @@ k_tile_pure(const DevProblem P, const int2 *__restrict__ tiles, int ntiles, doub
                 const int r = t/nB, cc = t-r*nB;
                 slot_store(base+(long long)r*W+cc, s_acc[r*acc_stride+cc]);
             }
-        } else if (!(symflush & 64))
+        } else
         for (int t = tid; t < nA*nB; t += PNL_NTHREADS) {
             const int r = t/nB, cc = t-r*nB;
             const double v = s_acc[r*acc_stride+cc];
             if (v != 0.) atomic_add_f64(&A[pnl_row(P, dofA[r])*ldA+pnl_col(P, dofB[cc])], v);
         }
         // PNL_FLAG_SYMMETRIC_FLUSH (no mirror pass): the transposed image in its own sweep, consecutive threads along a row of A
-        if (!(symflush & 64) && (symflush & 1))
+        if (symflush & 1)
             for (int t = tid; t < nA*nB; t += PNL_NTHREADS) {
                 const int cc = t/nA, r = t-cc*nA;
                 const double v = s_acc[r*acc_stride+cc];
@@ -2354,10 +2305,8 @@ k_worklist_sorted(const DevProblem P, const int4 *__restrict__ sorted, const uns
 template <int DIM, int DPE, int KT, bool SPARSE>
 __global__ void __launch_bounds__(PNL_NTHREADS)
 k_worklist_lane(const DevProblem P, const int4 *__restrict__ sorted, const unsigned *__restrict__ offs, double *__restrict__ A,
-                long long ldA, double *__restrict__ Dglob, const SparseOut S, int dbg, const ClusterTiles CT) {
-#ifndef PNL_DEBUG_ABLATE
-    dbg &= 8;                                           // the other bits skip work (debug builds only)
-#endif
+                long long ldA, double *__restrict__ Dglob, const SparseOut S, int flags, const ClusterTiles CT) {
+    const int symflush = flags & 8;                     // dense output: write (I, J) and (J, I) (PNL_FLAG_SYMMETRIC_FLUSH)
     const bool cluster = CT.npairs > 0;             // work list of the cluster tiles: entry.z indexes wl_pair / wl_ds
     constexpr int NV = DIM+1, NC = NV*DIM, ND = DPE*(DPE+1)/2, ST = 4+DPE, STP = (ST+1) & ~1;
     __shared__ unsigned s_coff[PNL_WL_BINS+1];
@@ -2501,11 +2450,10 @@ k_worklist_lane(const DevProblem P, const int4 *__restrict__ sorted, const unsig
             for (int a = 0; a < DPE; a++)
 #pragma unroll
                 for (int b = 0; b < DPE; b++)
-                    if (ld1[a] >= 0 && ld2[b] >= 0 && !(dbg & 1)) {
+                    if (ld1[a] >= 0 && ld2[b] >= 0) {
                         atomic_add_f64(&A[pnl_row(P, ld1[a])*ldA+pnl_col(P, ld2[b])], -vv*R.G[a][b]);
-                        if (dbg & 8) atomic_add_f64(&A[(long long)ld2[b]*ldA+ld1[a]], -vv*R.G[a][b]);      // symmetric flush
+                        if (symflush) atomic_add_f64(&A[(long long)ld2[b]*ldA+ld1[a]], -vv*R.G[a][b]);
                     }
-            if (!(dbg & 2))
 #pragma unroll
             for (int e = 0; e < ND; e++) {
                 atomic_add_f64(&Dglob[(size_t)c1*ND+e], vv*R.S1[e]);
@@ -3478,7 +3426,7 @@ k_tile_pair_codes(const DevProblem P, const DevFormula qo, const int2 *__restric
 #pragma unroll 2
         for (int k = 0; k < SWEEPS; k++) {
             const int i = tile_diag_cell(tile_sweep_row(tid, k, TILE, NT), j, TILE);
-            const int q = tile_pair_order<DIM, TILE>(qo, true, s_cf[i], cfb, s_cen, cenb, s_vid, s_lh, lhb, Llb, s_h, s_Ld, i, j, false,
+            const int q = tile_pair_order<DIM, TILE>(qo, true, s_cf[i], cfb, s_cen, cenb, s_vid, s_lh, lhb, Llb, s_h, s_Ld, i, j,
                                                      [&](bool any_dof, bool shared) { bad |= (any_dof && shared) ? 1 : 0; return true; });
             if (q) {
                 const int nq = (q <= 4 && q <= P.qmax) ? P.tt_n[q] : 0;

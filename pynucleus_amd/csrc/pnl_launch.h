@@ -9,12 +9,12 @@
 // where it fails), at most one per item; sets the kernel's dynamic LDS limit on the way.  rc != 0: that failed (ctx->err is set)
 struct PersistentGrid { int rc, grid, per_cu; };
 template <class K>
-static PersistentGrid persistent_grid(pnl_context *ctx, K kfun, int threads, size_t lds, int nitems, int per_cu_fallback, int mult = 1) {
+static PersistentGrid persistent_grid(pnl_context *ctx, K kfun, int threads, size_t lds, int nitems, int per_cu_fallback) {
     const hipError_t e = hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return {fail(ctx, PNL_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(e)), 0, 0};
     int per_cu = per_cu_fallback;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kfun, threads, lds);
-    return {PNL_OK, pnl_grid_cap(std::min(nitems, 256*std::max(per_cu, 1)*std::max(mult, 1))), per_cu};
+    return {PNL_OK, pnl_grid_cap(std::min(nitems, 256*std::max(per_cu, 1))), per_cu};
 }
 
 // dynamic LDS of the work-list kernels: the rule copy (+ for P2 the column sums of the PNL_NTHREADS / 16 pairs of a chunk) of
@@ -38,24 +38,24 @@ static size_t wl_lane_lds(F fun, int dpe, int kt) {
     return b;
 }
 
-// sorted evaluation of a work list: the orders with at most PNL_WL_LANE_MAXPTS points one pair per lane (k_worklist_lane, if
-// `lane`), the others 16 lanes per pair with the rule in LDS (k_worklist_sorted; bins nmin .. last_bin).  kb_option / kb_default:
-// KB of LDS for the rule copy; rules with more points are read from global memory.  18 KB are 8 workgroups per CU
+// sorted evaluation of a work list: the orders with at most PNL_WL_LANE_MAXPTS points one pair per lane (k_worklist_lane),
+// the others 16 lanes per pair with the rule in LDS (k_worklist_sorted, up to bin last_bin); sym: dense output, both images of
+// every entry (PNL_FLAG_SYMMETRIC_FLUSH, or behind the fold pass of the block-slot storage).  wl_kb: KB of LDS for the
+// rule copy; rules with more points are read from global memory.  18 KB are 8 workgroups per CU
 // (60 KB / 2 workgroups per CU was 0.6 ms slower at 98,304 cells in the dense path and 4 ms at C4 in the cluster path)
+constexpr int WL_RULE_KB = 18;       // dense and cluster work lists
 template <int DIM, int DPE, int KT, bool SPARSE>
-static int worklist_eval(pnl_context *ctx, const char *kb_option, int kb_default, const int4 *sorted, const WlBins &B, double *A, int64_t ldA,
-                  double *D, const SparseOut &S, const ClusterTiles &CT, int last_bin, int nmin, bool lane, int lane_flags) {
-    const int wl_kb = pnl_tune(kb_option) ? std::max(4, atoi(pnl_tune(kb_option))) : kb_default;
+static int worklist_eval(pnl_context *ctx, int wl_kb, const int4 *sorted, const WlBins &B, double *A, int64_t ldA,
+                  double *D, const SparseOut &S, const ClusterTiles &CT, int last_bin, bool sym) {
     const int tab_max = wl_tab_max<DPE>(wl_kb);
     const int wl_grid = 256*std::max(1, std::min(8, 150/(wl_kb+(KT == 0 ? 3 : 0))));      // KT == 0: + 3 KB of power tables
     const size_t lds = wl_sorted_lds<DPE>(tab_max);
     auto wfun = k_worklist_sorted<DIM, DPE, KT, SPARSE>;
     HIPCHK(ctx, hipFuncSetAttribute((const void*)wfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (lane)
-        hipLaunchKernelGGL((k_worklist_lane<DIM, DPE, KT, SPARSE>), dim3(256*4), dim3(PNL_NTHREADS), wl_lane_lds(k_worklist_lane<DIM, DPE, KT, SPARSE>, DPE, KT), ctx->stream, ctx->P,
-                           sorted, (const unsigned*)B.offs, A, (long long)ldA, D, S, lane_flags, CT);
+    hipLaunchKernelGGL((k_worklist_lane<DIM, DPE, KT, SPARSE>), dim3(256*4), dim3(PNL_NTHREADS), wl_lane_lds(k_worklist_lane<DIM, DPE, KT, SPARSE>, DPE, KT), ctx->stream, ctx->P,
+                       sorted, (const unsigned*)B.offs, A, (long long)ldA, D, S, sym ? 8 : 0, CT);
     hipLaunchKernelGGL(wfun, dim3(wl_grid), dim3(PNL_NTHREADS), lds, ctx->stream, ctx->P, sorted, (const unsigned*)B.offs,
-                       (const unsigned*)B.coff, A, (long long)ldA, D, tab_max, S, last_bin, nmin, CT);
+                       (const unsigned*)B.coff, A, (long long)ldA, D, tab_max, S, last_bin, (PNL_WL_LANE_MAXPTS+1) | (sym ? 1 << 16 : 0), CT);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }

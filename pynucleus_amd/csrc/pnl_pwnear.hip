@@ -69,13 +69,14 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
     HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
     ctx->run.tiles_launched = true;
     const int nbk = (ctx->nc+63)/64;
+    // the mixed tiles evaluate the rules with at most 16 points themselves (LDS sub-blocks); every other configuration classifies only
+    const bool in_tile = P1 && ctx->tile == 64;
     {
         // work list: only the pairs whose rule has more than 16 points arrive there when the tiles evaluate the others
         // themselves (overflow is detected by pnl_get_counters); the tile-less variant lists every pair of the cell range
         double pairs = 0.;
         for (long long c = cell_begin; c < cell_end; c++) pairs += (double)(ctx->nc-c);
-        const bool tiles_evaluate = P1 && ctx->tile == 64 && !pnl_tune("PNL_PW_NOMIXED");
-        const size_t want = tiles_evaluate ? (size_t)std::min<double>(std::max<double>(pairs*0.1, 1 << 20), 400e6)
+        const size_t want = in_tile ? (size_t)std::min<double>(std::max<double>(pairs*0.1, 1 << 20), 400e6)
                                            : (size_t)std::max<double>(pairs, 1024.);
         if (want > 1500000000ull) return fail(ctx, PNL_ERR_UNSUPPORTED, "%zu pairs exceed the work list of the pointwise path", want);
         if ((rc = reserve_worklist(ctx, want))) return rc;
@@ -97,7 +98,7 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
             if (DIM == 2) { F.a = sv-1.; F.b = 1.; F.e = sv; F.den0 = 0.4; } else { F.a = 2.*sv-1.; F.b = 0.; F.e = 2.*sv; F.den0 = 0.8; }
             return F;
         };
-        const bool allow = P1 && ctx->tile == T && ctx->qmax >= 2 && !pnl_tune("PNL_PW_NOTILE");
+        const bool allow = P1 && ctx->tile == T && ctx->qmax >= 2;
         const int a0 = cell_begin/T, a1 = (cell_end+T-1)/T;
         for (int d = 0; d < nbk; d++)
             for (int a = a0; a < a1 && a+d < nbk; a++) {
@@ -129,7 +130,6 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[EV_TILES_UNIFORM_DONE], ctx->stream));
     // the other tiles: classification, in-tile evaluation of the rules with at most 16 points (LDS sub-blocks), work list for the rest
-    const bool in_tile = P1 && ctx->tile == 64 && !pnl_tune("PNL_PW_NOMIXED");
     if constexpr (P1el) if (!mixed.empty() && in_tile) {
         const int acc_stride = ctx->nU+1;
         const size_t lds = sizeof(double)*(PNL_PW_LANE_MAXPTS*ST+64*PNL_PW_LANE_MAXPTS*2+2*64*ND)+sizeof(unsigned short)*64*64
@@ -159,7 +159,7 @@ int pointwise_impl(pnl_context *ctx, double *A, int64_t ldA, int zero_exterior, 
         const size_t lds = sizeof(double)*((size_t)tab_max*ST+(size_t)(PNL_NTHREADS/16)*tab_max*2);
         auto kfun = k_pw_distant<DIM, DPE>;
         HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const bool lane_kernel = P1 && !pnl_tune("PNL_PW_NOLANE");      // (with the in-tile evaluation only the rules of more than 16 points arrive here)
+        const bool lane_kernel = P1;      // (with the in-tile evaluation only the rules of more than 16 points arrive here)
         if constexpr (P1el) if (lane_kernel)
             hipLaunchKernelGGL((k_pw_lane<DIM>), dim3(256*2), dim3(PNL_NTHREADS), 0, ctx->stream, P, W, (const int4*)ctx->b_wlsorted.p,
                                (const unsigned*)B.offs, A, (long long)ldA, (double*)ctx->b_D.p);

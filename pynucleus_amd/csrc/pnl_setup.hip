@@ -37,7 +37,6 @@ struct TileOrderJob {
     std::vector<double> cellv;
     std::vector<int32_t> cdof;
     std::vector<int16_t> cslot;
-    bool reorder = true;                       // false (PNL_NO_REORDER): the reference's vertex order, lane tables only
     int nU = 0;
     UniLaneTables lanes[3];
     double lanes_seconds = 0.;
@@ -74,7 +73,6 @@ int pnl_tile_order_ready(pnl_context *ctx) {
     int rc2;
     ctx->ul_cellv_t = cellv_t;
     ctx->ul_cslot_t.assign(cslot_t.begin(), cslot_t.end());
-    if (!job->reorder) { delete job; ctx->tile_job = nullptr; return PNL_OK; }       // lperm is the identity: no tables of their own
     if ((rc2 = upload(ctx, ctx->b_cellv_t, cellv_t.data(), cellv_t.size()))) return rc2;
     if ((rc2 = upload(ctx, ctx->b_cdof_t, cdof_t.data(), cdof_t.size()))) return rc2;
     if ((rc2 = upload(ctx, ctx->b_cslot_t, cslot_t.data(), cslot_t.size()))) return rc2;
@@ -282,10 +280,9 @@ static void uni_lane_layout(int nblocks, int ncp, int nU, const int16_t *cslot_t
 static void tile_order_search(TileOrderJob *job) {
     const int nc = job->nc, T = job->T, nblocks = job->nblocks, ncp = job->ncp;
     // the blocks are independent: a few host threads
-    if (job->reorder)
-        host_threads([&](int th, int nthr) {
-            for (int b = th; b < nblocks; b += nthr) tile_order_block(b, nc, T, job->cells.data(), job->lperm.data());
-        });
+    host_threads([&](int th, int nthr) {
+        for (int b = th; b < nblocks; b += nthr) tile_order_block(b, nc, T, job->cells.data(), job->lperm.data());
+    });
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int16_t> cslot_t((size_t)3*ncp, -1);
     for (int c = 0; c < nc; c++) for (int k = 0; k < 3; k++) cslot_t[(size_t)k*ncp+c] = job->cslot[(size_t)job->lperm[(size_t)c*3+k]*ncp+c];
@@ -343,13 +340,13 @@ struct CellTables {
     std::vector<int> vptr, vcells;            // vertex -> cells adjacency (real cells)
 };
 
-static void start_tile_order_search(pnl_context *ctx, const CellTables &F, bool reorder) {
+static void start_tile_order_search(pnl_context *ctx, const CellTables &F) {
     const int nc = F.nc, nV = F.nV;
     TileOrderJob *job = new TileOrderJob;
     ctx->tile_job = job;
     job->cells = ctx->cells;
     job->nc = nc; job->T = F.T; job->nblocks = F.nblocks; job->ncp = F.ncp; job->dim = F.dim; job->dpe = F.dpe;
-    job->reorder = reorder; job->nU = ctx->nU;
+    job->nU = ctx->nU;
     job->cellv = F.cellv; job->cdof = F.cdof; job->cslot = F.cslot;   // the lane layout reads the slots: before the worker starts
     job->lperm.resize((size_t)nc*nV);
     for (int c = 0; c < nc; c++) for (int k = 0; k < nV; k++) job->lperm[(size_t)c*nV+k] = k;
@@ -749,7 +746,6 @@ static int finalize(pnl_context *ctx) {
     const int ncp = ctx->ncp = nblocks*T;
     CellTables F;
     F.dim = dim; F.nV = nV; F.nc = nc; F.dpe = dpe; F.T = T; F.nblocks = nblocks; F.ncp = ncp;
-    const bool reorder = dpe == nV && dim == 2 && !pnl_tune("PNL_NO_REORDER");
     tile_order_drop(ctx);
     int rc;
     if ((rc = padded_cell_tables(ctx, F))) return rc;
@@ -758,7 +754,7 @@ static int finalize(pnl_context *ctx) {
     // lane layout of the uniform-tile kernels, which reads the slots of the blocks (so the job starts behind block_dofs)
     ctx->have_tile_order = false;
     ctx->uni_lanes_up = -1;
-    if (dpe == nV && dim == 2) start_tile_order_search(ctx, F, reorder);
+    if (dpe == nV && dim == 2) start_tile_order_search(ctx, F);
     if ((rc = touching_cell_pairs(ctx, F))) return rc;
     if (ctx->nlab > 0 && (int)ctx->cell_labels.size() != nc) return fail(ctx, PNL_ERR_STATE, "cell labels do not match the mesh");
     if ((rc = upload_touching_pairs(ctx))) return rc;
@@ -903,14 +899,27 @@ std::mutex g_opt_mutex;
 // (the set of distinct values a process names is small)
 std::map<std::string, const std::string*> g_options;
 std::deque<std::string> g_option_values;
-// the options a product build accepts: the hooks through which the parity tests reach the alternative code paths, and the
-// diagnostics line
-const char *const k_product_options[] = {"PNL_WL_FRAC", "PNL_FH_NOTILES", "PNL_NO_POWTAB", "PNL_VERBOSE", "PNL_PLAN_TIMING", "PNL_PLAN_THREADS", "PNL_BND_OLD",
-                                         // profiling: every phase on the caller's stream, one after the other (per-kernel times that add up)
-                                         "PNL_NO_OVERLAP", "PNL_NO_FORK",
-                                         // tests: at most this many workgroups of a persistent tile kernel (every workgroup then walks
-                                         // many tiles at test sizes: the pipelined tile loops against the oracle)
-                                         "PNL_TILE_WGS", "PNL_UNI_GENERIC", "PNL_UNI_CHECKED", "PNL_UNI_LANES", "PNL_MIXED_GENERIC", "PNL_MIXED_UNSETTLED", "PNL_SETTLED_CODES"};
+// the options pnl_set_option accepts, all of them: the hooks through which the parity tests reach the alternative code paths, and
+// the diagnostics.  Every name is read by a pnl_tune call with the literal name somewhere in csrc/ (tests/test_abi.py checks both directions)
+const char *const k_product_options[] = {
+    "PNL_WL_FRAC",          // tests: work-list capacity as a fraction of the pairs, floor 64 entries (overflow must fail the call)
+    "PNL_FH_NOTILES",       // reference path: finite-horizon pairs through the pair lists, not the tile kernel
+    "PNL_NO_POWTAB",        // reference path: general power by exp / log instead of the tables
+    "PNL_VERBOSE",          // diagnostics: launch shapes and plan statistics on stderr
+    "PNL_PLAN_TIMING",      // diagnostics: times of the pattern planner's phases on stderr
+    "PNL_PLAN_THREADS",     // host threads of the planner
+    "PNL_BND_OLD",          // reference path: boundary term by k_boundary_distant instead of the tiled kernel
+    "PNL_NO_OVERLAP",       // profiling: every phase on the caller's stream, one after the other (per-kernel times that add up)
+    "PNL_NO_FORK",          // profiling: the order classes one after the other, no side streams
+    "PNL_TILE_WGS",         // tests: at most this many workgroups of a persistent tile kernel (every workgroup then walks many
+                            // tiles at test sizes: the pipelined tile loops against the oracle)
+    "PNL_UNI_GENERIC",      // reference path: uniform P1 tiles without the structured-rule evaluators
+    "PNL_UNI_CHECKED",      // tests: no uniform tile skips the per-pair validity test
+    "PNL_UNI_LANES",        // lane layout of the uniform P1 tiles: 0 identity, 1 searched (default), 2 random
+    "PNL_MIXED_GENERIC",    // reference path: mixed tiles without the structured-rule evaluators
+    "PNL_MIXED_UNSETTLED",  // reference path: every mixed tile through the classifying kernel
+    "PNL_SETTLED_CODES",    // reference path: settled tiles by their pair codes, not by the plan's pair lists
+};
 }  // namespace
 
 const char *pnl_tune(const char *name) {
@@ -919,30 +928,20 @@ const char *pnl_tune(const char *name) {
         auto it = g_options.find(name);
         if (it != g_options.end()) return it->second->c_str();
     }
-#ifdef PNL_TUNING
-    return getenv(name);
-#else
     return nullptr;
-#endif
 }
 
 extern "C" {
 
 const char *pnl_version(void) {
-#ifdef PNL_TUNING
-    return "pnl_hip 0.1 (gfx950, tuning build)";
-#else
     return "pnl_hip 0.1 (gfx950)";
-#endif
 }
 
 int pnl_set_option(const char *name, const char *value) {
     if (!name) return PNL_ERR_INVALID;
-#ifndef PNL_TUNING
     bool known = false;
     for (const char *k : k_product_options) known = known || std::strcmp(k, name) == 0;
     if (!known) return PNL_ERR_UNSUPPORTED;
-#endif
     std::lock_guard<std::mutex> lk(g_opt_mutex);
     if (value) {
         const std::string *v = nullptr;
@@ -975,11 +974,6 @@ int pnl_create(int device_id, pnl_context **out) {
     for (auto &e : ctx->ev)
         if (hipEventCreate(&e) != hipSuccess) { delete ctx; return PNL_ERR_HIP; }
     std::memset(&ctx->P, 0, sizeof(ctx->P));
-#ifdef PNL_DEBUG_ABLATE
-    if (const char *e = pnl_tune("PNL_ABLATE")) ctx->ablate = atoi(e);      // result-changing debug switches: debug builds only
-#endif
-    if (const char *e = pnl_tune("PNL_WL_LANE")) ctx->wl_lane = atoi(e) != 0;
-    if (const char *e = pnl_tune("PNL_PURE")) ctx->use_pure = atoi(e) != 0;
     ctx->cls.push_back(new pnl_context::ClassData());
     *out = ctx;
     return PNL_OK;
@@ -1402,7 +1396,7 @@ static int tile_orders(pnl_context *ctx, const TilePlan &R, const std::vector<in
     });
     // tiles the bounds left open: the exact order range of their cell pairs, on the device (2D; variable order: tiles whose
     // two blocks carry one label each -- their pairs all belong to this class and see its order formula)
-    if (!(allow && ctx->dim == 2 && (T == 64 || T == 32) && !pnl_tune("PNL_NO_EXACT_TILES"))) return PNL_OK;
+    if (!(allow && ctx->dim == 2 && (T == 64 || T == 32))) return PNL_OK;
     std::vector<int2> cand;
     std::vector<size_t> cand_idx;
     for (size_t i = 0; i < tiles.size(); i++) {
@@ -1437,9 +1431,8 @@ static int tile_orders(pnl_context *ctx, const TilePlan &R, const std::vector<in
 // 4096 pairs per tile in every assembly.  k_tile_order_range names the candidates, k_tile_pair_codes decides with the tile kernel's own
 // function.  settled: the settled tiles, those with the most pairs of a 6-point rule first (the tile loop hands out tickets: heavy
 // tiles first); is_settled: per entry of tiles.  No device memory for the codes, or no packed rules / DoF slots on the device: nothing is
-// settled, and that is no error.  The candidates come from the exact order range of tile_orders: where that is skipped (tuning option
-// PNL_NO_EXACT_TILES, uniform tiles switched off) nothing is settled either; a tile of ONE order 2 .. 4 that the uniform kernels do not
-// take (PNL_UNI_QMAX) is no candidate and stays with the classifying kernel.  The code kernel runs twice per plan (statistics of the
+// settled, and that is no error.  The candidates come from the exact order range of tile_orders: where that is skipped (no uniform
+// tiles for this element or order table) nothing is settled either.  The code kernel runs twice per plan (statistics of the
 // candidates, then the codes of the sorted list): a few milliseconds once per plan against an index array in the hot kernel.
 static int settle_tiles(pnl_context *ctx, const TilePlan &R, const std::vector<int2> &tiles, const std::vector<size_t> &open_234,
                         std::vector<int2> &settled, std::vector<char> &is_settled) {
@@ -1487,7 +1480,7 @@ static int tile_lists_single_launch(pnl_context *ctx, const TilePlan &R, const s
     ctx->sl_off[0] = 0;
     // symmetric order tables: a tile that holds pairs of several classes gets ONE entry that names the set of them (bit 29
     // + class bits); k_tile_p2 works through the classes inside one visit and flushes once with plain stores
-    const bool one_visit = norient == 1 && ncls > 1 && ncls <= 28 && !pnl_tune("PNL_P2_VISIT_PER_CLASS");
+    const bool one_visit = norient == 1 && ncls > 1 && ncls <= 28;
     std::vector<unsigned> tile_mask;
     if (one_visit) {
         tile_mask.assign((size_t)ctx->nblocks*ctx->nblocks, 0u);
@@ -1548,11 +1541,10 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
     R.filter = ctx->run.tile_cell_filter;
     // uniform tiles: order 2 through k_tile_pure (P1 in 1D and 2D), orders 2-4 through k_tile_uniform (2D: P1 orders 3 and 4, P2)
     R.p1 = T == 64 && (ctx->dpe == 3 || ctx->dpe == 2); R.p2 = ctx->dim == 2 && ctx->dpe == 6;
-    R.allow = ctx->use_pure && (R.p1 || R.p2) && ctx->qmax >= 2 && !ctx->nonsym;
+    R.allow = (R.p1 || R.p2) && ctx->qmax >= 2 && !ctx->nonsym;
     int qlimit = 2;
     if (ctx->dim == 2) for (int q = 3; q <= 4 && ctx->uni_off[q] >= 0 && ctx->uni_np[q] == 6 && q <= ctx->qmax; q++) qlimit = q;
     R.q2ok = R.p1 ? true : (ctx->uni_off[2] >= 0 && ctx->uni_np[2] == 3);
-    if (pnl_tune("PNL_UNI_QMAX")) qlimit = std::min(qlimit, std::max(2, atoi(pnl_tune("PNL_UNI_QMAX"))));
     R.qlimit = qlimit;
     // variable order: a class only visits the tiles whose blocks hold a label pair of that class (most blocks carry one
     // label, so the K passes together classify every tile about once instead of K times)
@@ -1651,7 +1643,7 @@ int pnl_block_row_costs(pnl_context *ctx, double *out, int n) {
     if (n != ctx->nblocks) return fail(ctx, PNL_ERR_INVALID, "pnl_block_row_costs: %d blocks expected", ctx->nblocks);
     const int T = ctx->tile, nb = ctx->nblocks;
     const bool p1 = T == 64 && (ctx->dpe == 3 || ctx->dpe == 2), p2 = ctx->dim == 2 && ctx->dpe == 6;
-    const bool allow = ctx->use_pure && (p1 || p2) && ctx->qmax >= 2 && !ctx->nonsym && ctx->cls.size() == 1;
+    const bool allow = (p1 || p2) && ctx->qmax >= 2 && !ctx->nonsym && ctx->cls.size() == 1;
     int qlimit = 2;
     if (ctx->dim == 2) for (int q = 3; q <= 4 && ctx->uni_off[q] >= 0 && ctx->uni_np[q] == 6 && q <= ctx->qmax; q++) qlimit = q;
     const pnl_order_formula F = ctx->cls[0]->form[0];

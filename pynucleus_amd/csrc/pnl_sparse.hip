@@ -70,9 +70,8 @@ int pairs_masked_impl(pnl_context *ctx, int np, const SparseOut &S, bool classif
         double *Dbuf = S.masks ? nullptr : (double*)ctx->b_D.p;
         if (Dbuf && !keepD) HIPCHK(ctx, hipMemsetAsync(Dbuf, 0, sizeof(double)*(size_t)ctx->ncp*ND, ctx->stream));      // keepD: the tiles of a finite horizon have been there
         // 60 KB of rule copy and the bins up to PNL_MAXQ: differences from the dense path that are kept, not decided
-        const int nmin = ctx->wl_lane ? PNL_WL_LANE_MAXPTS+1 : 0;
-        if ((rc = worklist_eval<DIM, DPE, KT, true>(ctx, "PNL_WL_MP_KB", 60, sorted, B, nullptr, 0, Dbuf, S, ClusterTiles{}, PNL_MAXQ, nmin,
-                                                    ctx->wl_lane, 0))) return rc;
+        constexpr int wl_mp_kb = 60;
+        if ((rc = worklist_eval<DIM, DPE, KT, true>(ctx, wl_mp_kb, sorted, B, nullptr, 0, Dbuf, S, ClusterTiles{}, PNL_MAXQ, false))) return rc;
         if (Dbuf) scatter_diag_sparse<DPE>(ctx, Dbuf, S);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -147,7 +146,7 @@ int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
         if (first) HIPCHK(ctx, hipEventRecord(ctx->ev[EV_START], ctx->stream));
         if (use_tiles) {
             auto kfun = k_tile_distant<DIM, DPE, TILE, KT, false, true>;
-            const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, KT, true), lds, nt, 2);
+            const PersistentGrid g = persistent_grid(ctx, kfun, tile_threads(DPE, true), lds, nt, 2);
             if (g.rc) return g.rc;
             if ((rc = ensure(ctx, ctx->b_tilectr, sizeof(unsigned)))) return rc;
             HIPCHK(ctx, hipMemsetAsync(ctx->b_tilectr.p, 0, sizeof(unsigned), ctx->stream));
@@ -157,7 +156,7 @@ int horizon_impl(pnl_context *ctx, SparseOut S, int cell_begin, int cell_end) {
             CT.wl_ds = (int2*)ctx->b_mp_pairs.p;                   // the pairs of the far-list entries
             SlotOut SOk{};
             SOk.nU = ctx->nU;                                      // rows of the LDS sub-block
-            hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, KT, true)), lds, ctx->stream, ctx->P, (const int2*)ctx->b_tiles.p+t0,
+            hipLaunchKernelGGL(kfun, dim3(g.grid), dim3(tile_threads(DPE, true)), lds, ctx->stream, ctx->P, (const int2*)ctx->b_tiles.p+t0,
                                (double*)nullptr, 0ll, (double*)ctx->b_D.p, std::max(cell_begin, 0), std::min(cell_end, ctx->nc), acc_stride, (int4*)ctx->b_mp_wl.p,
                                (unsigned*)ctx->b_wlcount.p, (unsigned)cap, 0, nt, CT, (unsigned*)ctx->b_tilectr.p, SOk, (const unsigned short*)nullptr);
         } else

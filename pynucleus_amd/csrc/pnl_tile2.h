@@ -38,14 +38,11 @@ __host__ __device__ constexpr int uni_rule_size(int dpe, int np) { return 3*np+n
 // A = A' + A'^T with A' gathered from the block-slot storage; every entry of A is written (no zero fill needed before).
 // 32 x 32 blocks of the upper block triangle, both images through an LDS transpose like k_mirror.
 // The gather runs over the COPIES: the copies of the 32 row DoFs x the copies of the 32 column DoFs form a grid of about
-// 42 x 42 candidate entries of the storage (1.3 copies per DoF); thread (ty, tx) takes the copy rows ty + 8 u and the copy
-// columns tx, tx + 32, loads the stored ones (six independent loads in flight) and adds them to the LDS image of the block
-// with ds_add_f64.  No per-entry walk whose length differs from lane to lane: the kernel was bound by instruction issue
+// 42 x 42 candidate entries of the storage (1.3 copies per DoF); the 256 threads share them as one index range, load the
+// stored ones (eight independent loads in flight per thread) and add them to the LDS image of the block with ds_add_f64.
+// No per-entry walk whose length differs from lane to lane: the kernel was bound by instruction issue
 // (1,050 VALU instructions per wave for 8 entries per thread) as much as by the chain of dependent loads.
 // Tables of a range of 32 DoFs come packed (FoldEntry[1 + PNL_FOLD_TAB], pnl_device.h): header + copies, one load per thread.
-#ifndef PNL_FOLD_FLAT
-#define PNL_FOLD_FLAT 1
-#endif
 template <bool NT>
 __global__ void __launch_bounds__(256)
 k_fold_mirror(const double *__restrict__ A2, const FoldEntry *__restrict__ tab, const int *__restrict__ cpoff, const int2 *__restrict__ cp,
@@ -80,7 +77,6 @@ k_fold_mirror(const double *__restrict__ A2, const FoldEntry *__restrict__ tab, 
     __syncthreads();
     const int n0 = (int)s_tab[0][0].off, n1 = (int)s_tab[1][0].off;
     if (n0 <= PNL_FOLD_TAB && n1 <= PNL_FOLD_TAB) {
-#if PNL_FOLD_FLAT
         // the nr x nc candidates of an image as ONE index range over the 256 threads, eight independent loads in flight per thread:
         // the (ty, tx) grid left the lanes tx >= nc - 32 of the second column sweep idle (nc is about 42) and had five or six loads
         // per thread in flight
@@ -108,34 +104,6 @@ k_fold_mirror(const double *__restrict__ A2, const FoldEntry *__restrict__ tab, 
                 for (int u = 0; u < 8; u++) if (dst[u] >= 0) lds_add_f64(tf+dst[u], v[u]);
             }
         }
-#else
-#pragma unroll
-        for (int g = 0; g < 2; g++) {                                   // g = 0: rows of range 0 -> t1, g = 1: rows of range 1 -> t2
-            if (g && bi == bj) break;
-            const int nr = g ? n1 : n0, nc = g ? n0 : n1;
-            double *__restrict__ tf = g ? &t2[0][0] : &t1[0][0];
-            for (int cj = tx; cj < nc; cj += 32) {
-                const FoldEntry col = s_tab[1-g][1+cj];
-                const int cb = col.ar >> 5, c = col.ar & 31;
-                for (int ci0 = ty; ci0 < nr; ci0 += 48) {
-                    double v[6];
-                    int dst[6];
-#pragma unroll
-                    for (int u = 0; u < 6; u++) {
-                        const int ci = ci0+8*u;
-                        dst[u] = -1;
-                        v[u] = 0.;
-                        if (ci < nr) {
-                            const FoldEntry rw = s_tab[g][1+ci];
-                            if (cb >= (rw.ar >> 5)) { v[u] = A2[rw.off+col.cy]; dst[u] = (rw.ar & 31)*33+c; }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < 6; u++) if (dst[u] >= 0) lds_add_f64(tf+dst[u], v[u]);
-                }
-            }
-        }
-#endif
     } else {
         // more copies than the packed table holds: per-entry walk over the lists in global memory
         auto gather = [&](int br, int bc, double (*t)[33]) {
@@ -206,9 +174,7 @@ __host__ __device__ constexpr size_t uniform_fixed_lds(int dpe, int np, int tile
 // the occupancy API how many workgroups that leaves per CU), except the P1 order-2 kernel of a general exponent, which needs 135
 // and is held to 128 so that a fourth workgroup fits (order-2 tiles at 98,304 cells, s = 0.4: 67.1 -> 61.5 ms), and the P1 6-point
 // kernels, held to 168 for the third (the general exponent needs 170: order-3 tiles 38.7 -> 28.7 ms)
-#ifndef PNL_U33K0_WAVES
-#define PNL_U33K0_WAVES 3
-#endif
+constexpr int PNL_U33K0_WAVES = 3;
 // STRUCT (P1, three points; pnl_context::uni_struct): equal weights w and w phi_b(y_j) = A + B delta_bj.  With the nine kernel values
 // g_ab = gamma(x_a, y_b), their row sums s_a, column sums c_b and total S, the cross block is
 //   G[a][b] = B^2 g_ab + A B (s_a + c_b) + A^2 S
@@ -240,14 +206,14 @@ __device__ __forceinline__ double uniform_f64(double v) {
 // a value loaded through the scalar cache, opaque from here on: the compiler keeps it in its scalar registers and does not load it again
 // inside a loop behind this point (it sinks loop-invariant scalar loads into the loop otherwise)
 __device__ __forceinline__ double scalar_f64(double v) { asm("" : "+s"(v)); return v; }
-#define PNL_UNI_FLAG_CHECKED 16                            // bit of k_tile_uniform's flags: every tile through the checked pair loop
+// k_tile_uniform's flags: bit 1 PNL_FLAG_SYMMETRIC_FLUSH, bit 8 power tables behind the sub-block, and
+#define PNL_UNI_FLAG_CHECKED 16                            // every tile through the checked pair loop
 
 template <int DPE, int NP, int KT, bool STRUCT = false>
 __global__ void __launch_bounds__(256, (DPE == 3 && NP == 3) ? (KT == 0 ? PNL_U33K0_WAVES : (KT == 2 ? 4 : 2)) : ((DPE == 3 && NP == 6) ? 3 : 2))
 k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__restrict__ tile_cls, const DevKernel *__restrict__ kcls,
                int ntiles, double *__restrict__ A, long long ldA, double *__restrict__ Dglob, int acc_stride, int q_uniform,
                int flags, const double *__restrict__ rule_g, int nUe, const SlotOut SO, unsigned *__restrict__ tile_ctr, const UniLanes UL) {
-    const int flags_in = flags;
     constexpr int DIM = 2, NV = 3, NC = 6, ND = DPE*(DPE+1)/2, NT = 256, NW = NT/64;
     constexpr int TILE = DPE == 6 ? 32 : 64, HALVES = 64/TILE, JW = TILE/NW, ITER = JW/HALVES;
     constexpr int R_BARY = 0, R_W = 3*NP, R_WPH = R_W+NP, R_PP = R_WPH+NP*DPE;
@@ -261,9 +227,6 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
     constexpr bool P1 = DPE == 3;                        // tile-constant work out of the pair loop (see above); P2 as it was
     constexpr int OFFB = P1 ? (int)sizeof(double) : 1;   // unit of s_slotb / s_sa: bytes (P1) or entries of the sub-block
     const pnl_const_f64_ptr rule = (pnl_const_f64_ptr)(unsigned long long)rule_g;
-#ifndef PNL_DEBUG_ABLATE
-    flags &= 1;                                          // the other bits skip work (debug builds only)
-#endif
     extern __shared__ double smem[];
     double *s_y = smem;                                  // [TILE][PS] quadrature points of the b-cells
     double *s_x = s_y+TILE*PS;                           // [TILE][XS] quadrature points (P2: vertices) of the a-cells
@@ -285,7 +248,7 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
     double *s_acc = (double*)(s_dof+(dof_lists ? 4*nUe : 0));    // [nUe+1][acc_stride]; nUe even
     // tables of the general power (KT == 0) behind the sub-block, if the launcher made room for them (bit 8 of flags: they
     // must not cost the second workgroup per CU)
-    const bool have_pow = KT == 0 && (flags_in & 8) != 0;
+    const bool have_pow = KT == 0 && (flags & 8) != 0;
     double *s_pow = s_acc+(size_t)(nUe+1)*acc_stride;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane%TILE, half = lane/TILE;
@@ -417,7 +380,7 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
         const double vola = s_vola[li];
         bool unchecked = false;                              // wave-uniform, the same in every wave
         if constexpr (P1) {
-            unchecked = __builtin_amdgcn_readfirstlane(s_next[1]) == 0x00010001 && !(flags_in & PNL_UNI_FLAG_CHECKED);
+            unchecked = __builtin_amdgcn_readfirstlane(s_next[1]) == 0x00010001 && !(flags & PNL_UNI_FLAG_CHECKED);
             tiles_unchecked += unchecked ? 1u : 0u; tiles_checked += unchecked ? 0u : 1u;
         }
         kern_dispatch<KT>(kk, ptab, [&](auto ktag) {
@@ -519,16 +482,14 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                     racc[a] = __builtin_fma(vvw, sr[a], racc[a]);
                     cacc[a] = __builtin_fma(vvw, sc[a], cacc[a]);
                 }
-                if (!(flags & 4)) {
-                    const double k2 = -vv*qk2, k1 = -vv*qk1, T = (-vv*qk0)*S;
-                    double ra[3], cb[3];
+                const double k2 = -vv*qk2, k1 = -vv*qk1, T = (-vv*qk0)*S;
+                double ra[3], cb[3];
 #pragma unroll
-                    for (int a = 0; a < 3; a++) { ra[a] = __builtin_fma(k1, sc[a], T); cb[a] = k1*sr[a]; }
+                for (int a = 0; a < 3; a++) { ra[a] = __builtin_fma(k1, sc[a], T); cb[a] = k1*sr[a]; }
 #pragma unroll
-                    for (int b = 0; b < 3; b++)
+                for (int b = 0; b < 3; b++)
 #pragma unroll
-                        for (int a = 0; a < 3; a++) lds_add_f64((double*)((char*)s_acc+(sa[a]+sbj[b])), __builtin_fma(k2, g[a][b], ra[b]+cb[a]));
-                } else if (S == 1.2345e300) s_acc[0] = vv;
+                    for (int a = 0; a < 3; a++) lds_add_f64((double*)((char*)s_acc+(sa[a]+sbj[b])), __builtin_fma(k2, g[a][b], ra[b]+cb[a]));
                 continue;
             }
             double c[NP], G[DPE][DPE];
@@ -594,17 +555,15 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                 }
             }
             // cross block -> LDS sub-block of A'
-            if (!(flags & 4)) {
 #pragma unroll
-                for (int b = 0; b < DPE; b++) {
-                    const int sb = sbj[b];
+            for (int b = 0; b < DPE; b++) {
+                const int sb = sbj[b];
 #pragma unroll
-                    for (int a = 0; a < DPE; a++) {
-                        if constexpr (P1) lds_add_f64((double*)((char*)s_acc+(sa[a]+sb)), -vv*G[a][b]);
-                        else lds_add_f64(&s_acc[sa[a]+sb], -vv*G[a][b]);
-                    }
+                for (int a = 0; a < DPE; a++) {
+                    if constexpr (P1) lds_add_f64((double*)((char*)s_acc+(sa[a]+sb)), -vv*G[a][b]);
+                    else lds_add_f64(&s_acc[sa[a]+sb], -vv*G[a][b]);
                 }
-            } else if (G[0][0]+G[1][2]+G[DPE-1][DPE-1] == 1.2345e300) s_acc[0] = vv;
+            }
             // scaled column sums of cell j
 #pragma unroll
             for (int jp = 0; jp < NP; jp++) {
@@ -661,7 +620,7 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                     slot_store2(row+cc, v.x, v.y);
                 }
             }
-        } else if (!(flags & 2))
+        } else
 #pragma unroll 1
         for (int r = wv; r < nA; r += NW) {
             double *__restrict__ row = A+(long long)__builtin_amdgcn_readfirstlane(dA[r])*ldA;
@@ -688,7 +647,6 @@ k_tile_uniform(const DevProblem P, const int2 *__restrict__ tiles, const int *__
                     }
                 }
             }
-        if (flags & 2) for (int t = tid; t < (nUe+1)*acc_stride; t += NT) s_acc[t] = 0.;
         // diagonal blocks of both sides from the scaled row / column sums: PARTS neighbouring lanes share a (side, cell), read its sums
         // with one instruction and zero them with a later one (LDS operations of a wave complete in order), each takes every
         // PARTS-th entry

@@ -33,7 +33,7 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
     // P1: 108-168 VGPRs allow three or four waves per SIMD and as many 38-53 KB workgroups share a CU (order-3 tiles of a general
     // exponent 36.4 -> 28.8 ms at 98,304 cells, s = 1/2: 17.8 -> 17.2; order-2 tiles of s = 1/2 with four: 42.8 -> 41.3 ms);
     // P2: two workgroups of 80 KB
-    const size_t cap_cu = (size_t)std::max(1, pnl_tune("PNL_UNI_PER_CU") ? atoi(pnl_tune("PNL_UNI_PER_CU")) : 4);
+    constexpr int cap_cu = 4;
     auto kfun = k_tile_uniform<DPE, NP, KT, STRUCT>;
     HIPCHK(ctx, hipFuncSetAttribute((const void*)kfun, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(160*1024, lds+sizeof(double)*PNL_POW_TAB_DOUBLES)));
     // workgroups that are really resident per CU (LDS and registers): the tile loop strides by the grid, a workgroup that has
@@ -44,7 +44,7 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
             (void)hipGetLastError();
             occ = (int)std::min<size_t>(2, (160*1024)/bytes);
         }
-        return std::max(1, std::min((int)cap_cu, occ));
+        return std::max(1, std::min(cap_cu, occ));
     };
     int pow_flag = 0;
     if (KT == 0) {
@@ -52,7 +52,7 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
         const size_t tab = sizeof(double)*PNL_POW_TAB_DOUBLES;
         const int per_cu0 = resident(lds);
         if (lds+tab <= 160*1024 && resident(lds+tab) == per_cu0) { lds += tab; pow_flag = 8; }
-        else if (lanes_mode == 0 && !pnl_tune("PNL_UNI_KEEP_STRIDE")) {
+        else if (lanes_mode == 0) {
             // the padded row stride of the sub-block (fewer LDS bank conflicts) or the tables: the tables win (measured)
             const int odd = (nUe+1) | 1;
             const size_t alt = fixed+sizeof(double)*(size_t)(nUe+1)*odd+tab;
@@ -85,13 +85,9 @@ int launch_uniform_t(pnl_context *ctx, const DevProblem &Pt, const int2 *tiles, 
                 lanes_mode, m.empty() ? 0. : sum/(double)m.size(), m.size(), ctx->uni_lanes_seconds);
     }
     const int uni_checked = (DPE == 3 && pnl_tune("PNL_UNI_CHECKED")) ? PNL_UNI_FLAG_CHECKED : 0;      // tests: no tile skips the validity test
-    int uni_abl = 0;
-#ifdef PNL_DEBUG_ABLATE
-    uni_abl = pnl_tune("PNL_UNI_ABL") ? atoi(pnl_tune("PNL_UNI_ABL")) : 0;
-#endif
     kt_begin(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     hipLaunchKernelGGL(kfun, dim3(grid), dim3(256), lds, ctx->stream, Pt, tiles, tile_cls, (const DevKernel*)ctx->b_kcls.p, ntiles, A,
-                       (long long)ldA, Dglob, acc_stride, q, (ctx->run.symflush ? 1 : 0) | uni_abl | pow_flag | uni_checked, (const double*)ctx->b_uni.p+ctx->uni_off[q],
+                       (long long)ldA, Dglob, acc_stride, q, (ctx->run.symflush ? 1 : 0) | pow_flag | uni_checked, (const double*)ctx->b_uni.p+ctx->uni_off[q],
                        nUe, SO, ctr, UL);
     kt_end(ctx, PNL_K_TILE_UNIFORM2+(q-2));
     HIPCHK(ctx, hipGetLastError());
