@@ -92,10 +92,13 @@ __device__ __forceinline__ void eval_distant_generic(const DevProblem &P, int of
 // so u_{DPE-1}(i) = r_i - sum_{b < DPE-1} u_b(i) saves one FMA per point pair.
 // (The table is read through the constant address space: it is never written by a kernel, and loads from that address space
 // with a uniform address are scalar loads wherever they stand -- global loads after the first store of a kernel are not.)
-template <int DIM, int DPE, int KT, int N>
+// SUMS (settled tiles with pair lists, see eval_struct3_sums): no S1 / S2; vv r_i is added to Ra[i] (LDS) from inside the row loop, csum
+// receives vv c_j; both sides in the packed point order of tab.
+template <int DIM, int DPE, int KT, int N, bool SUMS = false>
 __device__ __forceinline__ void eval_distant_fixed(const DevProblem &P, const double *__restrict__ tab, const double *gwp_global,
                                                    const double *av, const double *bv, PairAcc<DIM, DPE> &R,
-                                                   const double *__restrict__ lpow = nullptr) {
+                                                   const double *__restrict__ lpow = nullptr, double vv = 0., bool act = false,
+                                                   double *Ra = nullptr, double *csum = nullptr) {
     constexpr int NV = DIM+1, ST = 4+DPE;
     const pnl_const_f64_ptr gwp = (pnl_const_f64_ptr)(unsigned long long)gwp_global;
     // the weights are folded into the accumulations instead of being multiplied into every kernel value: with g = gamma(x_i, y_j)
@@ -146,11 +149,18 @@ __device__ __forceinline__ void eval_distant_fixed(const DevProblem &P, const do
             const double pa = wi*tab[i*ST+4+a];
 #pragma unroll
             for (int b = 0; b < DPE; b++) R.G[a][b] = __builtin_fma(pa, u[b], R.G[a][b]);
+            if constexpr (!SUMS) {
             const double pr = pa*r;
 #pragma unroll
             for (int b = a; b < DPE; b++) { R.S1[e] = __builtin_fma(pr, tab[i*ST+4+b], R.S1[e]); e++; }
+            }
         }
+        if constexpr (SUMS) { if (act) lds_add_f64(Ra+i, vv*r); }
     }
+    if constexpr (SUMS) {
+#pragma unroll
+        for (int j = 0; j < N; j++) csum[j] = vv*c[j];
+    } else {
 #pragma unroll
     for (int j = 0; j < N; j++) {
         int e = 0;
@@ -160,6 +170,7 @@ __device__ __forceinline__ void eval_distant_fixed(const DevProblem &P, const do
 #pragma unroll
             for (int b = a; b < DPE; b++) { R.S2[e] = __builtin_fma(pc, tab[j*ST+4+b], R.S2[e]); e++; }
         }
+    }
     }
 }
 
@@ -355,6 +366,125 @@ __device__ __forceinline__ void eval_struct6(const DevKernel &kk, pnl_const_f64_
         for (int b = a; b < 3; b++) { R.S2[e] = (a == b ? T2+D2[a] : T2)+(Q2[a]+Q2[b]); e++; }
 }
 
+// Twins of the two structured evaluators for the settled tiles with pair lists (k_tile_distant<.., LISTS>).  The diagonal blocks are
+// linear in the sums r_i = sum_j w_j g_ij and c_j = sum_i w_i g_ij: S1[ab] = sum_i (w phi_a phi_b)(x_i) r_i, S2 the same with c_j.  So the
+// twins hand back the cross block G (the same operations as above) and vv r_i, vv c_j (vv: the factor of the pair) instead of S1 / S2; the
+// tile adds them per (cell, point) and forms the six entries once per cell at its flush.  Three points: both sides in orbit order.
+template <int KT>
+__device__ __forceinline__ void eval_struct3_sums(const DevKernel &kk, pnl_const_f64_ptr rule, const double *av, const double *bv, double vv,
+                                                  PairAcc<2, 3> &R, double (&r)[3], double (&c)[3], const double *__restrict__ lpow) {
+    constexpr int R_W = 9, R_WPH = 12;                   // bary[3][3], w[3], w phi[3][3]
+    double x[3][2], y[3][2];
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            double sx = 0., sy = 0.;
+#pragma unroll
+            for (int k = 0; k < 3; k++) { sx = __builtin_fma(rule[3*p+k], av[2*k+d], sx); sy = __builtin_fma(rule[3*p+k], bv[2*k+d], sy); }
+            x[p][d] = sx; y[p][d] = sy;
+        }
+    double g[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            double d2 = 0.;
+#pragma unroll
+            for (int d = 0; d < 2; d++) { const double t = x[a][d]-y[b][d]; d2 = __builtin_fma(t, t, d2); }
+            g[a][b] = kern_eval<KT>(kk, d2, lpow);
+        }
+    double sr[3], sc[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) { sr[a] = (g[a][0]+g[a][1])+g[a][2]; sc[a] = (g[0][a]+g[1][a])+g[2][a]; }
+    const double S = (sr[0]+sr[1])+sr[2];
+    const double A = rule[R_WPH+1], B = rule[R_WPH]-rule[R_WPH+1];
+    const double k2 = B*B, k1 = A*B, T = (A*A)*S;
+    double ra[3], rc[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) { ra[a] = __builtin_fma(k1, sr[a], T); rc[a] = k1*sc[a]; }
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) R.G[a][b] = __builtin_fma(k2, g[a][b], ra[a]+rc[b]);
+    const double vw = vv*rule[R_W];
+#pragma unroll
+    for (int a = 0; a < 3; a++) { r[a] = vw*sr[a]; c[a] = vw*sc[a]; }
+}
+
+// six points: rows in the packed point order of tab, columns in orbit order, as in eval_struct6.  staged (wave-uniform): the tile holds the
+// points of this order in its LDS (pts: start of the doubles, TileSmem::o_pt; the same FMA chains, so the kernel values keep their bits),
+// ia / jb are the cells.
+// The row sums go to Ra[0 .. 5] (LDS, the row of cell ia) from inside the rolled row loop.
+template <int KT, class S, int TILE>
+__device__ __forceinline__ void eval_struct6_sums(const DevKernel &kk, pnl_const_f64_ptr rule, const double *__restrict__ tab, const double *av,
+                                                  const double *bv, const double *__restrict__ pts, bool staged, int ia, int jb, double vv, bool act,
+                                                  double *Ra, PairAcc<2, 3> &R, double (&c)[6], const double *__restrict__ lpow) {
+    constexpr int NP = 6, ST = 7, R_W = 3*NP, R_WPH = R_W+NP;
+    double y[NP][2];
+    if (staged) {
+#pragma unroll
+        for (int j = 0; j < NP; j++)
+#pragma unroll
+            for (int d = 0; d < 2; d++) y[j][d] = pts[S::o_pt(1, j, d)+jb];
+    } else {
+#pragma unroll
+        for (int j = 0; j < NP; j++)
+#pragma unroll
+            for (int d = 0; d < 2; d++) {
+                double s = 0.;
+#pragma unroll
+                for (int k = 0; k < 3; k++) s = __builtin_fma(rule[3*j+k], bv[2*k+d], s);
+                y[j][d] = s;
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; j++) c[j] = 0.;
+    const double w0 = rule[R_W], w1 = rule[R_W+3];
+    const double A0 = rule[R_WPH+1], B0 = rule[R_WPH]-A0, A1 = rule[R_WPH+3*3+1], B1 = rule[R_WPH+3*3]-A1;
+    const double vw0 = vv*w0, vw1 = vv*w1;
+    const double *__restrict__ xa = pts+S::o_pt(0, 0, 0)+ia;
+#pragma unroll 1
+    for (int i = 0; i < NP; i++) {
+        double x[2];
+        if (staged) {
+            x[0] = xa[(2*i)*TILE]; x[1] = xa[(2*i+1)*TILE];
+        } else {
+#pragma unroll
+            for (int d = 0; d < 2; d++) {
+                double s = 0.;
+#pragma unroll
+                for (int k = 0; k < 3; k++) s = __builtin_fma(tab[i*ST+k], av[2*k+d], s);
+                x[d] = s;
+            }
+        }
+        const double wi = tab[i*ST+3];
+        double g[NP];
+#pragma unroll
+        for (int j = 0; j < NP; j++) {
+            double d2 = 0.;
+#pragma unroll
+            for (int d = 0; d < 2; d++) { const double t = x[d]-y[j][d]; d2 = __builtin_fma(t, t, d2); }
+            g[j] = kern_eval<KT>(kk, d2, lpow);
+            c[j] = __builtin_fma(wi, g[j], c[j]);
+        }
+        const double s0 = (g[0]+g[1])+g[2], s1 = (g[3]+g[4])+g[5];
+        if (act) lds_add_f64(Ra+i, __builtin_fma(vw0, s0, vw1*s1));
+        const double base = __builtin_fma(A0, s0, A1*s1);
+        double u[3];
+#pragma unroll
+        for (int b = 0; b < 3; b++) u[b] = __builtin_fma(B0, g[b], __builtin_fma(B1, g[3+b], base));
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const double pa = wi*tab[i*ST+4+a];
+#pragma unroll
+            for (int b = 0; b < 3; b++) R.G[a][b] = __builtin_fma(pa, u[b], R.G[a][b]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; j++) c[j] *= vv;
+}
+
 // eval_distant_blocked: pnl_common.h
 // the evaluator of a work-list kernel: the branch-free power where it applies
 template <int DIM, int DPE, int KT, int CM>
@@ -488,6 +618,22 @@ struct TileSmem {
                                                            // [TILE*TILE] 32 bit: list B from the front, far list from the back
     static constexpr int n_short = o_list+3*TILE*TILE+2;
     static constexpr size_t fixed_bytes = sizeof(double)*n_dbl+sizeof(int)*n_int+sizeof(short)*((n_short+3)/4*4);
+    // The LISTS instantiation of k_tile_distant (2D P1) stages and classifies nothing, so s_cen, s_h, s_D, s_Ld, s_vid, s_cf, s_lh and
+    // the 32-bit lists are free (30.5 KB).  It overlays them with (offsets in doubles from the start of the doubles):
+    //   s_R  [2][TILE][NR]     per-(cell, point) sums of the diagonal blocks, points of order 2, 3, 4 at r_off(q), in the 32-bit lists
+    //   s_PP [2][ND][NR]       w phi_a phi_b per side and point in the point order of the side's sums, in s_vid
+    //   points of order 3, [side][point][dim][TILE]: side a in s_h .. s_Ld (one piece: the row loop indexes it), side b behind it,
+    //   in s_cen and in s_cf .. s_lh (compile-time point index).  The points of order 2 (6 KB more) do not fit.
+    static constexpr int NR = 15;
+    __host__ __device__ static constexpr int r_off(int q) { return q == 2 ? 0 : (q == 3 ? 3 : 9); }
+    static constexpr int o_R = n_dbl+n_int/2+(o_list+TILE*TILE)/4;
+    static constexpr int o_PP = n_dbl+o_vid/2;
+    __host__ __device__ static constexpr int o_pt(int side, int p, int d) {
+        const int r = 2*p+d;
+        return side == 0 ? o_h+r*TILE : (r < 4 ? o_h+(12+r)*TILE : (r < 8 ? o_cen+(r-4)*TILE : n_dbl+o_cf/2+(r-8)*TILE));
+    }
+    static constexpr bool overlay_ok = DIM == 2 && DPE == 3 && n_int%2 == 0 && o_list%4 == 0 && (TILE*TILE)%4 == 0 && o_vid%2 == 0 && o_cf%2 == 0 &&
+        2*TILE*NR <= TILE*TILE/2 && 2*ND*NR <= NV*TILE && o_tt-o_h >= 16*TILE && o_vol-o_cen >= 4*TILE && o_ttn-o_cf >= 8*TILE;
 };
 
 // Wave-aggregated bucket counter: lanes with the same key q (> 0) are handed consecutive positions from ONE LDS atomic
@@ -582,8 +728,10 @@ __host__ __device__ constexpr int tile_waves(int dpe, bool fh = false) { return 
 // LISTS (settled tiles whose pair lists the plan holds as well): the lists, the chunk queue and the order statistics of a settled tile
 // depend on its codes alone, so the plan keeps them too (k_tile_pair_lists, record layout: pnl_device.h; `codes` are the records then).
 // stage() copies the record of the next tile into the front of s_list, its header into s_chunk; the chunk queue and the statistics
-// come from the header, and the two passes over the codes, the reservations and the sort of list C are not compiled.  Evaluators,
-// flush and the ticket counter are the same code.
+// come from the header, and the two passes over the codes, the reservations and the sort of list C are not compiled.  In the LDS this
+// frees (TileSmem) it keeps one sum per (cell, point) for the diagonal blocks instead of s_D -- the evaluators hand back row and column
+// sums, the flush forms the six entries per cell -- and the points of order 3 of both sides, formed once per tile by stage().  The cross
+// block, the flush of the sub-block and the ticket counter are the same code.
 template <int DIM, int DPE, int TILE, int KT, bool CLUSTER, bool FH = false, bool SETTLED = false, bool LISTS = false>
 __global__ void __launch_bounds__(tile_threads(DPE, FH), tile_waves(DPE, FH))
 k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__restrict__ A, long long ldA,
@@ -634,6 +782,30 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         qA0 = (n == ((DIM == 2) ? 3 : 2)) ? q : qA0;
         qB0 = (n == ((DIM == 2) ? 6 : 3)) ? q : qB0;
     }
+    // LISTS: the per-(cell, point) sums in place of s_D, the table w phi_a phi_b of its flush and the staged points of order 3 (layout:
+    // TileSmem).  The sums of a side are in the point order of its evaluator -- orbit order (rule block of P.uni) under the structured
+    // evaluators, except the rows of a 6-point rule; else the packed order of tt_tab -- and the table follows it.  Read from global
+    // memory: no barrier has published s_tt yet, and the first reader of s_PP is a flush.
+    constexpr int NR = S::NR;
+    double *s_R = s_dbl+S::o_R, *s_PP = s_dbl+S::o_PP;
+    const bool pt_staged = LISTS && ((P.mix_struct >> 3) & 1);     // the structured 6-point evaluator takes the points of order 3 from the LDS
+    if constexpr (LISTS) {
+        static_assert(S::overlay_ok, "LISTS: sums, flush table and staged points in the LDS that the classification does not use");
+        for (int t = tid; t < 2*ND*NR; t += NT) {
+            const int side = t/(ND*NR), e = (t/NR)%ND, k = t%NR;
+            const int q = k < S::r_off(3) ? 2 : (k < S::r_off(4) ? 3 : 4), p = k-S::r_off(q), n = q == 2 ? 3 : 6;
+            const int a = e < 3 ? 0 : (e < 5 ? 1 : 2), b = e < 3 ? e : (e < 5 ? e-2 : 2);
+            double v = 0.;
+            if (q <= P.qmax && P.tt_n[q] == n) {
+                if (((P.mix_struct >> q) & 1) && (side == 1 || q == 2)) v = P.uni[P.uni_off[q]+(7+e)*n+p];
+                else {
+                    const double *__restrict__ tp = P.tt_tab+(size_t)(P.tt_off[q]+p)*(4+DPE);
+                    v = tp[3]*tp[4+a]*tp[4+b];
+                }
+            }
+            s_PP[t] = v;
+        }
+    }
     // persistent workgroups: the first tile by block index, every further one from a global counter (heavy tiles come first in
     // the list and tile costs differ by an order of magnitude: a static stride leaves 14 % of the wave slots idle at the end)
     __shared__ int s_tile_next;
@@ -682,6 +854,29 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
         }
         // what the classification reads per cell: one 8-byte word (padding and volume-zero cells carry negative vertex ids)
         if (!SETTLED) s_cf[side*TILE+l] = make_int2((vid0 >= 0 ? 1 : 0) | (has_dof ? 2 : 0), __float_as_int((float)P.clog[2*(size_t)P.ncp+c]));
+        if constexpr (LISTS) {
+            // the six points of order 3 of the cell, once per tile instead of once per pair: the FMA chains of eval_struct6, rows (side a)
+            // in the packed order of tt_tab, columns (side b) in the orbit order of the rule block.  A wave holds cells of one side.
+            if (pt_staged) {
+                double cv[NC];
+#pragma unroll
+                for (int k = 0; k < NC; k++) cv[k] = P.cellv[(size_t)k*P.ncp+c];
+                auto points = [&](auto sd, pnl_const_f64_ptr coef, int cst) {
+#pragma unroll
+                    for (int p = 0; p < 6; p++)
+#pragma unroll
+                        for (int d = 0; d < DIM; d++) {
+                            double s = 0.;
+#pragma unroll
+                            for (int k = 0; k < NV; k++) s = __builtin_fma(coef[p*cst+k], cv[k*DIM+d], s);
+                            s_dbl[S::o_pt(decltype(sd)::value, p, d)+l] = s;
+                        }
+                };
+                if (__builtin_amdgcn_readfirstlane(side) == 0)
+                    points(std::integral_constant<int, 0>{}, (pnl_const_f64_ptr)(unsigned long long)(P.tt_tab+(size_t)P.tt_off[3]*(4+DPE)), 4+DPE);
+                else points(std::integral_constant<int, 1>{}, (pnl_const_f64_ptr)(unsigned long long)(P.uni+P.uni_off[3]), 3);
+            }
+        }
     }
     if constexpr (LISTS) {
         // the record of the tile: header -> s_chunk[0 .. 2], the entries in use -> s_list (two 8-byte words per thread)
@@ -702,7 +897,8 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     const bool pipe = !symflush;
     if (pipe) {
         for (int t = tid; t < ((CLUSTER ? CT.chunk_stride : SO.nU)+1)*acc_stride; t += NT) s_acc[t] = 0.;
-        for (int t = tid; t < 2*TILE*ND; t += NT) s_D[t] = 0.;
+        if constexpr (LISTS) { for (int t = tid; t < 2*TILE*NR; t += NT) s_R[t] = 0.; }
+        else for (int t = tid; t < 2*TILE*ND; t += NT) s_D[t] = 0.;
         for (int t = tid; t < 2*(PNL_MAXQ+2)+4; t += NT) s_cnt[t] = 0;
         if ((int)blockIdx.x < ntiles) stage(blockIdx.x);
     }
@@ -715,7 +911,8 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     if (!pipe) {
         stage(tile_idx);
         for (int t = tid; t < (nA+1)*acc_stride; t += NT) s_acc[t] = 0.;
-        for (int t = tid; t < 2*TILE*ND; t += NT) s_D[t] = 0.;
+        if constexpr (LISTS) { for (int t = tid; t < 2*TILE*NR; t += NT) s_R[t] = 0.; }
+        else for (int t = tid; t < 2*TILE*ND; t += NT) s_D[t] = 0.;
         for (int t = tid; t < 2*(PNL_MAXQ+2)+4; t += NT) s_cnt[t] = 0;    // s_cnt, s_cur and s_misc are adjacent
     }
     lds_barrier();
@@ -1038,6 +1235,51 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
             p = (int)s_list[act ? idx : 0] & 4095;
         }
         const int j = p%TILE, i = (p/TILE+PNL_DIAG_MULT*j)%TILE;
+        if constexpr (LISTS) {
+            // the cross block as below; of the diagonal blocks only the sums vv r_i -> s_R[0][i], vv c_j -> s_R[1][j] at the points of
+            // the order (the flush forms the entries).  The plan keeps lists only where the orders 2, 3, 4 have 3, 6, 6 points.
+            const int nq = __builtin_amdgcn_readfirstlane(s_ttn[q]), to = __builtin_amdgcn_readfirstlane(s_tto[q]);
+            const bool strct = ((P.mix_struct >> q) & 1) != 0, staged = pt_staged && q == 3;
+            double av[NC], bv[NC];
+            if (!staged) {
+#pragma unroll
+                for (int k = 0; k < NC; k++) { av[k] = s_v[(0*NC+k)*TILE+i]; bv[k] = s_v[(1*NC+k)*TILE+j]; }
+            }
+            const double vv = act ? 2.*s_vol[i]*s_vol[TILE+j]*kern_scale<KT>(P.k) : 0.;
+            double *Ra = s_R+(0*TILE+i)*NR+S::r_off(q), *Rb = s_R+(1*TILE+j)*NR+S::r_off(q);
+            PairAcc<DIM, DPE> R;
+            R.clear();
+            const pnl_const_f64_ptr rule = (pnl_const_f64_ptr)(unsigned long long)(P.uni+P.uni_off[q]);
+            if (nq == 6) {
+                double c[6];
+                if (strct) eval_struct6_sums<KTE, S, TILE>(P.k, rule, s_tt+to*(4+DPE), av, bv, s_dbl, staged, i, j, vv, act, Ra, R, c, lpow);
+                else eval_distant_fixed<DIM, DPE, KTE, 6, true>(P, s_tt+to*(4+DPE), P.tt_wphi+to*DPE, av, bv, R, lpow, vv, act, Ra, c);
+                if (act)
+#pragma unroll
+                    for (int jp = 0; jp < 6; jp++) lds_add_f64(Rb+jp, c[jp]);
+            } else {
+                double c[3];
+                if (strct) {
+                    double r[3];
+                    eval_struct3_sums<KTE>(P.k, rule, av, bv, vv, R, r, c, lpow);
+                    if (act)
+#pragma unroll
+                        for (int ip = 0; ip < 3; ip++) lds_add_f64(Ra+ip, r[ip]);
+                } else eval_distant_fixed<DIM, DPE, KTE, 3, true>(P, s_tt+to*(4+DPE), P.tt_wphi+to*DPE, av, bv, R, lpow, vv, act, Ra, c);
+                if (act)
+#pragma unroll
+                    for (int jp = 0; jp < 3; jp++) lds_add_f64(Rb+jp, c[jp]);
+            }
+            if (act) {
+#pragma unroll
+                for (int a = 0; a < DPE; a++) {
+                    const int sa = s_slot[(0*DPE+a)*TILE+i];
+#pragma unroll
+                    for (int b = 0; b < DPE; b++) lds_add_f64(&s_acc[sa*acc_stride+s_slot[(1*DPE+b)*TILE+j]], -vv*R.G[a][b]);
+                }
+            }
+            continue;
+        }
         double av[NC], bv[NC];
 #pragma unroll
         for (int k = 0; k < NC; k++) { av[k] = s_v[(0*NC+k)*TILE+i]; bv[k] = s_v[(1*NC+k)*TILE+j]; }
@@ -1099,6 +1341,29 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
     lds_barrier();
 
     // ---- flush: sub-block of A' (rows = DoFs of block a, cols = DoFs of block b) and diagonal blocks ----
+    // LISTS: the six entries of a cell's diagonal block from its sums, D[e] = sum_k (w phi_a phi_b)[side][e][k] s_R[side][cell][k]; one
+    // thread per (side, cell) of the last two waves (the first two stage the next tile) reads and zeroes the sums of its cell
+    auto flush_R = [&]() {
+        const int sc = tid-(NT-2*TILE);
+        if (sc >= 0) {
+            double *Rc = s_R+sc*NR;
+            double rs[NR];
+            bool any = false;
+#pragma unroll
+            for (int k = 0; k < NR; k++) { rs[k] = Rc[k]; Rc[k] = 0.; any = any || rs[k] != 0.; }
+            if (any) {
+                const int side = sc/TILE, c = (side ? tb : ta)*TILE+(sc-side*TILE);
+                const double *__restrict__ pp = s_PP+side*ND*NR;
+#pragma unroll
+                for (int e = 0; e < ND; e++) {
+                    double v = 0.;
+#pragma unroll
+                    for (int k = 0; k < NR; k++) v = __builtin_fma(pp[e*NR+k], rs[k], v);
+                    atomic_add_f64(&Dglob[(size_t)c*ND+e], v);
+                }
+            }
+        }
+    };
     if (pipe) {
         const int nx = s_tile_next;
         // diagonal blocks: read and zeroed; cluster tiles before the next tile's slots replace s_dslot
@@ -1145,7 +1410,8 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
                 }
             }
         }
-        if (!CLUSTER) flush_D();
+        if constexpr (LISTS) flush_R();
+        else if (!CLUSTER) flush_D();
     } else {
     const int *__restrict__ dofA = CLUSTER ? CT.chunk_dofs+(size_t)ta*CT.chunk_stride : P.blk_dofs+(size_t)ta*P.blk_stride;
     const int *__restrict__ dofB = CLUSTER ? CT.chunk_dofs+(size_t)tb*CT.chunk_stride : P.blk_dofs+(size_t)tb*P.blk_stride;
@@ -1182,6 +1448,8 @@ k_tile_distant(const DevProblem P, const int2 *__restrict__ tiles, double *__res
             const double v = s_acc[r*acc_stride+c];
             if (v != 0.) atomic_add_f64(&A[(long long)dofB[c]*ldA+dofA[r]], v);
         }
+    if constexpr (LISTS) flush_R();
+    else
     for (int t = tid; t < 2*TILE*ND; t += NT) {
         const double v = s_D[t];
         if (v != 0.) {

@@ -1355,14 +1355,21 @@ struct TilePlan {
 static int settled_wanted() { return pnl_tune("PNL_MIXED_UNSETTLED") ? 0 : 1; }
 // the option PNL_SETTLED_CODES (a product option, read when the plan is made): the plan keeps the codes of the settled tiles only, and
 // the tile kernel builds their pair lists from the codes in every assembly
-static int lists_wanted() { return pnl_tune("PNL_SETTLED_CODES") ? 0 : 1; }
+// Lists are also kept only where the rules of the orders 2, 3 and 4 have 3, 6 and 6 points: the kernel that reads the lists keeps one
+// sum per (cell, point) for the diagonal blocks, 3 + 6 + 6 = TileSmem::NR of them (k_tile_distant<.., LISTS>, pnl_kernels.h).
+static int lists_wanted(const pnl_context *ctx) {
+    if (pnl_tune("PNL_SETTLED_CODES")) return 0;
+    for (int q = 2; q <= 4 && q <= ctx->qmax; q++)
+        if ((size_t)q+1 >= ctx->rule_off.size() || ctx->rule_off[q+1]-ctx->rule_off[q] != (q == 2 ? 3 : 6)) return 0;
+    return 1;
+}
 
 // repeated assemblies of the same work list keep it resident
 static bool tiles_resident(const pnl_context *ctx, const std::vector<int2> &tiles, const TilePlan &R) {
     const std::vector<pnl_order_formula> &forms = R.forms;
     return tiles.size() == ctx->tiles_cached.size() && ctx->b_tiles.p && ctx->tiles_cb == R.cell_begin && ctx->tiles_ce == R.cell_end &&
         forms.size() == ctx->tiles_forms.size() && std::memcmp(forms.data(), ctx->tiles_forms.data(), sizeof(pnl_order_formula)*R.ncls) == 0 &&
-        ctx->tiles_filter == ctx->run.tile_cell_filter && ctx->settled_want == settled_wanted() && ctx->lists_want == lists_wanted() &&
+        ctx->tiles_filter == ctx->run.tile_cell_filter && ctx->settled_want == settled_wanted() && ctx->lists_want == lists_wanted(ctx) &&
         (tiles.empty() || std::memcmp(tiles.data(), ctx->tiles_cached.data(), tiles.size()*sizeof(int2)) == 0);
 }
 
@@ -1583,7 +1590,7 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
         mixed[k].insert(mixed[k].end(), settled.begin(), settled.end());
     }
     if (settled.empty()) ctx->b_codes.release();
-    if (settled.empty() || !lists_wanted()) ctx->b_lists.release();
+    if (settled.empty() || !lists_wanted(ctx)) ctx->b_lists.release();
     ctx->settled_tiles.clear();
     std::vector<int2> all;
     ctx->single_launch = R.p2;
@@ -1605,7 +1612,7 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
         ctx->settled_tiles = settled;
         ctx->code_builds++;
         // the pair lists of these codes.  No device memory for them: the settled tiles stay settled and are taken by their codes
-        if (lists_wanted()) {
+        if (lists_wanted(ctx)) {
             if (ensure(ctx, ctx->b_lists, settled.size()*PNL_LIST_STRIDE*sizeof(unsigned short)) != PNL_OK) {
                 (void)hipGetLastError();
                 ctx->err.clear();
@@ -1615,7 +1622,7 @@ int pnl_upload_tiles(pnl_context *ctx, std::vector<int2> &tiles, int cell_begin,
         }
     }
     ctx->settled_want = settled_wanted();
-    ctx->lists_want = lists_wanted();
+    ctx->lists_want = lists_wanted(ctx);
     ctx->tiles_cached = tiles; ctx->tiles_cb = cell_begin; ctx->tiles_ce = cell_end; ctx->tiles_forms = R.forms;
     ctx->tiles_filter = ctx->run.tile_cell_filter;
     return PNL_OK;
