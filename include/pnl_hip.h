@@ -788,6 +788,60 @@ int pnl_cgb_refresh(pnl_context *ctx, int n, int nvec, const double *dinv_dev, c
                     double *R_dev, int64_t ldr, double *Z_dev, int64_t ldz, double *state_dev);
 int pnl_cgb_direction(pnl_context *ctx, int n, int nvec, const double *Z_dev, int64_t ldz, double *P_dev, int64_t ldp, double tol,
                       double *state_dev);
+/* The same loop for a preconditioner that the caller applies between the steps, Z = M^-1 R on whole blocks (a multigrid cycle:
+ * pnl_mg_cg_block is these calls around pnl_gemv_block and pnl_mg_cycle_block).  Blocks, state, partial sums, grid rule and validation
+ * as above; the convergence measure is conv = sqrt(|R . Z|), as pnl_mg_cg takes it:
+ *   pnl_cgb_residual   R = B - AX (AX_dev NULL: R = B).  state_dev NULL: every column v < nvec (the start, before there is a state);
+ *                      else the active columns (the recomputation every 50 iterations).  The state is only read.
+ *   pnl_cgb_start      with Z = M^-1 R of every column: P = Z, betaOld = beta = R . Z, conv, active = conv > tol and beta != 0; writes the
+ *                      whole state of the columns v < nvec
+ *   pnl_cgb_step       active columns: alpha = betaOld / (P . AP) (p . Ap goes to slot [1]); X += alpha P; R -= alpha AP
+ *   pnl_cgb_beta       active columns, with Z = M^-1 R: beta = R . Z; conv = sqrt(|beta|)
+ *   pnl_cgb_direction  as above
+ * A pass of the loop is: AP = A P; step; every 50th pass AX = A X and residual; Z = M^-1 R; beta; direction; read the state.  The
+ * preconditioner may run on every column: the Z of a column that is not active is not read.  Columns that are not active are neither
+ * read nor written by these calls.  Asynchronous on the context's stream. */
+int pnl_cgb_residual(pnl_context *ctx, int n, int nvec, const double *B_dev, int64_t ldb, const double *AX_dev, int64_t ldax, double *R_dev,
+                     int64_t ldr, const double *state_dev);
+int pnl_cgb_start(pnl_context *ctx, int n, int nvec, const double *R_dev, int64_t ldr, const double *Z_dev, int64_t ldz, double *P_dev, int64_t ldp,
+                  double tol, double *state_dev);
+int pnl_cgb_step(pnl_context *ctx, int n, int nvec, const double *P_dev, int64_t ldp, const double *AP_dev, int64_t ldap, double *X_dev, int64_t ldx,
+                 double *R_dev, int64_t ldr, double *state_dev);
+int pnl_cgb_beta(pnl_context *ctx, int n, int nvec, const double *R_dev, int64_t ldr, const double *Z_dev, int64_t ldz, double *state_dev);
+
+/* ---- multigrid for a block of right-hand sides (csrc/pnl_mg_block.hip): the cycle of pnl_mg_cycle and the loop of pnl_mg_cg for several
+ *      right-hand sides on one hierarchy. -----------------------------------------------------------------------------------------------
+ * Columns are stored one per row as in pnl_gemv_block: column v is B_dev[v*ldb .. v*ldb + n), its result X_dev[v*ldx .. v*ldx + n), n the
+ * size of the finest level.  The columns are processed in groups of at most 16; a group shares every pass over an operator.  Every level
+ * of the hierarchy must be dense (kind 0 or 2; both are read in full by pnl_gemv_block, no half-read of a symmetric level): a hierarchy
+ * whose finest level is an H2 operator (kind 1) is refused with PNL_ERR_INVALID.  The level blocks ([16][n_l] for rhs, sol and temp) are
+ * allocated by the first block call on the hierarchy, not by pnl_mg_create.  No floating-point atomics: the residuals and the coarse solve
+ * are pnl_gemv_block launches, the damped-Jacobi update and the transfer operators give one thread one row of the block and loop over the
+ * columns (sums in ascending order of the stored entries), the dot products are those of the pnl_cgb_* steps.  The bits of column v --
+ * X[v], iters[v], residuals[v] -- therefore depend neither on the number of columns nor on the position v nor on the other columns, and
+ * two calls repeat bit for bit.  They are not the bits of pnl_mg_cycle / pnl_mg_cg, which sum in another order.  The padding of B and X
+ * (ld > n) is neither read into a sum nor written.
+ *
+ * pnl_mg_cycle_block: one V cycle (solveOnLevel) on the finest level for nvec >= 1 columns.  x_is_zero: X counts as zero whatever it
+ * holds (it is not read), the first residual is B; else X holds the iterates.  Asynchronous on the context's stream, no host
+ * synchronisation inside.  PNL_ERR_INVALID, before any launch, for a null mg, B or X; nvec < 1; ldb or ldx < n; B_dev == X_dev; an H2
+ * finest level.
+ *
+ * pnl_mg_cg_block: pnl_mg_cg for nrhs columns; A_dev NULL: the finest operator of the hierarchy, else a dense row-major n x n operator
+ * (symmetric positive definite, read in full).  Every column runs the recurrence of pnl_mg_cg on its OWN (its own alpha, beta and
+ * convergence on sqrt(|r . M^-1 r|) <= tol, M^-1 = one V cycle from a zero guess); per iteration and group the columns share one
+ * pnl_gemv_block for A P and one pnl_mg_cycle_block for Z.  A column that has converged is FROZEN (its x, r and reported residual are no
+ * longer written; the cycle still carries it along), one whose r . M^-1 r is 0 at the start is frozen at once with 0 iterations and
+ * residual 0.  Iteration counts as pnl_mg_cg: a column that converges in the first pass reports 0, one that never converges maxiter.
+ * The residual is recomputed from b - A x when the counter reaches 50, for the active columns of the group.  More than 16 columns are
+ * taken as consecutive groups, each with a loop of its own.  x_is_zero: the caller states that X holds zeros (as for pnl_mg_cg), R = B
+ * without a product; else X holds the initial guesses.  maxiter = 0 leaves X untouched and reports the initial conv.  iters[nrhs] and
+ * residuals[nrhs] (the final conv) on the host, either may be NULL.  Synchronous: the host reads the state of the group back once per
+ * iteration.  PNL_ERR_INVALID, before any launch, for a null mg, B or X; nrhs < 1; ldb or ldx < n; ldA < n with a given A; maxiter < 0;
+ * B_dev == X_dev; an H2 finest level. */
+int pnl_mg_cycle_block(pnl_mg *mg, int nvec, const double *B_dev, int64_t ldb, double *X_dev, int64_t ldx, int x_is_zero);
+int pnl_mg_cg_block(pnl_mg *mg, const double *A_dev, int64_t ldA, int nrhs, const double *B_dev, int64_t ldb, double *X_dev, int64_t ldx,
+                    double tol, int maxiter, int x_is_zero, int *iters, double *residuals);
 
 #ifdef __cplusplus
 }

@@ -36,7 +36,8 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_csr_cg_jacobi', 'pnl_fe_space_create', 'pnl_fe_space_destroy', 'pnl_assemble_nonlinearity', 'pnl_imex_create',
            'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi', 'pnl_gemv_block', 'pnl_spmv_block', 'pnl_uniform_lane_layout',
            'pnl_h2_matvec_block', 'pnl_h2_upward_block', 'pnl_h2_interact_block', 'pnl_h2_downward_block',
-           'pnl_cg_jacobi_block', 'pnl_cgb_init', 'pnl_cgb_update', 'pnl_cgb_refresh', 'pnl_cgb_direction']
+           'pnl_cg_jacobi_block', 'pnl_cgb_init', 'pnl_cgb_update', 'pnl_cgb_refresh', 'pnl_cgb_direction',
+           'pnl_cgb_residual', 'pnl_cgb_start', 'pnl_cgb_step', 'pnl_cgb_beta', 'pnl_mg_cycle_block', 'pnl_mg_cg_block']
 
 PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
 PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
@@ -221,6 +222,12 @@ def load():
     L.pnl_cgb_update.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.pnl_cgb_refresh.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.pnl_cgb_direction.argtypes = [vp, i32, i32, vp, i64, vp, i64, dbl, vp]
+    L.pnl_cgb_residual.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp, i64, vp]
+    L.pnl_cgb_start.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp, i64, dbl, vp]
+    L.pnl_cgb_step.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.pnl_cgb_beta.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp]
+    L.pnl_mg_cycle_block.argtypes = [vp, i32, vp, i64, vp, i64, i32]
+    L.pnl_mg_cg_block.argtypes = [vp, vp, i64, i32, vp, i64, vp, i64, dbl, i32, i32, vp, vp]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
     L.pnl_upload_sparsity_device.argtypes = [vp, i32, vp, vp]
     L.pnl_set_classes.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -738,6 +745,25 @@ class Context:
         """active columns: frozen where conv <= tol, else P = Z + (beta / betaOld) P and betaOld = beta"""
         self.check(self.L.pnl_cgb_direction(self.h, int(n), int(nvec), _vp(Z_ptr), int(ldz), _vp(P_ptr), int(ldp), float(tol), _vp(state_ptr)))
 
+    # the same loop around a preconditioner that the caller applies between the steps (a multigrid cycle)
+    def cgb_residual(self, n, nvec, B_ptr, ldb, AX_ptr, ldax, R_ptr, ldr, state_ptr):
+        """R = B - AX (AX_ptr 0: R = B); state_ptr 0: every column, else the active ones"""
+        self.check(self.L.pnl_cgb_residual(self.h, int(n), int(nvec), _vp(B_ptr), int(ldb), _vp(AX_ptr), int(ldax), _vp(R_ptr), int(ldr), _vp(state_ptr)))
+
+    def cgb_start(self, n, nvec, R_ptr, ldr, Z_ptr, ldz, P_ptr, ldp, tol, state_ptr):
+        """P = Z, betaOld = beta = R.Z, conv = sqrt(|beta|), active: the state of every column"""
+        self.check(self.L.pnl_cgb_start(self.h, int(n), int(nvec), _vp(R_ptr), int(ldr), _vp(Z_ptr), int(ldz), _vp(P_ptr), int(ldp), float(tol),
+                                        _vp(state_ptr)))
+
+    def cgb_step(self, n, nvec, P_ptr, ldp, AP_ptr, ldap, X_ptr, ldx, R_ptr, ldr, state_ptr):
+        """active columns: alpha = betaOld / P.AP, X += alpha P, R -= alpha AP"""
+        self.check(self.L.pnl_cgb_step(self.h, int(n), int(nvec), _vp(P_ptr), int(ldp), _vp(AP_ptr), int(ldap), _vp(X_ptr), int(ldx), _vp(R_ptr), int(ldr),
+                                       _vp(state_ptr)))
+
+    def cgb_beta(self, n, nvec, R_ptr, ldr, Z_ptr, ldz, state_ptr):
+        """active columns: beta = R.Z, conv = sqrt(|beta|)"""
+        self.check(self.L.pnl_cgb_beta(self.h, int(n), int(nvec), _vp(R_ptr), int(ldr), _vp(Z_ptr), int(ldz), _vp(state_ptr)))
+
     def h2_matvec_block(self, nvec, X_ptr, ldx, Y_ptr, ldy):
         """Y[v] += far field of X[v] for the H2 operator set up in the context, without float atomics (pnl_h2_block.hip)"""
         self.check(self.L.pnl_h2_matvec_block(self.h, int(nvec), C.c_void_p(X_ptr) if X_ptr else None, int(ldx),
@@ -776,6 +802,17 @@ class Context:
         while len(out) > 1 and out[-1] != out[-1]:
             out.pop()
         return it.value, out
+
+    def mg_cycle_block(self, mg, nvec, B_ptr, ldb, X_ptr, ldx, x_is_zero):
+        """one V cycle for nvec columns (column v at B[v*ldb .. v*ldb + n)), groups of 16 sharing every pass over the operators"""
+        self.check(self.L.pnl_mg_cycle_block(mg, int(nvec), _vp(B_ptr), int(ldb), _vp(X_ptr), int(ldx), int(bool(x_is_zero))))
+
+    def mg_cg_block(self, mg, A_ptr, ldA, nrhs, B_ptr, ldb, X_ptr, ldx, tol, maxiter, x_is_zero):
+        """pnl_mg_cg for nrhs columns, every column its own recurrence; returns (iterations [nrhs] int32, final conv [nrhs])"""
+        its, res = np.zeros(max(int(nrhs), 1), dtype=np.int32), np.zeros(max(int(nrhs), 1))
+        self.check(self.L.pnl_mg_cg_block(mg, _vp(A_ptr), int(ldA), int(nrhs), _vp(B_ptr), int(ldb), _vp(X_ptr), int(ldx), float(tol), int(maxiter),
+                                          int(bool(x_is_zero)), its.ctypes.data, res.ctypes.data))
+        return its, res
 
     def theta_step(self, mg, S_ptr, ldS, M_indptr_ptr, M_indices_ptr, M_data_ptr, dt, theta, forcing_ptr, u_ptr, tol, maxiter):
         it, res = C.c_int(0), C.c_double(0.)

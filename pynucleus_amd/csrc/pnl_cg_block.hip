@@ -19,6 +19,12 @@
 //   k_cgb_finish     one workgroup: adds the partials of part[1] and writes beta and conv (at the start: betaOld, conv, active)
 //   k_cgb_direction  p = z + (beta / betaOld) p for the columns that go on
 //   k_cgb_advance    one workgroup: betaOld = beta, or active = 0 where conv <= tol
+// For a preconditioner that is applied between the calls (a multigrid cycle: pnl_mg_cg_block, pnl_mg_block.hip) the fused kernels are
+// split, on the same partial sums, grid rule and state (pnl_cgb_residual / _start / _step / _beta):
+//   k_cgb_r          r = b - Ax
+//   k_cgb_rz         partial sums of r . z (at the start: p = z as well)                                      -> part[1][wg][16]
+//   k_cgb_xr         as k_cgb_update up to r -= alpha Ap; no z, no sums
+//   k_cgb_finish     with conv = sqrt(|r . z|), as pnl_mg_cg takes it
 // The scalars stay on the device (state: PNL_CGB_STATE doubles per column); the driver reads the state back once per iteration.
 //
 // No floating-point atomics.  A dot product is summed in a fixed shape that depends on n only: per thread in ascending i (fma), the
@@ -162,7 +168,8 @@ k_cgb_residual(int n, int nv, const double *__restrict__ dinv, const double *__r
 
 // one workgroup.  START: betaOld = beta = r . p, conv, active = conv > tol (a zero residual is never active: no 0 / 0 later);
 // else, for the active columns, beta = r . z and conv
-template <bool START>
+// ABS (the external-preconditioner steps): conv = sqrt(|r . z|), as pnl_mg_cg takes it
+template <bool START, bool ABS = false>
 __global__ void __launch_bounds__(CGB_THREADS)
 k_cgb_finish(int nb, int nv, const double *__restrict__ part, double tol, double *state) {
     __shared__ double tot[CGB_NV];
@@ -170,7 +177,7 @@ k_cgb_finish(int nb, int nv, const double *__restrict__ part, double tol, double
     const int v = threadIdx.x;
     if (v >= nv) return;
     double *st = state+v*PNL_CGB_STATE;
-    const double conv = sqrt(tot[v]);
+    const double conv = sqrt(ABS ? fabs(tot[v]) : tot[v]);
     if (START) {
         st[ST_BETA_OLD] = tot[v]; st[ST_PAP] = 0.; st[ST_BETA] = tot[v]; st[ST_CONV] = conv;
         st[ST_ACTIVE] = (conv > tol && tot[v] != 0.) ? 1. : 0.;
@@ -211,6 +218,68 @@ __global__ void k_cgb_advance(int nv, double tol, double *state) {
     else st[ST_BETA_OLD] = st[ST_BETA];
 }
 
+// ---- the steps for a preconditioner that is applied between the calls (pnl_cgb_residual / _start / _step / _beta) -------------------
+// r = b - Ax (AX == nullptr: r = b).  ALL: every column v < nv (the start: there is no state yet); else the active ones
+template <bool ALL>
+__global__ void __launch_bounds__(CGB_THREADS)
+k_cgb_r(int n, int nv, const double *__restrict__ B, long long ldb, const double *__restrict__ AX, long long ldax, double *__restrict__ R,
+        long long ldr, const double *__restrict__ state) {
+    const unsigned mask = ALL ? (1u << nv)-1u : cgb_active_mask(state, nv);
+    for (int i = blockIdx.x*CGB_THREADS+threadIdx.x; i < n; i += gridDim.x*CGB_THREADS) {
+#pragma unroll
+        for (int v = 0; v < CGB_NV; v++)
+            if ((mask >> v) & 1) R[v*ldr+i] = AX ? B[v*ldb+i]-AX[v*ldax+i] : B[v*ldb+i];
+    }
+}
+
+// partial sums of r . z.  START: every column v < nv, and p = z; else the active columns
+template <bool START>
+__global__ void __launch_bounds__(CGB_THREADS)
+k_cgb_rz(int n, int nv, const double *__restrict__ R, long long ldr, const double *__restrict__ Z, long long ldz, double *__restrict__ P,
+         long long ldp, const double *__restrict__ state, double *__restrict__ part) {
+    const unsigned mask = START ? (1u << nv)-1u : cgb_active_mask(state, nv);
+    double s[CGB_NV];
+#pragma unroll
+    for (int v = 0; v < CGB_NV; v++) s[v] = 0.;
+    for (int i = blockIdx.x*CGB_THREADS+threadIdx.x; i < n; i += gridDim.x*CGB_THREADS) {
+#pragma unroll
+        for (int v = 0; v < CGB_NV; v++) {
+            if ((mask >> v) & 1) {
+                const double zi = Z[v*ldz+i];
+                if (START) P[v*ldp+i] = zi;
+                s[v] = __builtin_fma(R[v*ldr+i], zi, s[v]);
+            }
+        }
+    }
+    cgb_block_sums(s, mask, part+(size_t)blockIdx.x*CGB_NV);
+}
+
+// k_cgb_update without the preconditioner: alpha = betaOld / p.Ap from the partials, x += alpha p, r -= alpha Ap
+__global__ void __launch_bounds__(CGB_THREADS)
+k_cgb_xr(int n, int nv, const double *__restrict__ P, long long ldp, const double *__restrict__ AP, long long ldap, double *__restrict__ X,
+         long long ldx, double *__restrict__ R, long long ldr, double *state, const double *__restrict__ part_pap) {
+    __shared__ double tot[CGB_NV], al[CGB_NV];
+    const unsigned mask = cgb_active_mask(state, nv);
+    cgb_totals(part_pap, (int)gridDim.x, tot);
+    if (threadIdx.x < CGB_NV) {
+        const int v = threadIdx.x;
+        const bool on = (mask >> v) & 1;
+        al[v] = on ? state[v*PNL_CGB_STATE+ST_BETA_OLD]/tot[v] : 0.;
+        if (on && blockIdx.x == 0) state[v*PNL_CGB_STATE+ST_PAP] = tot[v];       // a slot that no workgroup of this launch reads
+    }
+    __syncthreads();
+    for (int i = blockIdx.x*CGB_THREADS+threadIdx.x; i < n; i += gridDim.x*CGB_THREADS) {
+#pragma unroll
+        for (int v = 0; v < CGB_NV; v++) {
+            if ((mask >> v) & 1) {
+                const double alpha = al[v];
+                X[v*ldx+i] = __builtin_fma(alpha, P[v*ldp+i], X[v*ldx+i]);
+                R[v*ldr+i] = __builtin_fma(-alpha, AP[v*ldap+i], R[v*ldr+i]);
+            }
+        }
+    }
+}
+
 // the context's scratch for the partial sums: [2][CGB_MAXBLK][16]
 int cgb_part(pnl_context *ctx, double **part) {
     if (int rc = ensure(ctx, ctx->b_cgb_part, sizeof(double)*2*CGB_PART)) return rc;
@@ -221,6 +290,14 @@ int cgb_part(pnl_context *ctx, double **part) {
 int cgb_finish(pnl_context *ctx, bool start, int n, int nv, const double *part, double tol, double *state) {
     if (start) hipLaunchKernelGGL((k_cgb_finish<true>), dim3(1), dim3(CGB_THREADS), 0, ctx->stream, cgb_blocks(n), nv, part, tol, state);
     else hipLaunchKernelGGL((k_cgb_finish<false>), dim3(1), dim3(CGB_THREADS), 0, ctx->stream, cgb_blocks(n), nv, part, tol, state);
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+
+// the same with conv = sqrt(|r . z|)
+int cgb_finish_abs(pnl_context *ctx, bool start, int n, int nv, const double *part, double tol, double *state) {
+    if (start) hipLaunchKernelGGL((k_cgb_finish<true, true>), dim3(1), dim3(CGB_THREADS), 0, ctx->stream, cgb_blocks(n), nv, part, tol, state);
+    else hipLaunchKernelGGL((k_cgb_finish<false, true>), dim3(1), dim3(CGB_THREADS), 0, ctx->stream, cgb_blocks(n), nv, part, tol, state);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
@@ -286,6 +363,63 @@ int pnl_cgb_direction(pnl_context *ctx, int n, int nvec, const double *Z_dev, in
     hipLaunchKernelGGL(k_cgb_advance, dim3(1), dim3(64), 0, ctx->stream, nvec, tol, state_dev);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
+}
+
+int pnl_cgb_residual(pnl_context *ctx, int n, int nvec, const double *B_dev, int64_t ldb, const double *AX_dev, int64_t ldax, double *R_dev,
+                     int64_t ldr, const double *state_dev) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (n < 1 || nvec < 1 || nvec > CGB_NV || cgb_bad_block(B_dev, ldb, n) || cgb_bad_block(R_dev, ldr, n) || (AX_dev && ldax < n) || B_dev == R_dev ||
+        AX_dev == R_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cgb_residual: bad arguments (n=%d nvec=%d)", n, nvec);
+    if (state_dev) hipLaunchKernelGGL((k_cgb_r<false>), dim3(cgb_blocks(n)), dim3(CGB_THREADS), 0, ctx->stream, n, nvec, B_dev, (long long)ldb, AX_dev,
+                                      (long long)ldax, R_dev, (long long)ldr, state_dev);
+    else hipLaunchKernelGGL((k_cgb_r<true>), dim3(cgb_blocks(n)), dim3(CGB_THREADS), 0, ctx->stream, n, nvec, B_dev, (long long)ldb, AX_dev,
+                            (long long)ldax, R_dev, (long long)ldr, state_dev);
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+
+int pnl_cgb_start(pnl_context *ctx, int n, int nvec, const double *R_dev, int64_t ldr, const double *Z_dev, int64_t ldz, double *P_dev, int64_t ldp,
+                  double tol, double *state_dev) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (n < 1 || nvec < 1 || nvec > CGB_NV || cgb_bad_block(R_dev, ldr, n) || cgb_bad_block(Z_dev, ldz, n) || cgb_bad_block(P_dev, ldp, n) ||
+        !state_dev || R_dev == P_dev || Z_dev == P_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cgb_start: bad arguments (n=%d nvec=%d)", n, nvec);
+    double *part;
+    if (int rc = cgb_part(ctx, &part)) return rc;
+    hipLaunchKernelGGL((k_cgb_rz<true>), dim3(cgb_blocks(n)), dim3(CGB_THREADS), 0, ctx->stream, n, nvec, R_dev, (long long)ldr, Z_dev, (long long)ldz,
+                       P_dev, (long long)ldp, (const double*)state_dev, part+CGB_PART);
+    HIPCHK(ctx, hipGetLastError());
+    return cgb_finish_abs(ctx, true, n, nvec, part+CGB_PART, tol, state_dev);
+}
+
+int pnl_cgb_step(pnl_context *ctx, int n, int nvec, const double *P_dev, int64_t ldp, const double *AP_dev, int64_t ldap, double *X_dev, int64_t ldx,
+                 double *R_dev, int64_t ldr, double *state_dev) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (n < 1 || nvec < 1 || nvec > CGB_NV || cgb_bad_block(P_dev, ldp, n) || cgb_bad_block(AP_dev, ldap, n) || cgb_bad_block(X_dev, ldx, n) ||
+        cgb_bad_block(R_dev, ldr, n) || !state_dev || X_dev == R_dev || P_dev == X_dev || P_dev == R_dev || AP_dev == X_dev || AP_dev == R_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cgb_step: bad arguments (n=%d nvec=%d)", n, nvec);
+    double *part;
+    if (int rc = cgb_part(ctx, &part)) return rc;
+    const dim3 grid(cgb_blocks(n));
+    hipLaunchKernelGGL(k_cgb_pap, grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, P_dev, (long long)ldp, AP_dev, (long long)ldap,
+                       (const double*)state_dev, part);
+    hipLaunchKernelGGL(k_cgb_xr, grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, P_dev, (long long)ldp, AP_dev, (long long)ldap, X_dev, (long long)ldx,
+                       R_dev, (long long)ldr, state_dev, (const double*)part);
+    HIPCHK(ctx, hipGetLastError());
+    return PNL_OK;
+}
+
+int pnl_cgb_beta(pnl_context *ctx, int n, int nvec, const double *R_dev, int64_t ldr, const double *Z_dev, int64_t ldz, double *state_dev) {
+    if (!ctx) return PNL_ERR_INVALID;
+    if (n < 1 || nvec < 1 || nvec > CGB_NV || cgb_bad_block(R_dev, ldr, n) || cgb_bad_block(Z_dev, ldz, n) || !state_dev)
+        return fail(ctx, PNL_ERR_INVALID, "pnl_cgb_beta: bad arguments (n=%d nvec=%d)", n, nvec);
+    double *part;
+    if (int rc = cgb_part(ctx, &part)) return rc;
+    hipLaunchKernelGGL((k_cgb_rz<false>), dim3(cgb_blocks(n)), dim3(CGB_THREADS), 0, ctx->stream, n, nvec, R_dev, (long long)ldr, Z_dev, (long long)ldz,
+                       (double*)nullptr, 0ll, (const double*)state_dev, part+CGB_PART);
+    HIPCHK(ctx, hipGetLastError());
+    return cgb_finish_abs(ctx, false, n, nvec, part+CGB_PART, 0., state_dev);
 }
 
 int pnl_cg_jacobi_block(pnl_context *ctx, const double *A_dev, int64_t ldA, int n, int nrhs, const double *B_dev, int64_t ldb, double *X_dev,

@@ -21,19 +21,7 @@
 // run as a fixed sequence of small launches on the context's stream, no host synchronisation inside a cycle.
 #include "pnl_context.h"
 #include "pnl_common.h"
-
-struct pnl_mg {
-    pnl_context *ctx = nullptr;
-    int nlevels = 0;
-    std::vector<pnl_mg_level_desc> lv;
-    const double *coarse_inv = nullptr;
-    double omega = 2./3.;
-    int pre = 1, post = 1;
-    // per level: invD (omega / diag), rhs, sol, temp
-    std::vector<DevBuf> invD, rhs, sol, temp;
-    DevBuf r, p, Ap, z, scal, work, h2tmp;
-    double last_conv = 0.;          // preconditioned residual norm sqrt(r.Br) at the end of the last pnl_mg_cg
-};
+#include "pnl_mg.h"                 // struct pnl_mg
 
 // ---- near-field matvec (pnl_spmv): CSR_LinearOperator / SSS_LinearOperator matvec (CSR_LinearOperator_{SCALAR}.pxi:259-284,
 // SSS_LinearOperator_{SCALAR}.pxi:146-176).  One wave per row; SSS adds the mirrored entries with atomics.

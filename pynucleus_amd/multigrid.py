@@ -12,7 +12,7 @@ Host-side mirror of
     ``discretizedTransientProblem`` (nl/PyNucleus_nl/discretizedProblems.py:722-905).
 
 The cycle, the CG loop and the time step run inside libpnl_hip.so (csrc/pnl_solver.hip: pnl_mg_cycle, pnl_mg_solve,
-pnl_mg_cg, pnl_theta_step); this module builds the hierarchy, keeps the level data alive in HBM and hands pointers over.
+pnl_mg_cg, pnl_theta_step; csrc/pnl_mg_block.hip: pnl_mg_cycle_block, pnl_mg_cg_block for a 2-D block of right-hand sides); this module builds the hierarchy, keeps the level data alive in HBM and hands pointers over.
 No CPU fallback: without the HIP library / a GPU the constructors raise.
 """
 import numpy as np
@@ -183,6 +183,11 @@ def buildTransientHierarchy(levels, alpha, beta):
 
 
 # ---- multigrid --------------------------------------------------------------------------------------------------------
+def _is_block(b):
+    """a 2-D right-hand side [nrhs, n], numpy or torch"""
+    return (b.ndim if hasattr(b, 'ndim') else np.ndim(b)) == 2
+
+
 class multigrid:
     """multigrid(hierarchy, smoother=('jacobi', {'omega': 2/3})) like the reference's solver class; ``hierarchy`` is a
     fractionalHierarchy or a list of level dicts with 'A' (Dense_LinearOperator), 'R', 'P'."""
@@ -384,8 +389,11 @@ class multigrid:
         return xd if isinstance(like, torch.Tensor) else xd.cpu().numpy()
 
     def cycle(self, b, x=None):
-        """one V cycle (solveOnLevel on the finest level); returns the new iterate"""
+        """one V cycle (solveOnLevel on the finest level); returns the new iterate.  A 2-D b [nrhs, n] is a block of right-hand sides: one
+        cycle for all rows, 16 of them per pass over the operators (pnl_mg_cycle_block)"""
         import torch
+        if _is_block(b):
+            return self._cycle_block(b, x)
         bd = self._vec(b)
         zero = x is None
         xd = torch.zeros_like(bd) if zero else self._vec(x).clone()
@@ -420,8 +428,12 @@ class multigrid:
         return self._ret(b, xd), its, res
 
     def cg(self, b, x=None, tol=1e-8, maxiter=100, A=None):
-        """CG on A (default: the finest operator) preconditioned by one V cycle: (x, iterations, sqrt(r.Br) history)"""
+        """CG on A (default: the finest operator) preconditioned by one V cycle: (x, iterations, sqrt(r.Br) history).  A 2-D b [nrhs, n]
+        is a block of right-hand sides, every row its own recurrence (pnl_mg_cg_block): (X, iterations per row, final sqrt(r.Br) per row),
+        what solvers.cg_multi returns"""
         import torch
+        if _is_block(b):
+            return self._cg_block(b, x, tol, maxiter, A)
         bd = self._vec(b)
         zero = x is None
         if not self._native:
@@ -444,7 +456,56 @@ class multigrid:
             for _ in range(maxIter-1):
                 z = self.cycle(r, z)
             return z
+        B.multigrid, B.maxIter = self, maxIter            # solvers.cg_multi takes the block cycle of this hierarchy
         return B
+
+    # -- blocks of right-hand sides (pnl_mg_block.hip) --------------------------------------------------------------------------
+    def _require_block(self):
+        """the block cycle runs inside the library on dense levels with the Jacobi smoother"""
+        if self.smootherType != 'jacobi':
+            raise NotImplementedError('multigrid on a block of right-hand sides: the Chebyshev smoother on blocks is not built')
+        if not self._native:
+            raise NotImplementedError('multigrid on a block of right-hand sides: the generic (Python-driven) cycle over H2 / sparse levels '
+                                      'has no block form; every level must be dense')
+        if self._h2_top is not None:
+            raise NotImplementedError('multigrid on a block of right-hand sides: a block cycle with an H2 operator on the finest level is not built')
+
+    def _blocks(self, B, X):
+        import torch
+        from .linear_operators import _as_block
+        Bd = _as_block(B, self.device)
+        nrhs, n = Bd.shape
+        assert nrhs >= 1 and n == self.num_rows, (tuple(Bd.shape), self.num_rows)
+        Xd = torch.zeros((nrhs, n), dtype=torch.float64, device=self.device) if X is None else _as_block(X, self.device).clone(
+            memory_format=torch.contiguous_format)
+        assert Xd.shape == Bd.shape, (tuple(Xd.shape), tuple(Bd.shape))
+        return Bd, Xd, nrhs, n
+
+    def _cycle_block(self, B, X=None):
+        import torch
+        self._require_block()
+        Bd, Xd, nrhs, n = self._blocks(B, X)
+        torch.cuda.current_stream(self.device).synchronize()
+        self._set_stream()
+        self.ctx.mg_cycle_block(self._mg, nrhs, Bd.data_ptr(), max(int(Bd.stride(0)), n), Xd.data_ptr(), n, X is None)
+        self.ctx.synchronize()
+        return Xd if isinstance(B, torch.Tensor) else Xd.cpu().numpy()
+
+    def _cg_block(self, B, X=None, tol=1e-8, maxiter=100, A=None):
+        import torch
+        self._require_block()
+        if A is not None and not hasattr(A, 'A'):
+            # any operator with matvec_multi: the loop over the library's steps (solvers.cg_multi)
+            from .solvers import cg_multi
+            return cg_multi(A, B, X, tol, maxiter, preconditioner=self)
+        Bd, Xd, nrhs, n = self._blocks(B, X)
+        if A is not None:
+            assert A.num_rows == A.num_columns == n, (A.shape, n)
+        Aptr, ld = (A.A.data_ptr(), max(int(A.A.stride(0)), n)) if A is not None else (None, 0)
+        torch.cuda.current_stream(self.device).synchronize()
+        self._set_stream()
+        its, res = self.ctx.mg_cg_block(self._mg, Aptr, ld, nrhs, Bd.data_ptr(), max(int(Bd.stride(0)), n), Xd.data_ptr(), n, tol, maxiter, X is None)
+        return (Xd if isinstance(B, torch.Tensor) else Xd.cpu().numpy()), its, res
 
     def __str__(self):
         sm = ('Chebyshev (degree {})'.format(int(self.smootherParams.get('degree', 3))) if self.smootherType == 'chebyshev'

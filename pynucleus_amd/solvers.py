@@ -136,20 +136,87 @@ def _cg_group(A, ctx, dinv, B, X, have_x0, tol, maxiter, its, res):
     its[active] = maxiter
 
 
+def _cg_group_mg(A, ctx, cycle, B, X, have_x0, tol, maxiter, its, res):
+    """the loop of pnl_mg_cg_block (csrc/pnl_mg_block.hip) for at most 16 rows of B, with ``A.matvec_multi`` as the product, ``cycle``
+    (R [nv, n] -> Z, one V cycle from a zero guess for every row: multigrid.cycle on a block) as the preconditioner and the library's
+    external-preconditioner steps on device blocks; X [nv, n] contiguous holds the guesses and the results, its / res are filled"""
+    import torch
+    from ._lib import PNL_CGB_STATE
+    nv, n = B.shape
+    dev = B.device
+    R, P = (torch.empty((nv, n), dtype=torch.float64, device=dev) for _ in range(2))
+    state = torch.zeros(nv*PNL_CGB_STATE, dtype=torch.float64, device=dev)
+    ldb = max(int(B.stride(0)), n)
+
+    def product(V):
+        ctx.synchronize()
+        W = A.matvec_multi(V)
+        torch.cuda.current_stream(dev).synchronize()
+        return W
+
+    def precondition():
+        ctx.synchronize()
+        Z = cycle(R).contiguous()
+        torch.cuda.current_stream(dev).synchronize()
+        return Z
+
+    def read_state():
+        ctx.synchronize()
+        return state.cpu().numpy().reshape(nv, PNL_CGB_STATE)
+
+    AX = product(X) if have_x0 else None
+    torch.cuda.current_stream(dev).synchronize()
+    ctx.cgb_residual(n, nv, B.data_ptr(), ldb, AX.data_ptr() if AX is not None else 0, n, R.data_ptr(), n, 0)
+    Z = precondition()
+    ctx.cgb_start(n, nv, R.data_ptr(), n, Z.data_ptr(), n, P.data_ptr(), n, tol, state.data_ptr())
+    st = read_state()
+    res[:] = st[:, 3]
+    its[:] = 0
+    active = st[:, 4] != 0.
+    k = 0
+    for it in range(maxiter):
+        if not active.any():
+            break
+        AP = product(P)
+        ctx.cgb_step(n, nv, P.data_ptr(), n, AP.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, state.data_ptr())
+        if k == 50:
+            AX = product(X)                             # recalculate the residual to avoid rounding errors
+            ctx.cgb_residual(n, nv, B.data_ptr(), ldb, AX.data_ptr(), n, R.data_ptr(), n, state.data_ptr())
+            k = 0
+        Z = precondition()
+        ctx.cgb_beta(n, nv, R.data_ptr(), n, Z.data_ptr(), n, state.data_ptr())
+        ctx.cgb_direction(n, nv, Z.data_ptr(), n, P.data_ptr(), n, tol, state.data_ptr())
+        st = read_state()
+        res[active] = st[active, 3]
+        done = active & (st[:, 4] == 0.)
+        its[done] = it
+        active &= ~done
+        k += 1
+    its[active] = maxiter
+
+
 def cg_multi(A, B, X0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
     """Solve A X[v] = B[v] for the rows of a 2-D B [nrhs, n], A symmetric positive definite.  Every row runs the recurrence of ``cg``
     on its own (own step lengths, own convergence test sqrt(r.Br) <= tol, frozen once it has converged) and the rows share the
     operator product: one ``matvec_multi`` per iteration and 16 rows.  A symmetric Dense_LinearOperator on one GPU with the Jacobi
     preconditioner is one library call (pnl_cg_jacobi_block); any other operator with ``matvec_multi`` and ``diagonal`` (CSR, SSS, H2,
-    interpolated) runs the same loop here over the library's step calls.  ``preconditioner``: 'jacobi' or None (the unit diagonal).
+    interpolated) runs the same loop here over the library's step calls.  ``preconditioner``: 'jacobi', None (the unit diagonal), or a
+    ``multigrid`` object / its ``asPreconditioner()`` (dense levels, Jacobi smoother): one V cycle from a zero guess per iteration for the
+    whole block.  A dense A of the hierarchy's size is then one library call (pnl_mg_cg_block); any other operator with ``matvec_multi``
+    runs the loop here over the external-preconditioner steps (pnl_cgb_residual / _start / _step / _beta / _direction) and
+    ``multigrid.cycle`` on the block.
     Returns (X, iterations[nrhs], residuals[nrhs]): the final sqrt(r.Br) of every row; X is a torch tensor on the operator's device if
     B is one, else a numpy array."""
     import torch
     from ._lib import PNL_CGB_MAXVEC
     from .linear_operators import Dense_LinearOperator, _as_block
-    if callable(preconditioner):
-        raise NotImplementedError('cg_multi: a callable preconditioner (multigrid) for a block of right-hand sides is not built')
-    if preconditioner not in ('jacobi', None):
+    from .multigrid import multigrid as _multigrid
+    # a multigrid object, or the callable of its asPreconditioner(): the block cycle of that hierarchy
+    mg = preconditioner if isinstance(preconditioner, _multigrid) else getattr(preconditioner, 'multigrid', None)
+    if mg is None and callable(preconditioner):
+        raise NotImplementedError('cg_multi: a plain callable as preconditioner for a block of right-hand sides is not built '
+                                  '(pass a multigrid object or its asPreconditioner())')
+    if mg is None and preconditioner not in ('jacobi', None):
         raise NotImplementedError(preconditioner)
     from .linear_operators import DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator
     from .distributed_h2 import DistributedH2Matrix_localData
@@ -158,7 +225,12 @@ def cg_multi(A, B, X0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
         raise NotImplementedError('cg_multi: the block products of the distributed operators loop their matvec; solve row by row with cg')
     if not hasattr(A, 'matvec_multi'):
         raise NotImplementedError('cg_multi needs an operator with matvec_multi; got {!r}'.format(A))
-    if isinstance(A, Dense_LinearOperator) and A.symmetric and preconditioner == 'jacobi':
+    if mg is not None:
+        mg._require_block()                                 # NotImplementedError for a Chebyshev smoother, H2 / sparse levels
+        cycles = getattr(preconditioner, 'maxIter', 1)
+        if isinstance(A, Dense_LinearOperator) and A.num_rows == A.num_columns == mg.num_rows and cycles == 1:
+            return mg._cg_block(B, X0, tol, maxiter, None if A is mg.A else A)          # one library call (pnl_mg_cg_block)
+    elif isinstance(A, Dense_LinearOperator) and A.symmetric and preconditioner == 'jacobi':
         return A.solve_cg_jacobi_block(B, X0, tol, maxiter)
     if hasattr(A, 'assure_constructed'):
         A.assure_constructed()
@@ -180,7 +252,11 @@ def cg_multi(A, B, X0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
     its, res = np.zeros(nrhs, dtype=np.int32), np.zeros(nrhs)
     for v0 in range(0, nrhs, PNL_CGB_MAXVEC):
         v1 = min(nrhs, v0+PNL_CGB_MAXVEC)
-        _cg_group(A, ctx, dinv, Bd[v0:v1], X[v0:v1], X0 is not None, tol, maxiter, its[v0:v1], res[v0:v1])
+        if mg is not None:
+            _cg_group_mg(A, ctx, preconditioner if callable(preconditioner) else mg.cycle, Bd[v0:v1], X[v0:v1], X0 is not None, tol, maxiter,
+                         its[v0:v1], res[v0:v1])
+        else:
+            _cg_group(A, ctx, dinv, Bd[v0:v1], X[v0:v1], X0 is not None, tol, maxiter, its[v0:v1], res[v0:v1])
     if isinstance(B, torch.Tensor):
         return X, its, res
     return X.cpu().numpy(), its, res
