@@ -124,9 +124,19 @@ def oracle_entries(T, ij, cell_range=None, with_pairs=False):
 
 
 def oracle_centres(mesh):
-    """cell centres as nl_oracle.c forms them: (v0 + v1 + v2) * (1 / 3)"""
+    """cell centres as nl_oracle.c forms them: (v0 + v1 + v2) * (1 / 3); on an interval (v0 + v1) * (1 / 2)"""
     v = mesh.vertices[mesh.cells]
+    if v.shape[1] == 2:
+        return (v[:, 0]+v[:, 1])*(1./2.)
     return (v[:, 0]+v[:, 1]+v[:, 2])*(1./3.)
+
+
+def _dist2(diff):
+    """squared length of the rows, summed over the coordinates in the order of nl_oracle.c"""
+    d2 = diff[:, 0]*diff[:, 0]
+    for j in range(1, diff.shape[1]):
+        d2 = d2+diff[:, j]*diff[:, j]
+    return d2
 
 
 def _margin(a1, a2):
@@ -139,14 +149,12 @@ def pair_tie_margin(T, c1, c2):
     op = as_oracle(T)
     mesh = op.tables.dm.mesh
     cen, h = oracle_centres(mesh), mesh.hVector
-    diff = cen[c1]-cen[c2]
-    d2 = diff[:, 0]*diff[:, 0]+diff[:, 1]*diff[:, 1]
-    return _margin(*_order_args(op.tables.qo, h[c1], h[c2], d2, op.tables.H0))
+    return _margin(*_order_args(op.tables.qo, h[c1], h[c2], _dist2(cen[c1]-cen[c2]), op.tables.H0))
 
 
 def _cell_vertex_incidence(mesh):
-    nc = mesh.num_cells
-    return sp.csr_matrix((np.ones(3*nc), (np.repeat(np.arange(nc), 3), np.asarray(mesh.cells).ravel())), shape=(nc, mesh.num_vertices))
+    nc, nV = np.asarray(mesh.cells).shape
+    return sp.csr_matrix((np.ones(nV*nc), (np.repeat(np.arange(nc), nV), np.asarray(mesh.cells).ravel())), shape=(nc, mesh.num_vertices))
 
 
 def strip_distant_pairs(T, c0, c1):
@@ -164,8 +172,7 @@ def formula_orders(T, a, b):
     op = as_oracle(T)
     mesh = op.tables.dm.mesh
     cen, h = oracle_centres(mesh), mesh.hVector
-    diff = cen[a]-cen[b]
-    a1, a2 = _order_args(op.tables.qo, h[a], h[b], diff[:, 0]*diff[:, 0]+diff[:, 1]*diff[:, 1], op.tables.H0)
+    a1, a2 = _order_args(op.tables.qo, h[a], h[b], _dist2(cen[a]-cen[b]), op.tables.H0)
     return np.maximum(np.maximum(np.ceil(a1), np.ceil(a2)), 2.).astype(np.int64)
 
 
@@ -264,3 +271,162 @@ def strips(mesh, block, pad):
     c0, c1 = out[0]
     assert h[c0+pad:c1-pad].min() <= h.min()*(1.+1e-9)
     return out
+
+
+# ---- helpers of tests/test_graded_nearfield.py: graded intervals, the masked cell pairs and boundary items of a near field ----------
+
+def graded_interval(noRef, mu):
+    """interval(noRef) on [-1, 1] with every vertex moved by x -> sign(x) (1 - (1 - |x|)^mu): cells shrink towards both end points
+    (longest over shortest cell: 2^noRef - 1 for mu = 2).  Cells, their order and the boundary vertices are kept."""
+    from pynucleus_amd import interval
+    base = interval(noRef)
+    x = np.array(base.vertices, dtype=np.float64)
+    mesh = copy.copy(base)
+    mesh.vertices = np.ascontiguousarray(np.sign(x)*(1.-(1.-np.minimum(np.abs(x), 1.))**mu))
+    mesh.setMeshTransformation(None)
+    mesh.resetMeshInfo()
+    return mesh
+
+
+def distant_pair_mask(mesh, pairs):
+    """per cell pair (a, b): the two cells share no vertex (a == b shares all)"""
+    cells = np.asarray(mesh.cells)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    return ~(cells[pairs[:, 0]][:, :, None] == cells[pairs[:, 1]][:, None, :]).any(axis=(1, 2))
+
+
+def pair_evaluations(T, pairs):
+    """kernel evaluations per cell pair of the list, as the oracle's numIntegrations counts them: n_q^2 for a distant pair of order q
+    (formula_orders: the oracle's order wherever near_tie_margin is far above the rounding of a logarithm), the size of the rule of
+    the touching panel otherwise.  Returns (evaluations [np], distant [np])."""
+    op = as_oracle(T)
+    mesh = op.tables.dm.mesh
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    cells = np.asarray(mesh.cells)
+    common = (cells[pairs[:, 0]][:, :, None] == cells[pairs[:, 1]][:, None, :]).any(axis=2).sum(axis=1)
+    distant = common == 0
+    out = np.zeros(pairs.shape[0], dtype=np.int64)
+    off = np.asarray(op.tables.dist_off, dtype=np.int64)
+    q = formula_orders(op, pairs[distant, 0], pairs[distant, 1])
+    assert q.size == 0 or q.max() <= op.tables.qcap
+    out[distant] = (off[q+1]-off[q])**2
+    for k in np.unique(common[~distant]):
+        out[common == k] = evaluations(op, -int(k))
+    return out, distant
+
+
+def near_evaluations(T, pairs, masks):
+    """P[i, j] for every DoF pair: the kernel evaluations of the DISTANT masked cell pairs whose masked local entries reach (i, j) --
+    what oracle_entries returns per separated entry (all the cell pairs of a separated DoF pair are distant, and a near-field cluster
+    pair that holds the DoF pair requests all of them), for the whole near field at once.  pairs [np, 2] with a <= b and masks
+    [np, 4] uint64 over the (2 dpe)(2 dpe + 1) / 2 entries of the symmetric local matrix as clusters.buildMasksForClusters makes
+    them: bit k(p, q), p <= q, sends the pair's contribution to (ld[p], ld[q]) and to (ld[q], ld[p])."""
+    op = as_oracle(T)
+    dm = op.tables.dm
+    N = dm.num_dofs
+    dofs = np.asarray(dm.dofs)
+    dpe = dofs.shape[1]
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    masks = np.asarray(masks, dtype=np.uint64).reshape(-1, 4)
+    ev, distant = pair_evaluations(op, pairs)
+    pairs, masks, ev = pairs[distant], masks[distant], ev[distant].astype(np.float64)
+    ld = np.concatenate([dofs[pairs[:, 0]], dofs[pairs[:, 1]]], axis=1)
+    P = np.zeros(N*N)
+    k = 0
+    for p in range(2*dpe):
+        for q in range(p, 2*dpe):
+            bit = ((masks[:, k >> 6] >> np.uint64(k & 63)) & np.uint64(1)).astype(bool)
+            sel = bit & (ld[:, p] >= 0) & (ld[:, q] >= 0)
+            k += 1
+            if not sel.any():
+                continue
+            I, J = ld[sel, p].astype(np.int64), ld[sel, q].astype(np.int64)
+            P += np.bincount(I*N+J, weights=ev[sel], minlength=N*N)
+            if p != q:
+                P += np.bincount(J*N+I, weights=ev[sel], minlength=N*N)
+    assert P.max() < 2.**53
+    return np.rint(P).astype(np.int64).reshape(N, N)
+
+
+def near_magnitudes(T, pairs):
+    """M[i, j] for every DoF pair: a bound of the sum of the ABSOLUTE values of the quadrature terms behind a separated entry, for
+    elements whose shape functions change sign (P2), where the terms of an entry are not of one sign and |A_ij| is no measure of them.
+    The shape functions of a cell sum to 1 and |phi| <= 1, so the absolute terms of the cell pair (a, b) for any (p, q) sum to at most
+    S_ab = 2 vol sum_kl w_k w_l gamma(x_k, y_l) = 2 |sum_pq contrib_ab[p, dpe + q]| of the oracle's own contribution (nlo_eval), and
+    M_ij = sum of S_ab over the distant cell pairs of the list with a in the support of i and b in that of j, in either order."""
+    op = as_oracle(T)
+    dm = op.tables.dm
+    dofs = np.asarray(dm.dofs)
+    nc, dpe = dofs.shape
+    n2 = 2*dpe
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    pairs = pairs[distant_pair_mask(dm.mesh, pairs)]
+    cross = np.array([n2*p-(p*(p+1) >> 1)+dpe+q for p in range(dpe) for q in range(dpe)])
+    S = np.array([2.*abs(op.eval(int(a), int(b))[1][cross].sum()) for a, b in pairs])
+    E = sp.csr_matrix((S, (pairs[:, 0], pairs[:, 1])), shape=(nc, nc))
+    c, k = np.nonzero(dofs >= 0)
+    inc = sp.csr_matrix((np.ones(c.size), (c, dofs[c, k])), shape=(nc, dm.num_dofs))
+    half = (inc.T@E@inc).toarray()
+    return half+half.T
+
+
+def near_tie_margin(T, pairs, bcells=None, bfacets=None):
+    """smallest distance to an integer of the two ceil() arguments of the oracle's order formulas over what a near field classifies:
+    the masked cell pairs without a common vertex (nlo_panel: centres, longest edges h, formula qo) and the (cell, facet) items
+    without a common vertex (nlo_panel_boundary, which nlo_assemble_boundary_masked calls with the item's facet as its only boundary
+    facet: cell centre against facet centre, h of the cell against the length of the facet -- 1 on an interval --, formula bqo: the
+    facet formula of strip_tie_margin).  In 1-D and 2-D.  Returns (margin of the pairs, their number, margin of the items, their
+    number); the margin of an empty set is inf."""
+    op = as_oracle(T)
+    Tb = op.tables
+    mesh = Tb.dm.mesh
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    keep = distant_pair_mask(mesh, pairs)
+    a, b = pairs[keep, 0], pairs[keep, 1]
+    mp = float(pair_tie_margin(op, a, b).min()) if a.size else np.inf
+    mi, ni = np.inf, 0
+    if bcells is not None and len(bcells):
+        c = np.asarray(bcells, dtype=np.int64)
+        f = np.asarray(bfacets, dtype=np.int64).reshape(c.shape[0], -1)
+        cells = np.asarray(mesh.cells)
+        keep = ~(cells[c][:, :, None] == f[:, None, :]).any(axis=(1, 2))
+        c, f = c[keep], f[keep]
+        ni = int(c.size)
+        if ni:
+            v = mesh.vertices[f]                                         # [ni, dim, dim]
+            if f.shape[1] == 2:
+                fcen = (v[:, 0]+v[:, 1])*0.5
+                flen = np.sqrt((v[:, 1, 0]-v[:, 0, 0])**2+(v[:, 1, 1]-v[:, 0, 1])**2)
+            else:
+                fcen, flen = v[:, 0]*1., np.ones(ni)
+            d2 = _dist2(oracle_centres(mesh)[c]-fcen)
+            mi = float(_margin(*_order_args(Tb.bqo, mesh.hVector[c], flen, d2, Tb.H0)).min())
+    return mp, int(a.size), mi, ni
+
+
+def facet_item_evaluations(T, bcells, bfacets):
+    """point pairs per (cell, facet) item as the oracle's nlo_eval_boundary counts them: n_q nf_q for an item without a common vertex
+    (order q by the facet formula bqo), the size of the touching rule otherwise.  Returns (evaluations [ni], distant [ni])."""
+    op = as_oracle(T)
+    Tb = op.tables
+    mesh = Tb.dm.mesh
+    c = np.asarray(bcells, dtype=np.int64)
+    f = np.asarray(bfacets, dtype=np.int64).reshape(c.shape[0], -1)
+    cells = np.asarray(mesh.cells)
+    common = (cells[c][:, :, None] == f[:, None, :]).any(axis=2).sum(axis=1)
+    distant = common == 0
+    out = np.zeros(c.shape[0], dtype=np.int64)
+    cd, fd = c[distant], f[distant]
+    v = mesh.vertices[fd]
+    if f.shape[1] == 2:
+        fcen = (v[:, 0]+v[:, 1])*0.5
+        flen = np.sqrt((v[:, 1, 0]-v[:, 0, 0])**2+(v[:, 1, 1]-v[:, 0, 1])**2)
+    else:
+        fcen, flen = v[:, 0]*1., np.ones(cd.size)
+    a1, a2 = _order_args(Tb.bqo, mesh.hVector[cd], flen, _dist2(oracle_centres(mesh)[cd]-fcen), Tb.H0)
+    q = np.maximum(np.maximum(np.ceil(a1), np.ceil(a2)), 2.).astype(np.int64)
+    off, foff = np.asarray(Tb.dist_off, dtype=np.int64), np.asarray(Tb.bfacet_off, dtype=np.int64)
+    out[distant] = (off[q+1]-off[q])*(foff[q+1]-foff[q])
+    for k in np.unique(common[~distant]):
+        out[common == k] = int(Tb.bsingular[-int(k)].num_nodes)
+    return out, distant
