@@ -809,6 +809,77 @@ int pnl_cgb_step(pnl_context *ctx, int n, int nvec, const double *P_dev, int64_t
                  double *R_dev, int64_t ldr, double *state_dev);
 int pnl_cgb_beta(pnl_context *ctx, int n, int nvec, const double *R_dev, int64_t ldr, const double *Z_dev, int64_t ldz, double *state_dev);
 
+/* ---- BiCGStab for a block of right-hand sides (csrc/pnl_bicgstab_block.hip): bicgstab_solver.solve
+ *      (base/PyNucleus_base/solvers.pyx:716-787) for A X = B with a general (non-symmetric) A and several right-hand sides at once. ----
+ * Up to PNL_CGB_MAXVEC = 16 right-hand sides ("columns", stored one per row as in pnl_gemv_block) are solved together.  Every column
+ * runs its OWN recurrence of the reference's right-preconditioned BiCGStab (its own alpha, omega, beta, convergence and breakdown) and
+ * the columns share the two operator products of a pass:
+ *   start:  R = B - A X;  P = R;  R0 = M^-1 R;  P2 = M^-1 P;  kappa = R . R0;  res = sqrt(|kappa|)
+ *   pass:   T = A P2;  alpha = kappa / (T . R0);  S = R - alpha T;  S2 = M^-1 S;  T2 = A S2;  omega = (T2 . S) / (T2 . T2);
+ *           X += alpha P2 + omega S2;  R = S - omega T2;  res = sqrt(R . R);  kappaNew = R . R0;  res < tol: converged; else
+ *           beta = kappaNew / kappa * alpha / omega;  P = R + beta (P - omega T);  P2 = M^-1 P;  kappa = kappaNew
+ * Convergence is ||r||_2 < tol, absolute and strict, as in the reference; there is no test at the start and the residual is never
+ * recomputed from b - A x.  A column that converges in the first pass reports 0 iterations, one that never converges maxiter.
+ * maxiter = 0 returns res = sqrt(|kappa|) and leaves X alone.  A column that has converged is FROZEN: none of its blocks and nothing
+ * of its state is written again.  More than 16 columns are taken as consecutive groups of 16, each with a loop of its own.
+ * Breakdowns (the reference divides and returns NaN):
+ *   kappa == 0 at the start (b = 0 with x0 = 0): frozen at once, 0 iterations, residual 0.
+ *   T2 . T2 == 0 (S = 0, the lucky breakdown): omega := 0, so X += alpha P2, R = S, and the column converges by the normal test.
+ *   A column whose next scalar would be 0 / 0, x / 0 or not finite -- T . R0 == 0; omega == 0 or kappaNew == 0 when the column has not
+ *   converged; any sum that is not finite -- is frozen BEFORE a value that is not finite is written to one of its blocks.  Its
+ *   iteration count is the pass in which this happened, its residual the last one computed: iterations < maxiter with
+ *   residual >= tol identifies a breakdown.  The code stays in slot [6] of the state.
+ * No floating-point atomics: every dot product is summed in a shape that depends on n only (that of the pnl_cgb_* steps).  With a
+ * product whose bits are independent per vector (pnl_gemv_block; pnl_spmv_block on CSR; the ordered H2 far field) the bits of X[v],
+ * iters[v] and residuals[v] depend neither on the number of columns nor on the position v nor on the other columns, and two calls
+ * repeat bit for bit.  The padding of the blocks (ld > n) is neither read into a sum nor written.
+ *
+ * pnl_bicgstab_block: A dense, square, general, row-major n x n, read in full by pnl_gemv_block; nothing assumes symmetry.
+ * jacobi != 0: M^-1 = 1 / diagonal (pnl_inv_diagonal); else M = I.  X_dev holds the initial guesses and the results; iters[nrhs] and
+ * residuals[nrhs] on the host (either may be NULL).  Work comes from a growing buffer of the context; nothing else is allocated per
+ * call.  Synchronous: the host reads the state of the group back once per pass.  PNL_ERR_INVALID, before any launch, for a null ctx,
+ * A, B or X; n or nrhs < 1; ldA, ldb or ldx < n; maxiter < 0; B_dev == X_dev or A_dev == X_dev. */
+int pnl_bicgstab_block(pnl_context *ctx, const double *A_dev, int64_t ldA, int n, int nrhs, int jacobi, const double *B_dev, int64_t ldb,
+                       double *X_dev, int64_t ldx, double tol, int maxiter, int *iters, double *residuals);
+/* The steps of that loop on caller-owned device blocks [nvec][ld], nvec <= 16 (pnl_bicgstab_block is exactly these calls around
+ * pnl_gemv_block).  Preconditioner: external == 0: M^-1 = dinv_dev (1 / diagonal, n doubles; NULL: the unit diagonal), applied by the
+ * steps; external != 0: the caller applies M^-1 on whole blocks between the calls, the steps neither read dinv_dev nor touch R0 (init),
+ * S2 (alpha) or P2 (init, direction), which may then be NULL.  state_dev: PNL_BCGB_STATE doubles per column, column v at
+ * state_dev[v * PNL_BCGB_STATE]:
+ *   [0] kappa   [1] alpha   [2] omega   [3] res   [4] active (1 or 0)   [5] kappaNew = R . R0   [6] breakdown code PNL_BCGB_*
+ *   [7] T . R0   [8] T2 . S   [9] T2 . T2   [10] R . R   [11] beta
+ *   pnl_bcgb_init       every column: R = B - AX (AX_dev NULL: X is zero, R = B), P = R; external == 0: also R0 = P2 = dinv R and the
+ *                       start state as pnl_bcgb_start
+ *   pnl_bcgb_start      with the caller's R0 = M^-1 R of every column: kappa = R . R0, res = sqrt(|kappa|), active = kappa is finite
+ *                       and not 0; writes the whole state of the columns v < nvec.  (The caller also sets P2 = R0.)
+ *   pnl_bcgb_alpha      active columns: alpha = kappa / (T . R0); S = R - alpha T, written over R (RS_dev); external == 0: S2 = dinv S.
+ *                       T . R0 == 0 or not finite: the code is set and none of the column's blocks is written
+ *   pnl_bcgb_omega      live columns (active, no code): omega; X += alpha P2 + omega S2; R = S - omega T2 over S (RS_dev); res,
+ *                       kappaNew; then res < tol: active = 0; a breakdown: the code and active = 0; else beta and kappa = kappaNew.
+ *                       Clears active of a column whose code pnl_bcgb_alpha has set; its res stays
+ *   pnl_bcgb_direction  active columns: P = R + beta (P - omega T); external == 0: P2 = dinv P.  The state is only read
+ * A pass of the loop is: T = A P2; alpha; (S2 = M^-1 S); T2 = A S2; omega; direction; (P2 = M^-1 P); read the state.  Columns that are
+ * not active are neither read nor written.  Asynchronous on the context's stream.  PNL_ERR_INVALID, before any launch, for a null
+ * pointer (but dinv_dev, AX_dev in pnl_bcgb_init and the blocks an external preconditioner owns), n < 1, nvec < 1, nvec > 16, a
+ * leading dimension below n, a block that is written being the same as another block of the call. */
+#define PNL_BCGB_STATE 12
+#define PNL_BCGB_OK 0
+#define PNL_BCGB_TR0 1          /* T . R0 == 0 */
+#define PNL_BCGB_OMEGA 2        /* omega == 0 and the column has not converged */
+#define PNL_BCGB_KAPPA 3        /* kappaNew == 0 and the column has not converged */
+#define PNL_BCGB_NONFINITE 4    /* a sum or a scalar that is not finite */
+int pnl_bcgb_init(pnl_context *ctx, int n, int nvec, int external, const double *dinv_dev, const double *B_dev, int64_t ldb, const double *AX_dev,
+                  int64_t ldax, double *R_dev, int64_t ldr, double *P_dev, int64_t ldp, double *R0_dev, int64_t ldr0, double *P2_dev, int64_t ldp2,
+                  double *state_dev);
+int pnl_bcgb_start(pnl_context *ctx, int n, int nvec, const double *R_dev, int64_t ldr, const double *R0_dev, int64_t ldr0, double *state_dev);
+int pnl_bcgb_alpha(pnl_context *ctx, int n, int nvec, int external, const double *dinv_dev, const double *T_dev, int64_t ldt, const double *R0_dev,
+                   int64_t ldr0, double *RS_dev, int64_t ldr, double *S2_dev, int64_t lds2, double *state_dev);
+int pnl_bcgb_omega(pnl_context *ctx, int n, int nvec, const double *P2_dev, int64_t ldp2, const double *S2_dev, int64_t lds2, const double *T2_dev,
+                   int64_t ldt2, const double *R0_dev, int64_t ldr0, double *X_dev, int64_t ldx, double *RS_dev, int64_t ldr, double tol,
+                   double *state_dev);
+int pnl_bcgb_direction(pnl_context *ctx, int n, int nvec, int external, const double *dinv_dev, const double *R_dev, int64_t ldr, const double *T_dev,
+                       int64_t ldt, double *P_dev, int64_t ldp, double *P2_dev, int64_t ldp2, const double *state_dev);
+
 /* ---- multigrid for a block of right-hand sides (csrc/pnl_mg_block.hip): the cycle of pnl_mg_cycle and the loop of pnl_mg_cg for several
  *      right-hand sides on one hierarchy. -----------------------------------------------------------------------------------------------
  * Columns are stored one per row as in pnl_gemv_block: column v is B_dev[v*ldb .. v*ldb + n), its result X_dev[v*ldx .. v*ldx + n), n the

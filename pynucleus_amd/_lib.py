@@ -37,13 +37,17 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_imex_destroy', 'pnl_imex_sweep', 'pnl_lincomb', 'pnl_gemv_multi', 'pnl_gemv_block', 'pnl_spmv_block', 'pnl_uniform_lane_layout',
            'pnl_h2_matvec_block', 'pnl_h2_upward_block', 'pnl_h2_interact_block', 'pnl_h2_downward_block',
            'pnl_cg_jacobi_block', 'pnl_cgb_init', 'pnl_cgb_update', 'pnl_cgb_refresh', 'pnl_cgb_direction',
-           'pnl_cgb_residual', 'pnl_cgb_start', 'pnl_cgb_step', 'pnl_cgb_beta', 'pnl_mg_cycle_block', 'pnl_mg_cg_block']
+           'pnl_cgb_residual', 'pnl_cgb_start', 'pnl_cgb_step', 'pnl_cgb_beta', 'pnl_mg_cycle_block', 'pnl_mg_cg_block',
+           'pnl_bicgstab_block', 'pnl_bcgb_init', 'pnl_bcgb_start', 'pnl_bcgb_alpha', 'pnl_bcgb_omega', 'pnl_bcgb_direction']
 
 PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
 PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
 PNL_IMEX_MAX_STAGES, PNL_IMEX_MAX_COMP = 4, 2
 PNL_INTERP_MAX_OPS = 21
 PNL_CGB_MAXVEC, PNL_CGB_STATE = 16, 8
+# pnl_bcgb_*: doubles per column of the state; the breakdown codes of slot [6]
+PNL_BCGB_STATE = 12
+PNL_BCGB_OK, PNL_BCGB_TR0, PNL_BCGB_OMEGA, PNL_BCGB_KAPPA, PNL_BCGB_NONFINITE = 0, 1, 2, 3, 4
 
 
 def source_sha16():
@@ -226,6 +230,12 @@ def load():
     L.pnl_cgb_start.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp, i64, dbl, vp]
     L.pnl_cgb_step.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.pnl_cgb_beta.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp]
+    L.pnl_bicgstab_block.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, i64, dbl, i32, vp, vp]
+    L.pnl_bcgb_init.argtypes = [vp, i32, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.pnl_bcgb_start.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp]
+    L.pnl_bcgb_alpha.argtypes = [vp, i32, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.pnl_bcgb_omega.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, dbl, vp]
+    L.pnl_bcgb_direction.argtypes = [vp, i32, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.pnl_mg_cycle_block.argtypes = [vp, i32, vp, i64, vp, i64, i32]
     L.pnl_mg_cg_block.argtypes = [vp, vp, i64, i32, vp, i64, vp, i64, dbl, i32, i32, vp, vp]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
@@ -763,6 +773,39 @@ class Context:
     def cgb_beta(self, n, nvec, R_ptr, ldr, Z_ptr, ldz, state_ptr):
         """active columns: beta = R.Z, conv = sqrt(|beta|)"""
         self.check(self.L.pnl_cgb_beta(self.h, int(n), int(nvec), _vp(R_ptr), int(ldr), _vp(Z_ptr), int(ldz), _vp(state_ptr)))
+
+    # -- BiCGStab for a block of right-hand sides (pnl_bicgstab_block.hip), a general A: column v is B[v*ldb .. v*ldb + n) ---
+    def bicgstab_block(self, A_ptr, ldA, n, nrhs, jacobi, B_ptr, ldb, X_ptr, ldx, tol, maxiter):
+        """every column its own BiCGStab recurrence, two pnl_gemv_block passes per pass and group of 16; X holds the initial guesses and
+        the results.  Returns (iterations [nrhs] int32, residuals [nrhs]); iterations < maxiter with residual >= tol is a breakdown"""
+        its, res = np.zeros(max(int(nrhs), 1), dtype=np.int32), np.zeros(max(int(nrhs), 1))
+        self.check(self.L.pnl_bicgstab_block(self.h, _vp(A_ptr), int(ldA), int(n), int(nrhs), int(bool(jacobi)), _vp(B_ptr), int(ldb), _vp(X_ptr),
+                                             int(ldx), float(tol), int(maxiter), its.ctypes.data, res.ctypes.data))
+        return its, res
+
+    def bcgb_init(self, n, nvec, external, dinv_ptr, B_ptr, ldb, AX_ptr, ldax, R_ptr, ldr, P_ptr, ldp, R0_ptr, ldr0, P2_ptr, ldp2, state_ptr):
+        """R = B - AX (AX_ptr 0: R = B), P = R; not external: R0 = P2 = dinv R and the start state (include/pnl_hip.h)"""
+        self.check(self.L.pnl_bcgb_init(self.h, int(n), int(nvec), int(bool(external)), _vp(dinv_ptr), _vp(B_ptr), int(ldb), _vp(AX_ptr), int(ldax),
+                                        _vp(R_ptr), int(ldr), _vp(P_ptr), int(ldp), _vp(R0_ptr), int(ldr0), _vp(P2_ptr), int(ldp2), _vp(state_ptr)))
+
+    def bcgb_start(self, n, nvec, R_ptr, ldr, R0_ptr, ldr0, state_ptr):
+        """kappa = R.R0, res = sqrt(|kappa|), active: the state of every column, from the caller's R0 = M^-1 R"""
+        self.check(self.L.pnl_bcgb_start(self.h, int(n), int(nvec), _vp(R_ptr), int(ldr), _vp(R0_ptr), int(ldr0), _vp(state_ptr)))
+
+    def bcgb_alpha(self, n, nvec, external, dinv_ptr, T_ptr, ldt, R0_ptr, ldr0, RS_ptr, ldr, S2_ptr, lds2, state_ptr):
+        """active columns: alpha = kappa / T.R0, S = R - alpha T over R; not external: S2 = dinv S"""
+        self.check(self.L.pnl_bcgb_alpha(self.h, int(n), int(nvec), int(bool(external)), _vp(dinv_ptr), _vp(T_ptr), int(ldt), _vp(R0_ptr), int(ldr0),
+                                         _vp(RS_ptr), int(ldr), _vp(S2_ptr), int(lds2), _vp(state_ptr)))
+
+    def bcgb_omega(self, n, nvec, P2_ptr, ldp2, S2_ptr, lds2, T2_ptr, ldt2, R0_ptr, ldr0, X_ptr, ldx, RS_ptr, ldr, tol, state_ptr):
+        """live columns: omega, X += alpha P2 + omega S2, R = S - omega T2 over S, res, kappaNew; converged, broken down, or beta"""
+        self.check(self.L.pnl_bcgb_omega(self.h, int(n), int(nvec), _vp(P2_ptr), int(ldp2), _vp(S2_ptr), int(lds2), _vp(T2_ptr), int(ldt2),
+                                         _vp(R0_ptr), int(ldr0), _vp(X_ptr), int(ldx), _vp(RS_ptr), int(ldr), float(tol), _vp(state_ptr)))
+
+    def bcgb_direction(self, n, nvec, external, dinv_ptr, R_ptr, ldr, T_ptr, ldt, P_ptr, ldp, P2_ptr, ldp2, state_ptr):
+        """active columns: P = R + beta (P - omega T); not external: P2 = dinv P"""
+        self.check(self.L.pnl_bcgb_direction(self.h, int(n), int(nvec), int(bool(external)), _vp(dinv_ptr), _vp(R_ptr), int(ldr), _vp(T_ptr), int(ldt),
+                                             _vp(P_ptr), int(ldp), _vp(P2_ptr), int(ldp2), _vp(state_ptr)))
 
     def h2_matvec_block(self, nvec, X_ptr, ldx, Y_ptr, ldy):
         """Y[v] += far field of X[v] for the H2 operator set up in the context, without float atomics (pnl_h2_block.hip)"""

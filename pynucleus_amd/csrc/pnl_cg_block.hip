@@ -29,64 +29,22 @@
 //
 // No floating-point atomics.  A dot product is summed in a fixed shape that depends on n only: per thread in ascending i (fma), the
 // 64 lanes in the DPP tree of wave_sum, the four waves in ascending order, the workgroups in 16 interleaved runs in ascending order
-// and those 16 in ascending order (cgb_totals).  With a product whose bits are independent per vector (pnl_gemv_block,
-// pnl_spmv_block on CSR, the ordered H2 far field) the bits of X[v], its iteration count and its residual therefore depend neither
+// and those 16 in ascending order (cgb_block_sums and cgb_totals, pnl_cgb_sums.h, shared with pnl_bicgstab_block.hip).  With a
+// product whose bits are independent per vector (pnl_gemv_block, pnl_spmv_block on CSR, the ordered H2 far field) the bits of X[v], its iteration count and its residual therefore depend neither
 // on nvec nor on the position v nor on the other columns, and two calls repeat bit for bit.  The redundant final adds cost
 // 16 x blocks loads per workgroup, which the cap CGB_MAXBLK bounds at 4096.
-#include "pnl_context.h"
-#include "pnl_common.h"
+#include "pnl_cgb_sums.h"
 
 namespace {
 
-constexpr int CGB_NV = PNL_CGB_MAXVEC;     // columns per group = vectors per pass of the block products
-constexpr int CGB_THREADS = 256;
-constexpr int CGB_MAXBLK = 256;            // workgroups per launch at most (one per CU)
-constexpr int CGB_PART = CGB_MAXBLK*CGB_NV;
-static_assert(CGB_NV == 16 && CGB_THREADS == 16*CGB_NV, "cgb_totals: 16 runs of partial sums x 16 columns");
-
 // slots of the per-column state (include/pnl_hip.h)
 enum { ST_BETA_OLD = 0, ST_PAP = 1, ST_BETA = 2, ST_CONV = 3, ST_ACTIVE = 4 };
-
-inline int cgb_blocks(int n) { return std::min(CGB_MAXBLK, (n+CGB_THREADS-1)/CGB_THREADS); }
 
 // bit v: column v < nv is active
 __device__ __forceinline__ unsigned cgb_active_mask(const double *__restrict__ state, int nv) {
     unsigned m = 0;
     for (int v = 0; v < nv; v++) m |= state[v*PNL_CGB_STATE+ST_ACTIVE] != 0. ? 1u << v : 0u;
     return m;
-}
-
-// the workgroup's sums of the thread values s[v] for the columns of mask (0 for the others) -> row[0 .. 16)
-__device__ __forceinline__ void cgb_block_sums(const double (&s)[CGB_NV], unsigned mask, double *__restrict__ row) {
-    __shared__ double sw[CGB_THREADS/64][CGB_NV];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-    for (int v = 0; v < CGB_NV; v++) {
-        if ((mask >> v) & 1) {                     // uniform over the workgroup
-            const double t = wave_sum(s[v]);
-            if (lane == 0) sw[wv][v] = t;
-        }
-    }
-    __syncthreads();
-    if (tid < CGB_NV) row[tid] = ((mask >> tid) & 1) ? ((sw[0][tid]+sw[1][tid])+sw[2][tid])+sw[3][tid] : 0.;
-}
-
-// tot[v] = sum of part[k][v] over the nb workgroups, v < 16: thread (j, v) adds the run k = j, j + 16, ... in ascending order, then
-// the 16 runs are added in ascending j.  Ends with a barrier: every thread may read tot.
-__device__ __forceinline__ void cgb_totals(const double *__restrict__ part, int nb, double *tot) {
-    __shared__ double sp[CGB_NV][CGB_NV+1];
-    const int tid = threadIdx.x, v = tid & 15, j = tid >> 4;
-    double s = 0.;
-    for (int k = j; k < nb; k += 16) s += part[k*CGB_NV+v];
-    sp[j][v] = s;
-    __syncthreads();
-    if (tid < CGB_NV) {
-        double t = sp[0][tid];
-#pragma unroll
-        for (int jj = 1; jj < 16; jj++) t += sp[jj][tid];
-        tot[tid] = t;
-    }
-    __syncthreads();
 }
 
 __global__ void __launch_bounds__(CGB_THREADS)
@@ -301,8 +259,6 @@ int cgb_finish_abs(pnl_context *ctx, bool start, int n, int nv, const double *pa
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
-
-bool cgb_bad_block(const void *p, int64_t ld, int n) { return !p || ld < n; }
 
 }  // namespace
 

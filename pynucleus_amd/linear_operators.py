@@ -204,6 +204,29 @@ class Dense_LinearOperator(blockProducts):
             return Xd, its, res
         return Xd.cpu().numpy(), its, res
 
+    def solve_bicgstab_block(self, B, X0=None, tol=1e-8, maxiter=50, preconditioner=None):
+        """BiCGStab for the rows of B [nrhs, n] at once (pnl_bicgstab_block), the operator square and general (nothing assumes symmetry):
+        every row its own recurrence, two passes over the block per pass of the loop and 16 rows.  ``preconditioner``: None or 'jacobi'.
+        Returns (X, iterations[nrhs], residuals[nrhs], the 2-norms); torch in, torch out, else numpy.  No float atomics: the bits of a
+        row do not depend on the other rows.  iterations < maxiter with residual >= tol: the recurrence of that row broke down."""
+        if preconditioner not in (None, 'jacobi'):
+            raise NotImplementedError(preconditioner)
+        dev = self.A.device
+        assert self.num_rows == self.num_columns
+        Bd = _as_block(B, dev)
+        k = Bd.shape[0]
+        assert k >= 1 and Bd.shape[1] == self.num_rows, (tuple(Bd.shape), self.num_rows)
+        Xd = torch.zeros((k, self.num_rows), dtype=torch.float64, device=dev) if X0 is None else _as_block(X0, dev).clone(
+            memory_format=torch.contiguous_format)
+        assert Xd.shape == Bd.shape, (tuple(Xd.shape), tuple(Bd.shape))
+        torch.cuda.current_stream(dev).synchronize()
+        its, res = self.ctx.bicgstab_block(self.A.data_ptr(), max(int(self.A.stride(0)), self.num_rows), self.num_rows, k,
+                                           preconditioner == 'jacobi', Bd.data_ptr(), max(int(Bd.stride(0)), self.num_rows), Xd.data_ptr(),
+                                           self.num_rows, tol, maxiter)
+        if isinstance(B, torch.Tensor):
+            return Xd, its, res
+        return Xd.cpu().numpy(), its, res
+
     def solve_direct(self, b):
         """x with A x = b through the Cholesky factor (solvers.chol; a symmetric operator) or the pivoted LU factors (solvers.plu; any
         other square one) of a device copy of the block, computed on the first call and kept until invalidate() / refresh() or until

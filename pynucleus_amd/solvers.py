@@ -10,6 +10,9 @@ The dense operator additionally has this loop as one library call (pnl_cg_jacobi
 ``gmres`` follows gmres_solver.solve (solvers.pyx:504-659; the drivers' gmres-jacobi / gmres-mg for non-symmetric orders):
 left (default) or right preconditioner, modified Gram-Schmidt, Givens rotations, the rotated right-hand side as residual
 estimate, restarts; the Krylov basis stays in HBM, the small Hessenberg problem lives on the host.
+``bicgstab`` follows bicgstab_solver.solve (solvers.pyx:716-787); ``bicgstab_multi`` is that recurrence for a 2-D block of right-hand
+sides of a general operator: every row its own recurrence, the two operator products of a pass shared (matvec_multi); the dense
+operator has it as one library call (pnl_bicgstab_block), the others run it over the library's steps (pnl_bcgb_*).
 ``chol`` / ``lu`` are the direct solver of the symmetric dense operators (lu_solver, solvers.pyx:80-186): the Cholesky factor is
 computed once in HBM (pnl_potrf), every solve is two triangular sweeps (pnl_potrs).  ``plu`` is the same solver for any square dense
 operator, symmetric or not: P A = L U with partial pivoting (pnl_getrf), every solve the swaps and two sweeps (pnl_getrs)."""
@@ -347,9 +350,148 @@ def gmres(A, b, x0=None, tol=1e-8, maxiter=50, restarts=1, preconditioner=None, 
     return x.cpu().numpy(), allIter, residuals
 
 
+def _bicgstab_group(A, ctx, dinv, cycle, B, X, have_x0, tol, maxiter, its, res):
+    """the loop of pnl_bicgstab_block (csrc/pnl_bicgstab_block.hip) for at most 16 rows of B, with ``A.matvec_multi`` as the product and
+    the library's step calls on device blocks.  ``cycle`` None: the preconditioner is ``dinv`` (None: the unit diagonal), applied by the
+    steps; else the external mode, ``cycle`` (a block [nv, n] -> M^-1 of every row: multigrid.cycle) applied here between the steps.
+    X [nv, n] contiguous holds the guesses and the results, its / res are filled"""
+    import torch
+    from ._lib import PNL_BCGB_STATE
+    nv, n = B.shape
+    dev = B.device
+    ext = cycle is not None
+    R, P, R0, P2, S2 = (torch.empty((nv, n), dtype=torch.float64, device=dev) for _ in range(5))
+    state = torch.zeros(nv*PNL_BCGB_STATE, dtype=torch.float64, device=dev)
+    dp = dinv.data_ptr() if dinv is not None else 0
+    ldb = max(int(B.stride(0)), n)
+
+    def product(V):
+        ctx.synchronize()
+        W = A.matvec_multi(V)
+        torch.cuda.current_stream(dev).synchronize()
+        return W
+
+    def precondition(V, out):
+        ctx.synchronize()
+        out.copy_(cycle(V))
+        torch.cuda.current_stream(dev).synchronize()
+
+    def read_state():
+        ctx.synchronize()
+        return state.cpu().numpy().reshape(nv, PNL_BCGB_STATE)
+
+    AX = product(X) if have_x0 else None
+    torch.cuda.current_stream(dev).synchronize()
+    ctx.bcgb_init(n, nv, ext, dp, B.data_ptr(), ldb, AX.data_ptr() if AX is not None else 0, n, R.data_ptr(), n, P.data_ptr(), n, R0.data_ptr(), n,
+                  P2.data_ptr(), n, state.data_ptr())
+    if ext:
+        precondition(R, R0)
+        P2.copy_(R0)                                    # P = R at the start
+        torch.cuda.current_stream(dev).synchronize()
+        ctx.bcgb_start(n, nv, R.data_ptr(), n, R0.data_ptr(), n, state.data_ptr())
+    st = read_state()
+    res[:] = st[:, 3]
+    its[:] = 0
+    active = st[:, 4] != 0.
+    for it in range(maxiter):
+        if not active.any():
+            break
+        T = product(P2)
+        ctx.bcgb_alpha(n, nv, ext, dp, T.data_ptr(), n, R0.data_ptr(), n, R.data_ptr(), n, S2.data_ptr(), n, state.data_ptr())
+        if ext:
+            precondition(R, S2)                         # S lives in R between the two steps
+        T2 = product(S2)
+        ctx.bcgb_omega(n, nv, P2.data_ptr(), n, S2.data_ptr(), n, T2.data_ptr(), n, R0.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, tol,
+                       state.data_ptr())
+        ctx.bcgb_direction(n, nv, ext, dp, R.data_ptr(), n, T.data_ptr(), n, P.data_ptr(), n, P2.data_ptr(), n, state.data_ptr())
+        if ext:
+            precondition(P, P2)
+        st = read_state()
+        res[active] = st[active, 3]
+        done = active & (st[:, 4] == 0.)
+        its[done] = it
+        active &= ~done
+    its[active] = maxiter
+
+
+def bicgstab_multi(A, B, X0=None, tol=1e-8, maxiter=50, preconditioner=None):
+    """Solve A X[v] = B[v] for the rows of a 2-D B [nrhs, n], A a general (non-symmetric) operator.  Every row runs the recurrence of
+    ``bicgstab`` on its own (own alpha, omega, beta, own convergence test ||r||_2 < tol, frozen once it has converged) and the rows
+    share the two operator products of a pass: two ``matvec_multi`` per pass and 16 rows.  A square Dense_LinearOperator on one GPU with
+    ``preconditioner`` None or 'jacobi' is one library call (pnl_bicgstab_block); any other operator with ``matvec_multi`` (CSR, SSS, H2
+    in either far-field mode, interpolated, non-symmetric H2) runs the same loop here over the library's step calls.  A ``multigrid``
+    object or its ``asPreconditioner()`` (dense levels, Jacobi smoother) is applied between the steps: one V cycle from a zero guess
+    for the whole block, twice per pass and once at the start.
+    Unlike the reference, which divides and returns NaN, a row whose recurrence breaks down (T.R0, omega or kappa 0, a sum that is not
+    finite) is frozen before anything that is not finite is written: it reports the pass of the breakdown and its last residual, so
+    iterations < maxiter with residual >= tol identifies it.  A zero right-hand side with a zero guess reports 0 iterations and
+    residual 0.
+    Returns (X, iterations[nrhs], residuals[nrhs]): the final ||r||_2 of every row (for maxiter = 0 the start value sqrt(|r.M^-1 r|)); X
+    is a torch tensor on the operator's device if B is one, else a numpy array."""
+    from .linear_operators import Dense_LinearOperator
+    from .multigrid import multigrid as _multigrid
+    mg = preconditioner if isinstance(preconditioner, _multigrid) else getattr(preconditioner, 'multigrid', None)
+    if mg is None and callable(preconditioner):
+        raise NotImplementedError('bicgstab_multi: a plain callable as preconditioner for a block of right-hand sides is not built '
+                                  '(pass a multigrid object or its asPreconditioner())')
+    if mg is None and preconditioner not in ('jacobi', None):
+        raise NotImplementedError(preconditioner)
+    from .linear_operators import DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator
+    from .distributed_h2 import DistributedH2Matrix_localData
+    if isinstance(A, (DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator,
+                      DistributedH2Matrix_localData)):
+        raise NotImplementedError('bicgstab_multi: the block products of the distributed operators loop their matvec; solve row by row '
+                                  'with bicgstab')
+    if not hasattr(A, 'matvec_multi'):
+        raise NotImplementedError('bicgstab_multi needs an operator with matvec_multi; got {!r}'.format(A))
+    if mg is not None:
+        mg._require_block()                                 # NotImplementedError for a Chebyshev smoother, H2 / sparse levels
+    elif isinstance(A, Dense_LinearOperator) and A.num_rows == A.num_columns:
+        return A.solve_bicgstab_block(B, X0, tol, maxiter, preconditioner)          # one library call (pnl_bicgstab_block)
+    return _bicgstab_steps(A, B, X0, tol, maxiter, preconditioner)
+
+
+def _bicgstab_steps(A, B, X0, tol, maxiter, preconditioner):
+    """bicgstab_multi over the library's step calls, groups of 16 rows; the arguments have been checked"""
+    import torch
+    from ._lib import PNL_CGB_MAXVEC
+    from .linear_operators import _as_block
+    from .multigrid import multigrid as _multigrid
+    mg = preconditioner if isinstance(preconditioner, _multigrid) else getattr(preconditioner, 'multigrid', None)
+    if hasattr(A, 'assure_constructed'):
+        A.assure_constructed()
+    ctx = A.ctx if hasattr(A, 'ctx') else A.ops[0].ctx
+    device = getattr(A, 'device', None)
+    if device is None:
+        device = A.A.device if hasattr(A, 'A') else A._device()
+    Bd = _as_block(B, device)
+    nrhs, n = Bd.shape
+    assert nrhs >= 1 and n == A.num_rows == A.num_columns, (tuple(Bd.shape), A.shape)
+    X = torch.zeros((nrhs, n), dtype=torch.float64, device=device) if X0 is None else _as_block(X0, device).clone(
+        memory_format=torch.contiguous_format)
+    assert X.shape == Bd.shape, (tuple(X.shape), tuple(Bd.shape))
+    dinv = None
+    if preconditioner == 'jacobi':
+        d = A.diagonal
+        d = d() if callable(d) else d
+        dinv = 1./_dev_vector(d, device)
+    cycle = None
+    if mg is not None:
+        cycle = preconditioner if callable(preconditioner) else mg.cycle
+    its, res = np.zeros(nrhs, dtype=np.int32), np.zeros(nrhs)
+    for v0 in range(0, nrhs, PNL_CGB_MAXVEC):
+        v1 = min(nrhs, v0+PNL_CGB_MAXVEC)
+        _bicgstab_group(A, ctx, dinv, cycle, Bd[v0:v1], X[v0:v1], X0 is not None, tol, maxiter, its[v0:v1], res[v0:v1])
+    if isinstance(B, torch.Tensor):
+        return X, its, res
+    return X.cpu().numpy(), its, res
+
+
 def bicgstab(A, b, x0=None, tol=1e-8, maxiter=50, preconditioner=None):
     """bicgstab_solver.solve (solvers.pyx:716-787): right-preconditioned stabilised BiCG, r0 = B r, stopping on the 2-norm of
-    the residual.  Returns (x, iterations, residuals)."""
+    the residual.  Returns (x, iterations, residuals).  A 2-D b [nrhs, n] is a block of right-hand sides: ``bicgstab_multi``."""
+    if getattr(b, 'ndim', None) == 2 or (not hasattr(b, 'ndim') and np.ndim(b) == 2):
+        return bicgstab_multi(A, b, x0, tol, maxiter, preconditioner)
     import torch
     device = getattr(A, 'device', None)
     if device is None:
