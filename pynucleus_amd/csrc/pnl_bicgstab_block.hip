@@ -19,10 +19,11 @@
 // SEVEN work blocks [nvec][ld]: R (S lives in R's storage between the alpha and the omega step), P, R0, P2, S2, T, T2; plus dinv [n]
 // and the state.  T and T2 are both needed by the direction step, P2 and S2 both by the X update.
 //
-// Kernels, with the grid rule and the dot products of pnl_cgb_sums.h (cgb_blocks(n) workgroups of 256 threads, a grid-stride loop, a
+// Kernels, with the grid rule and the dot products of pnl_krylov_block.h (cgb_blocks(n) workgroups of 256 threads, a grid-stride loop, a
 // thread owns the same elements in every column; no floating-point atomics):
 //   k_bcgb_init      R = B - AX, P = R and, unless the preconditioner is external, R0 = P2 = dinv R with the partial sums of R . R0
-//   k_bcgb_dot       partial sums of one dot product per column (R . R0 of an external start; T . R0)        -> part[0]
+//   k_kb_dot         partial sums of one dot product per column (R . R0 of an external start; T . R0 of the active columns: behind
+//                    k_bcgb_begin and k_bcgb_finish these are the live ones)                                   -> part[0]
 //   k_bcgb_begin     one workgroup: kappa, res = sqrt(|kappa|), active = kappa is finite and not 0; the rest of the state 0
 //   k_bcgb_s         every workgroup adds the partials of T . R0 to get alpha; S = R - alpha T (in R's storage), S2 = dinv S: T, R and
 //                    dinv are read once
@@ -40,7 +41,7 @@
 // R = S, and the column converges by the normal test.  A column whose next scalar would be 0 / 0, x / 0 or not finite -- T . R0 == 0,
 // omega == 0 or kappaNew == 0 when it has not converged, any sum that is not finite -- is frozen BEFORE anything that is not finite is
 // written to one of its blocks, with the code PNL_BCGB_* in its state.
-#include "pnl_cgb_sums.h"
+#include "pnl_krylov_block.h"
 
 namespace {
 
@@ -48,6 +49,7 @@ namespace {
 enum { ST_KAPPA = 0, ST_ALPHA = 1, ST_OMEGA = 2, ST_RES = 3, ST_ACTIVE = 4, ST_KAPPA_NEW = 5, ST_CODE = 6, ST_TR0 = 7, ST_T2S = 8, ST_T2T2 = 9,
        ST_RR = 10, ST_BETA = 11 };
 static_assert(PNL_BCGB_STATE == 12, "the slots above");
+static_assert(ST_RES == KB_ST_RES && ST_ACTIVE == KB_ST_ACTIVE, "the slots that the drivers read");
 
 // bit v: column v < nv is live
 __device__ __forceinline__ unsigned bcgb_live_mask(const double *__restrict__ state, int nv) {
@@ -58,11 +60,7 @@ __device__ __forceinline__ unsigned bcgb_live_mask(const double *__restrict__ st
 }
 
 // bit v: column v < nv is active (the launches in front of which a column with a code is no longer active)
-__device__ __forceinline__ unsigned bcgb_active_mask(const double *__restrict__ state, int nv) {
-    unsigned m = 0;
-    for (int v = 0; v < nv; v++) m |= state[v*PNL_BCGB_STATE+ST_ACTIVE] != 0. ? 1u << v : 0u;
-    return m;
-}
+__device__ __forceinline__ unsigned bcgb_active_mask(const double *__restrict__ state, int nv) { return kb_active_mask<PNL_BCGB_STATE>(state, nv); }
 
 __device__ __forceinline__ bool bcgb_finite(double x) { return __builtin_isfinite(x); }
 
@@ -117,23 +115,6 @@ k_bcgb_init(int n, int nv, const double *__restrict__ dinv, const double *__rest
         }
     }
     if (!EXT) cgb_block_sums(s, mask, part+(size_t)blockIdx.x*CGB_NV);
-}
-
-// partial sums of U . V.  START: every column v < nv (there is no state yet); else the live ones
-template <bool START>
-__global__ void __launch_bounds__(CGB_THREADS)
-k_bcgb_dot(int n, int nv, const double *__restrict__ Uv, long long ldu, const double *__restrict__ Vv, long long ldv,
-           const double *__restrict__ state, double *__restrict__ part) {
-    const unsigned mask = START ? (1u << nv)-1u : bcgb_live_mask(state, nv);
-    double s[CGB_NV];
-#pragma unroll
-    for (int v = 0; v < CGB_NV; v++) s[v] = 0.;
-    for (int i = blockIdx.x*CGB_THREADS+threadIdx.x; i < n; i += gridDim.x*CGB_THREADS) {
-#pragma unroll
-        for (int v = 0; v < CGB_NV; v++)
-            if ((mask >> v) & 1) s[v] = __builtin_fma(Uv[v*ldu+i], Vv[v*ldv+i], s[v]);
-    }
-    cgb_block_sums(s, mask, part+(size_t)blockIdx.x*CGB_NV);
 }
 
 // one workgroup: the start state of every column v < nv from the partial sums of R . R0
@@ -328,29 +309,15 @@ k_bcgb_direction(int n, int nv, const double *__restrict__ dinv, const double *_
     }
 }
 
-// the context's scratch for the partial sums: [5][CGB_MAXBLK][16]: T . R0 (R . R0 at the start), T2 . S, T2 . T2, R . R, R . R0
-int bcgb_part(pnl_context *ctx, double **part) {
-    if (int rc = ensure(ctx, ctx->b_bcgb_part, sizeof(double)*5*CGB_PART)) return rc;
-    *part = (double*)ctx->b_bcgb_part.p;
-    return PNL_OK;
-}
-
+// the partial sums (kb_part): part[0] T . R0 (R . R0 at the start), [1] T2 . S, [2] T2 . T2, [3] R . R, [4] R . R0
 int bcgb_begin(pnl_context *ctx, int n, int nv, const double *part, double *state) {
-    hipLaunchKernelGGL(k_bcgb_begin, dim3(1), dim3(CGB_THREADS), 0, ctx->stream, cgb_blocks(n), nv, part, state);
+    KB_LAUNCH1(k_bcgb_begin, ctx, cgb_blocks(n), nv, part, state);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
 
-bool bcgb_bad_dims(int n, int nvec) { return n < 1 || nvec < 1 || nvec > CGB_NV; }
-
-// two of the pointers are the same block
-template <size_t N>
-bool bcgb_aliased(const void *const (&p)[N]) {
-    for (size_t a = 0; a < N; a++)
-        for (size_t b = a+1; b < N; b++)
-            if (p[a] && p[a] == p[b]) return true;
-    return false;
-}
+// a block that a step writes unless the preconditioner is external; then the step does not look at it
+KbBlock bcgb_own(int external, const void *p, int64_t ld) { return external ? KbBlock{nullptr, 0, KB_OPTIONAL} : KbBlock{p, ld, KB_WRITTEN}; }
 
 }  // namespace
 
@@ -360,33 +327,24 @@ int pnl_bcgb_init(pnl_context *ctx, int n, int nvec, int external, const double 
                   int64_t ldax, double *R_dev, int64_t ldr, double *P_dev, int64_t ldp, double *R0_dev, int64_t ldr0, double *P2_dev, int64_t ldp2,
                   double *state_dev) {
     if (!ctx) return PNL_ERR_INVALID;
-    const void *const blocks[] = {B_dev, AX_dev, R_dev, P_dev, external ? nullptr : R0_dev, external ? nullptr : P2_dev};
-    if (bcgb_bad_dims(n, nvec) || cgb_bad_block(B_dev, ldb, n) || cgb_bad_block(R_dev, ldr, n) || cgb_bad_block(P_dev, ldp, n) ||
-        (AX_dev && ldax < n) || (!external && (cgb_bad_block(R0_dev, ldr0, n) || cgb_bad_block(P2_dev, ldp2, n) || !state_dev)) || bcgb_aliased(blocks))
+    if (kb_bad_args(n, nvec, {{B_dev, ldb, KB_READ}, {AX_dev, ldax, KB_READ | KB_OPTIONAL}, {R_dev, ldr, KB_WRITTEN}, {P_dev, ldp, KB_WRITTEN},
+                              bcgb_own(external, R0_dev, ldr0), bcgb_own(external, P2_dev, ldp2)}, true) || (!external && !state_dev))
         return fail(ctx, PNL_ERR_INVALID, "pnl_bcgb_init: bad arguments (n=%d nvec=%d)", n, nvec);
     double *part;
-    if (int rc = bcgb_part(ctx, &part)) return rc;
-    const dim3 grid(cgb_blocks(n));
-    if (external) {
-        hipLaunchKernelGGL((k_bcgb_init<true>), grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, (const double*)nullptr, B_dev, (long long)ldb, AX_dev,
-                           (long long)ldax, R_dev, (long long)ldr, P_dev, (long long)ldp, (double*)nullptr, 0ll, (double*)nullptr, 0ll, part);
-        HIPCHK(ctx, hipGetLastError());
-        return PNL_OK;
-    }
-    hipLaunchKernelGGL((k_bcgb_init<false>), grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, dinv_dev, B_dev, (long long)ldb, AX_dev, (long long)ldax,
-                       R_dev, (long long)ldr, P_dev, (long long)ldp, R0_dev, (long long)ldr0, P2_dev, (long long)ldp2, part);
+    if (int rc = kb_part(ctx, &part)) return rc;
+    KB_LAUNCH(external ? k_bcgb_init<true> : k_bcgb_init<false>, ctx, n, nvec, dinv_dev, B_dev, ldb, AX_dev, ldax, R_dev, ldr, P_dev, ldp, R0_dev,
+              ldr0, P2_dev, ldp2, part);
     HIPCHK(ctx, hipGetLastError());
-    return bcgb_begin(ctx, n, nvec, part, state_dev);
+    return external ? PNL_OK : bcgb_begin(ctx, n, nvec, part, state_dev);
 }
 
 int pnl_bcgb_start(pnl_context *ctx, int n, int nvec, const double *R_dev, int64_t ldr, const double *R0_dev, int64_t ldr0, double *state_dev) {
     if (!ctx) return PNL_ERR_INVALID;
-    if (bcgb_bad_dims(n, nvec) || cgb_bad_block(R_dev, ldr, n) || cgb_bad_block(R0_dev, ldr0, n) || !state_dev)
+    if (kb_bad_args(n, nvec, {{R_dev, ldr, KB_READ}, {R0_dev, ldr0, KB_READ}}) || !state_dev)
         return fail(ctx, PNL_ERR_INVALID, "pnl_bcgb_start: bad arguments (n=%d nvec=%d)", n, nvec);
     double *part;
-    if (int rc = bcgb_part(ctx, &part)) return rc;
-    hipLaunchKernelGGL((k_bcgb_dot<true>), dim3(cgb_blocks(n)), dim3(CGB_THREADS), 0, ctx->stream, n, nvec, R_dev, (long long)ldr, R0_dev,
-                       (long long)ldr0, (const double*)state_dev, part);
+    if (int rc = kb_part(ctx, &part)) return rc;
+    KB_LAUNCH((k_kb_dot<PNL_BCGB_STATE, true>), ctx, n, nvec, R_dev, ldr, R0_dev, ldr0, state_dev, part);
     HIPCHK(ctx, hipGetLastError());
     return bcgb_begin(ctx, n, nvec, part, state_dev);
 }
@@ -394,19 +352,13 @@ int pnl_bcgb_start(pnl_context *ctx, int n, int nvec, const double *R_dev, int64
 int pnl_bcgb_alpha(pnl_context *ctx, int n, int nvec, int external, const double *dinv_dev, const double *T_dev, int64_t ldt, const double *R0_dev,
                    int64_t ldr0, double *RS_dev, int64_t ldr, double *S2_dev, int64_t lds2, double *state_dev) {
     if (!ctx) return PNL_ERR_INVALID;
-    const void *const blocks[] = {T_dev, R0_dev, RS_dev, external ? nullptr : S2_dev};
-    if (bcgb_bad_dims(n, nvec) || cgb_bad_block(T_dev, ldt, n) || cgb_bad_block(R0_dev, ldr0, n) || cgb_bad_block(RS_dev, ldr, n) ||
-        (!external && cgb_bad_block(S2_dev, lds2, n)) || !state_dev || bcgb_aliased(blocks))
+    if (kb_bad_args(n, nvec, {{T_dev, ldt, KB_READ}, {R0_dev, ldr0, KB_READ}, {RS_dev, ldr, KB_WRITTEN}, bcgb_own(external, S2_dev, lds2)}, true) ||
+        !state_dev)
         return fail(ctx, PNL_ERR_INVALID, "pnl_bcgb_alpha: bad arguments (n=%d nvec=%d)", n, nvec);
     double *part;
-    if (int rc = bcgb_part(ctx, &part)) return rc;
-    const dim3 grid(cgb_blocks(n));
-    hipLaunchKernelGGL((k_bcgb_dot<false>), grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, T_dev, (long long)ldt, R0_dev, (long long)ldr0,
-                       (const double*)state_dev, part);
-    if (external) hipLaunchKernelGGL((k_bcgb_s<true>), grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, (const double*)nullptr, T_dev, (long long)ldt,
-                                     RS_dev, (long long)ldr, (double*)nullptr, 0ll, state_dev, (const double*)part);
-    else hipLaunchKernelGGL((k_bcgb_s<false>), grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, dinv_dev, T_dev, (long long)ldt, RS_dev,
-                            (long long)ldr, S2_dev, (long long)lds2, state_dev, (const double*)part);
+    if (int rc = kb_part(ctx, &part)) return rc;
+    KB_LAUNCH((k_kb_dot<PNL_BCGB_STATE, false>), ctx, n, nvec, T_dev, ldt, R0_dev, ldr0, state_dev, part);
+    KB_LAUNCH(external ? k_bcgb_s<true> : k_bcgb_s<false>, ctx, n, nvec, dinv_dev, T_dev, ldt, RS_dev, ldr, S2_dev, lds2, state_dev, part);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
@@ -416,23 +368,15 @@ int pnl_bcgb_omega(pnl_context *ctx, int n, int nvec, const double *P2_dev, int6
                    double *state_dev) {
     if (!ctx) return PNL_ERR_INVALID;
     // what is written must stand alone; the blocks that are only read may coincide
-    const void *const written[] = {X_dev, RS_dev};
-    bool alias = bcgb_aliased(written);
-    for (const void *w : written)
-        for (const void *r : {(const void*)P2_dev, (const void*)S2_dev, (const void*)T2_dev, (const void*)R0_dev}) alias |= w == r;
-    if (bcgb_bad_dims(n, nvec) || cgb_bad_block(P2_dev, ldp2, n) || cgb_bad_block(S2_dev, lds2, n) || cgb_bad_block(T2_dev, ldt2, n) ||
-        cgb_bad_block(R0_dev, ldr0, n) || cgb_bad_block(X_dev, ldx, n) || cgb_bad_block(RS_dev, ldr, n) || !state_dev || alias)
+    if (kb_bad_args(n, nvec, {{P2_dev, ldp2, KB_READ}, {S2_dev, lds2, KB_READ}, {T2_dev, ldt2, KB_READ}, {R0_dev, ldr0, KB_READ},
+                              {X_dev, ldx, KB_WRITTEN}, {RS_dev, ldr, KB_WRITTEN}}) || !state_dev)
         return fail(ctx, PNL_ERR_INVALID, "pnl_bcgb_omega: bad arguments (n=%d nvec=%d)", n, nvec);
     double *part;
-    if (int rc = bcgb_part(ctx, &part)) return rc;
-    const dim3 grid(cgb_blocks(n));
-    hipLaunchKernelGGL(k_bcgb_dot2, grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, T2_dev, (long long)ldt2, (const double*)RS_dev, (long long)ldr,
-                       (const double*)state_dev, part+CGB_PART, part+2*CGB_PART);
-    hipLaunchKernelGGL(k_bcgb_xr, grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, P2_dev, (long long)ldp2, S2_dev, (long long)lds2, T2_dev,
-                       (long long)ldt2, X_dev, (long long)ldx, RS_dev, (long long)ldr, R0_dev, (long long)ldr0, state_dev,
-                       (const double*)(part+CGB_PART), (const double*)(part+2*CGB_PART), part+3*CGB_PART, part+4*CGB_PART);
-    hipLaunchKernelGGL(k_bcgb_finish, dim3(1), dim3(CGB_THREADS), 0, ctx->stream, cgb_blocks(n), nvec, (const double*)(part+3*CGB_PART),
-                       (const double*)(part+4*CGB_PART), tol, state_dev);
+    if (int rc = kb_part(ctx, &part)) return rc;
+    double *t2s = part+CGB_PART, *t2t2 = part+2*CGB_PART, *rr = part+3*CGB_PART, *rr0 = part+4*CGB_PART;
+    KB_LAUNCH(k_bcgb_dot2, ctx, n, nvec, T2_dev, ldt2, RS_dev, ldr, state_dev, t2s, t2t2);
+    KB_LAUNCH(k_bcgb_xr, ctx, n, nvec, P2_dev, ldp2, S2_dev, lds2, T2_dev, ldt2, X_dev, ldx, RS_dev, ldr, R0_dev, ldr0, state_dev, t2s, t2t2, rr, rr0);
+    KB_LAUNCH1(k_bcgb_finish, ctx, cgb_blocks(n), nvec, rr, rr0, tol, state_dev);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
@@ -440,15 +384,11 @@ int pnl_bcgb_omega(pnl_context *ctx, int n, int nvec, const double *P2_dev, int6
 int pnl_bcgb_direction(pnl_context *ctx, int n, int nvec, int external, const double *dinv_dev, const double *R_dev, int64_t ldr, const double *T_dev,
                        int64_t ldt, double *P_dev, int64_t ldp, double *P2_dev, int64_t ldp2, const double *state_dev) {
     if (!ctx) return PNL_ERR_INVALID;
-    const void *const blocks[] = {R_dev, T_dev, P_dev, external ? nullptr : P2_dev};
-    if (bcgb_bad_dims(n, nvec) || cgb_bad_block(R_dev, ldr, n) || cgb_bad_block(T_dev, ldt, n) || cgb_bad_block(P_dev, ldp, n) ||
-        (!external && cgb_bad_block(P2_dev, ldp2, n)) || !state_dev || bcgb_aliased(blocks))
+    if (kb_bad_args(n, nvec, {{R_dev, ldr, KB_READ}, {T_dev, ldt, KB_READ}, {P_dev, ldp, KB_WRITTEN}, bcgb_own(external, P2_dev, ldp2)}, true) ||
+        !state_dev)
         return fail(ctx, PNL_ERR_INVALID, "pnl_bcgb_direction: bad arguments (n=%d nvec=%d)", n, nvec);
-    const dim3 grid(cgb_blocks(n));
-    if (external) hipLaunchKernelGGL((k_bcgb_direction<true>), grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, (const double*)nullptr, R_dev,
-                                     (long long)ldr, T_dev, (long long)ldt, P_dev, (long long)ldp, (double*)nullptr, 0ll, state_dev);
-    else hipLaunchKernelGGL((k_bcgb_direction<false>), grid, dim3(CGB_THREADS), 0, ctx->stream, n, nvec, dinv_dev, R_dev, (long long)ldr, T_dev,
-                            (long long)ldt, P_dev, (long long)ldp, P2_dev, (long long)ldp2, state_dev);
+    KB_LAUNCH(external ? k_bcgb_direction<true> : k_bcgb_direction<false>, ctx, n, nvec, dinv_dev, R_dev, ldr, T_dev, ldt, P_dev, ldp, P2_dev,
+              ldp2, state_dev);
     HIPCHK(ctx, hipGetLastError());
     return PNL_OK;
 }
@@ -460,55 +400,37 @@ int pnl_bicgstab_block(pnl_context *ctx, const double *A_dev, int64_t ldA, int n
         (const void*)A_dev == (const void*)X_dev)
         return fail(ctx, PNL_ERR_INVALID, "pnl_bicgstab_block: bad arguments (n=%d nrhs=%d ldA=%lld ldb=%lld ldx=%lld maxiter=%d)", n, nrhs,
                     (long long)ldA, (long long)ldb, (long long)ldx, maxiter);
-    // work: dinv [n]; R, P, R0, P2, S2, T, T2 [16][ld]; the state [16][PNL_BCGB_STATE]
-    const int64_t ld = ((int64_t)n+1) & ~(int64_t)1;
+    // work: dinv [n]; R, P, R0, P2, S2, T, T2 [16][ld]; the state
+    const int64_t ld = kb_ld(n);
     const int gmax = std::min(nrhs, CGB_NV);
     int rc;
-    if ((rc = ensure(ctx, ctx->b_bcgb_work, sizeof(double)*(size_t)(ld+7*gmax*ld+CGB_NV*PNL_BCGB_STATE)))) return rc;
-    double *dwork = (double*)ctx->b_bcgb_work.p, *R = dwork+ld, *P = R+gmax*ld, *R0 = P+gmax*ld, *P2 = R0+gmax*ld, *S2 = P2+gmax*ld,
-           *T = S2+gmax*ld, *T2 = T+gmax*ld, *state = T2+gmax*ld;
-    const double *dinv = nullptr;
-    hipStream_t st = ctx->stream;
-    if (jacobi) {
-        if ((rc = pnl_inv_diagonal(ctx, A_dev, ldA, n, dwork))) return rc;
-        dinv = dwork;
-    }
-    double hs[CGB_NV*PNL_BCGB_STATE];
+    if ((rc = ensure(ctx, ctx->b_bcgb_work, kb_work_bytes(ld, 7, gmax, ld, PNL_BCGB_STATE)))) return rc;
+    double *dwork = (double*)ctx->b_bcgb_work.p;
+    KbCarve work{dwork+ld, gmax*ld};
+    double *R = work.next(), *P = work.next(), *R0 = work.next(), *P2 = work.next(), *S2 = work.next(), *T = work.next(), *T2 = work.next(),
+           *state = work.p;
+    if (jacobi && (rc = pnl_inv_diagonal(ctx, A_dev, ldA, n, dwork))) return rc;
+    const double *dinv = jacobi ? dwork : nullptr;
     for (int v0 = 0; v0 < nrhs; v0 += CGB_NV) {
         const int nv = std::min(CGB_NV, nrhs-v0);
         const double *B = B_dev+(int64_t)v0*ldb;
         double *X = X_dev+(int64_t)v0*ldx;
+        KbColumns<PNL_BCGB_STATE> cols{ctx, state, nv, iters ? iters+v0 : nullptr, residuals ? residuals+v0 : nullptr};
         auto product = [&](const double *V, int64_t ldv, double *W) {
             return pnl_gemv_block(ctx, A_dev, ldA, n, n, nv, V, ldv, 1., 0., nullptr, 0, W, ld);
         };
-        bool active[CGB_NV];
-        int nactive = 0;
-        // the columns that are active on the host and no longer on the device have converged or broken down in pass `it`
-        auto read_state = [&](int it) -> int {
-            HIPCHK(ctx, hipMemcpyAsync(hs, state, sizeof(double)*nv*PNL_BCGB_STATE, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            for (int v = 0; v < nv; v++) {
-                if (it >= 0 && !active[v]) continue;
-                if (residuals) residuals[v0+v] = hs[v*PNL_BCGB_STATE+ST_RES];
-                const bool on = hs[v*PNL_BCGB_STATE+ST_ACTIVE] != 0.;
-                if (it < 0) { active[v] = on; nactive += on; if (iters) iters[v0+v] = 0; }
-                else if (!on) { active[v] = false; nactive--; if (iters) iters[v0+v] = it; }
-            }
-            return PNL_OK;
-        };
         if ((rc = product(X, ldx, T))) return rc;
         if ((rc = pnl_bcgb_init(ctx, n, nv, 0, dinv, B, ldb, T, ld, R, ld, P, ld, R0, ld, P2, ld, state))) return rc;
-        if ((rc = read_state(-1))) return rc;
-        for (int it = 0; it < maxiter && nactive > 0; it++) {
+        if ((rc = cols.read(-1))) return rc;
+        for (int it = 0; it < maxiter && cols.nactive > 0; it++) {
             if ((rc = product(P2, ld, T))) return rc;
             if ((rc = pnl_bcgb_alpha(ctx, n, nv, 0, dinv, T, ld, R0, ld, R, ld, S2, ld, state))) return rc;
             if ((rc = product(S2, ld, T2))) return rc;
             if ((rc = pnl_bcgb_omega(ctx, n, nv, P2, ld, S2, ld, T2, ld, R0, ld, X, ldx, R, ld, tol, state))) return rc;
             if ((rc = pnl_bcgb_direction(ctx, n, nv, 0, dinv, R, ld, T, ld, P, ld, P2, ld, state))) return rc;
-            if ((rc = read_state(it))) return rc;
+            if ((rc = cols.read(it))) return rc;
         }
-        for (int v = 0; v < nv; v++)
-            if (active[v] && iters) iters[v0+v] = maxiter;
+        cols.end(maxiter);
     }
     return PNL_OK;
 }

@@ -145,8 +145,8 @@ struct pnl_context {
     DevBuf b_cholinfo;                // pnl_potrf (pnl_direct.hip): the word that takes the first pivot that is not positive
     DevBuf b_luwork, b_lutmp;         // pnl_getrf (pnl_direct.hip): info word, ticket, pivot rows, partial maxima; pnl_getrs: the permuted right-hand sides
     DevBuf b_blk_part, b_blk_xt;      // pnl_block.hip: partial sums of the column chunks [chunk][16][nrows]; the transposed group of vectors [n][NV]
-    DevBuf b_cgb_part, b_cgb_work;    // pnl_cg_block.hip: partial sums of the dot products [2][256][16]; pnl_cg_jacobi_block: dinv, R, P, AP, Z and the state
-    DevBuf b_bcgb_part, b_bcgb_work;  // pnl_bicgstab_block.hip: partial sums [5][256][16]; pnl_bicgstab_block: dinv, seven blocks and the state
+    DevBuf b_kb_part;                 // pnl_krylov_block.h: partial sums of the dot products of the block Krylov steps [5][256][16]
+    DevBuf b_cgb_work, b_bcgb_work;   // pnl_cg_jacobi_block: dinv, R, P, AP, Z and the state; pnl_bicgstab_block: dinv, seven blocks and the state
     std::vector<int32_t> slab_rowdofs, slab_coldofs;
     int slab_rows = 0, slab_cols = 0;
     std::vector<DevKernel> kcls_host;

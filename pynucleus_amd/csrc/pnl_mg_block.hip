@@ -22,18 +22,15 @@
 //
 // pnl_mg_cg_block is the loop of pnl_mg_cg around pnl_gemv_block (A P), pnl_mg_cycle_block (Z = cycle(R) from a zero guess) and the
 // external-preconditioner steps of pnl_cg_block.hip; the host reads the state of the group back once per iteration.
-#include "pnl_context.h"
-#include "pnl_common.h"
+#include "pnl_krylov_block.h"
 #include "pnl_mg.h"
 
 namespace {
 
-constexpr int MGB_NV = PNL_CGB_MAXVEC;      // columns per group = vectors per pass of pnl_gemv_block
+constexpr int MGB_NV = CGB_NV;              // columns per group = vectors per pass of pnl_gemv_block
 constexpr int MGB_THREADS = 256;
-enum { ST_CONV = 3, ST_ACTIVE = 4 };         // slots of the per-column state (include/pnl_hip.h)
 
 inline unsigned mgb_blocks(int n) { return (unsigned)((n+MGB_THREADS-1)/MGB_THREADS); }
-inline int64_t mgb_ld(int n) { return ((int64_t)n+1) & ~(int64_t)1; }
 
 // damped Jacobi on a block: X[v][i] += invD[i] R[v][i]  (SET: X[v][i] = invD[i] R[v][i], the sweep from a zero guess; X is not read).
 // One thread per i: invD[i] is loaded once for the nv columns, the loads and stores of every column are coalesced along i.
@@ -111,7 +108,7 @@ int ensure_blocks(pnl_mg *mg) {
     const int nl = mg->nlevels;
     if ((int)mg->btemp.size() != nl) { mg->brhs.resize(nl); mg->bsol.resize(nl); mg->btemp.resize(nl); }
     for (int l = 0; l < nl; l++) {
-        const size_t bytes = sizeof(double)*(size_t)MGB_NV*(size_t)mgb_ld(mg->lv[l].n);
+        const size_t bytes = sizeof(double)*(size_t)MGB_NV*(size_t)kb_ld(mg->lv[l].n);
         int rc;
         if (l < nl-1 && ((rc = ensure(ctx, mg->brhs[l], bytes)) || (rc = ensure(ctx, mg->bsol[l], bytes)))) return rc;
         if (l > 0 && (rc = ensure(ctx, mg->btemp[l], bytes))) return rc;
@@ -129,7 +126,7 @@ int residual(pnl_mg *mg, int l, int nv, const double *B, int64_t ldb, const doub
 int smooth_block(pnl_mg *mg, int l, int nv, const double *B, int64_t ldb, double *X, int64_t ldx, int steps, bool simple) {
     pnl_context *ctx = mg->ctx;
     const int n = mg->lv[l].n;
-    const int64_t ldt = mgb_ld(n);
+    const int64_t ldt = kb_ld(n);
     double *T = (double*)mg->btemp[l].p;
     const double *invD = (const double*)mg->invD[l].p;
     int rc;
@@ -151,7 +148,7 @@ int solve_on_level_block(pnl_mg *mg, int l, int nv, const double *B, int64_t ldb
     const pnl_mg_level_desc &L = mg->lv[l];
     if (l == 0) return pnl_gemv_block(ctx, mg->coarse_inv, L.n, L.n, L.n, nv, B, ldb, 1., 0., nullptr, 0, X, ldx);     // X = A_0^{-1} B
     const pnl_mg_level_desc &C = mg->lv[l-1];
-    const int64_t ldt = mgb_ld(L.n), ldc = mgb_ld(C.n);
+    const int64_t ldt = kb_ld(L.n), ldc = kb_ld(C.n);
     double *T = (double*)mg->btemp[l].p, *defect = (double*)mg->brhs[l-1].p, *solcg = (double*)mg->bsol[l-1].p;
     int rc;
     if ((rc = smooth_block(mg, l, nv, B, ldb, X, ldx, mg->pre, simple))) return rc;
@@ -208,46 +205,26 @@ int pnl_mg_cg_block(pnl_mg *mg, const double *A_dev, int64_t ldA, int nrhs, cons
     if (!A_dev || ldA < n || maxiter < 0)
         return fail(ctx, PNL_ERR_INVALID, "pnl_mg_cg_block: no operator, ldA < n or maxiter < 0 (n=%d ldA=%lld maxiter=%d)", n, (long long)ldA, maxiter);
     if ((rc = ensure_blocks(mg))) return rc;
-    // work: R, P, AP, Z [16][ld]; the state [16][PNL_CGB_STATE]
-    const int64_t ld = mgb_ld(n);
-    const int gmax = std::min(nrhs, MGB_NV);
-    if ((rc = ensure(ctx, mg->bcg, sizeof(double)*(size_t)(4*MGB_NV*ld+MGB_NV*PNL_CGB_STATE)))) return rc;
-    double *R = (double*)mg->bcg.p, *P = R+gmax*ld, *AP = P+gmax*ld, *Z = AP+gmax*ld, *state = R+4*MGB_NV*ld;
-    hipStream_t st = ctx->stream;
-    double hs[MGB_NV*PNL_CGB_STATE];
+    // work: R, P, AP, Z [16][ld]; the state
+    const int64_t ld = kb_ld(n);
+    if ((rc = ensure(ctx, mg->bcg, kb_work_bytes(0, 4, MGB_NV, ld, PNL_CGB_STATE)))) return rc;
+    KbCarve work{(double*)mg->bcg.p, std::min(nrhs, MGB_NV)*ld};
+    double *R = work.next(), *P = work.next(), *AP = work.next(), *Z = work.next(), *state = work.p;
     for (int v0 = 0; v0 < nrhs; v0 += MGB_NV) {
         const int nv = std::min(MGB_NV, nrhs-v0);
         const double *B = B_dev+(int64_t)v0*ldb;
         double *X = X_dev+(int64_t)v0*ldx;
+        KbColumns<PNL_CGB_STATE> cols{ctx, state, nv, iters ? iters+v0 : nullptr, residuals ? residuals+v0 : nullptr};
         auto product = [&](const double *V, int64_t ldv) { return pnl_gemv_block(ctx, A_dev, ldA, n, n, nv, V, ldv, 1., 0., nullptr, 0, AP, ld); };
         // one V cycle from a zero guess for the whole group: its cost does not depend on the frozen columns, whose Z is not used
         auto precond = [&]() { return solve_on_level_block(mg, top, nv, R, ld, Z, ld, true); };
-        bool active[MGB_NV];
-        int nactive = 0;
-        // the columns that are active on the host and no longer on the device have converged in pass `it`
-        auto read_state = [&](int it) -> int {
-            HIPCHK(ctx, hipMemcpyAsync(hs, state, sizeof(double)*nv*PNL_CGB_STATE, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            for (int v = 0; v < nv; v++) {
-                if (it >= 0 && !active[v]) continue;
-                if (residuals) residuals[v0+v] = hs[v*PNL_CGB_STATE+ST_CONV];
-                const bool on = hs[v*PNL_CGB_STATE+ST_ACTIVE] != 0.;
-                if (it < 0) { active[v] = on; nactive += on; if (iters) iters[v0+v] = 0; }
-                else if (!on) { active[v] = false; nactive--; if (iters) iters[v0+v] = it; }
-            }
-            return PNL_OK;
-        };
-        if (x_is_zero) {                                                            // the caller's X holds zeros, as for pnl_mg_cg
-            if ((rc = pnl_cgb_residual(ctx, n, nv, B, ldb, nullptr, 0, R, ld, nullptr))) return rc;
-        } else {
-            if ((rc = product(X, ldx))) return rc;
-            if ((rc = pnl_cgb_residual(ctx, n, nv, B, ldb, AP, ld, R, ld, nullptr))) return rc;
-        }
+        if (!x_is_zero && (rc = product(X, ldx))) return rc;                        // else the caller's X holds zeros, as for pnl_mg_cg
+        if ((rc = pnl_cgb_residual(ctx, n, nv, B, ldb, x_is_zero ? nullptr : AP, ld, R, ld, nullptr))) return rc;
         if ((rc = precond())) return rc;
         if ((rc = pnl_cgb_start(ctx, n, nv, R, ld, Z, ld, P, ld, tol, state))) return rc;
-        if ((rc = read_state(-1))) return rc;
+        if ((rc = cols.read(-1))) return rc;
         int k = 0;
-        for (int it = 0; it < maxiter && nactive > 0; it++) {
+        for (int it = 0; it < maxiter && cols.nactive > 0; it++) {
             if ((rc = product(P, ld))) return rc;
             if ((rc = pnl_cgb_step(ctx, n, nv, P, ld, AP, ld, X, ldx, R, ld, state))) return rc;
             if (k == 50) {
@@ -259,11 +236,10 @@ int pnl_mg_cg_block(pnl_mg *mg, const double *A_dev, int64_t ldA, int nrhs, cons
             if ((rc = precond())) return rc;
             if ((rc = pnl_cgb_beta(ctx, n, nv, R, ld, Z, ld, state))) return rc;
             if ((rc = pnl_cgb_direction(ctx, n, nv, Z, ld, P, ld, tol, state))) return rc;
-            if ((rc = read_state(it))) return rc;
+            if ((rc = cols.read(it))) return rc;
             k++;
         }
-        for (int v = 0; v < nv; v++)
-            if (active[v] && iters) iters[v0+v] = maxiter;
+        cols.end(maxiter);
     }
     return PNL_OK;
 }

@@ -33,7 +33,18 @@ def _as_block(X, device):
     return Xd
 
 
-def _block_out(X, Yd, Y):
+def _rhs_blocks(B, X0, device, n):
+    """the right-hand sides B [nrhs, n] and the guesses X0 (None: zeros) of a block solve on ``device``: (Bd, Xd), Bd as ``_as_block``
+    gives it, Xd a contiguous copy that takes the result"""
+    Bd = _as_block(B, device)
+    assert Bd.shape[0] >= 1 and Bd.shape[1] == n, (tuple(Bd.shape), n)
+    Xd = torch.zeros(tuple(Bd.shape), dtype=torch.float64, device=device) if X0 is None else _as_block(X0, device).clone(
+        memory_format=torch.contiguous_format)
+    assert Xd.shape == Bd.shape, (tuple(Xd.shape), tuple(Bd.shape))
+    return Bd, Xd
+
+
+def _block_out(X, Yd, Y=None):
     """torch in / torch out, else numpy; ``Y`` is filled and returned if given"""
     if isinstance(X, torch.Tensor):
         if Y is not None:
@@ -189,20 +200,13 @@ class Dense_LinearOperator(blockProducts):
         over the block per iteration and 16 rows.  Returns (X, iterations[nrhs], residuals[nrhs] in the preconditioner norm); torch
         in, torch out, else numpy.  The block is read in full (no half-read as ``solve_cg_jacobi``); no float atomics: the bits of a
         row do not depend on the other rows."""
-        dev = self.A.device
-        assert self.num_rows == self.num_columns
-        Bd = _as_block(B, dev)
-        k = Bd.shape[0]
-        assert k >= 1 and Bd.shape[1] == self.num_rows, (tuple(Bd.shape), self.num_rows)
-        Xd = torch.zeros((k, self.num_rows), dtype=torch.float64, device=dev) if X0 is None else _as_block(X0, dev).clone(
-            memory_format=torch.contiguous_format)
-        assert Xd.shape == Bd.shape, (tuple(Xd.shape), tuple(Bd.shape))
+        dev, n = self.A.device, self.num_rows
+        assert n == self.num_columns
+        Bd, Xd = _rhs_blocks(B, X0, dev, n)
         torch.cuda.current_stream(dev).synchronize()
-        its, res = self.ctx.cg_jacobi_block(self.A.data_ptr(), max(int(self.A.stride(0)), self.num_rows), self.num_rows, k,
-                                            Bd.data_ptr(), max(int(Bd.stride(0)), self.num_rows), Xd.data_ptr(), self.num_rows, tol, maxiter)
-        if isinstance(B, torch.Tensor):
-            return Xd, its, res
-        return Xd.cpu().numpy(), its, res
+        its, res = self.ctx.cg_jacobi_block(self.A.data_ptr(), max(int(self.A.stride(0)), n), n, Bd.shape[0], Bd.data_ptr(),
+                                            max(int(Bd.stride(0)), n), Xd.data_ptr(), n, tol, maxiter)
+        return _block_out(B, Xd), its, res
 
     def solve_bicgstab_block(self, B, X0=None, tol=1e-8, maxiter=50, preconditioner=None):
         """BiCGStab for the rows of B [nrhs, n] at once (pnl_bicgstab_block), the operator square and general (nothing assumes symmetry):
@@ -211,21 +215,13 @@ class Dense_LinearOperator(blockProducts):
         row do not depend on the other rows.  iterations < maxiter with residual >= tol: the recurrence of that row broke down."""
         if preconditioner not in (None, 'jacobi'):
             raise NotImplementedError(preconditioner)
-        dev = self.A.device
-        assert self.num_rows == self.num_columns
-        Bd = _as_block(B, dev)
-        k = Bd.shape[0]
-        assert k >= 1 and Bd.shape[1] == self.num_rows, (tuple(Bd.shape), self.num_rows)
-        Xd = torch.zeros((k, self.num_rows), dtype=torch.float64, device=dev) if X0 is None else _as_block(X0, dev).clone(
-            memory_format=torch.contiguous_format)
-        assert Xd.shape == Bd.shape, (tuple(Xd.shape), tuple(Bd.shape))
+        dev, n = self.A.device, self.num_rows
+        assert n == self.num_columns
+        Bd, Xd = _rhs_blocks(B, X0, dev, n)
         torch.cuda.current_stream(dev).synchronize()
-        its, res = self.ctx.bicgstab_block(self.A.data_ptr(), max(int(self.A.stride(0)), self.num_rows), self.num_rows, k,
-                                           preconditioner == 'jacobi', Bd.data_ptr(), max(int(Bd.stride(0)), self.num_rows), Xd.data_ptr(),
-                                           self.num_rows, tol, maxiter)
-        if isinstance(B, torch.Tensor):
-            return Xd, its, res
-        return Xd.cpu().numpy(), its, res
+        its, res = self.ctx.bicgstab_block(self.A.data_ptr(), max(int(self.A.stride(0)), n), n, Bd.shape[0], preconditioner == 'jacobi',
+                                           Bd.data_ptr(), max(int(Bd.stride(0)), n), Xd.data_ptr(), n, tol, maxiter)
+        return _block_out(B, Xd), its, res
 
     def solve_direct(self, b):
         """x with A x = b through the Cholesky factor (solvers.chol; a symmetric operator) or the pivoted LU factors (solvers.plu; any

@@ -471,15 +471,9 @@ class multigrid:
             raise NotImplementedError('multigrid on a block of right-hand sides: a block cycle with an H2 operator on the finest level is not built')
 
     def _blocks(self, B, X):
-        import torch
-        from .linear_operators import _as_block
-        Bd = _as_block(B, self.device)
-        nrhs, n = Bd.shape
-        assert nrhs >= 1 and n == self.num_rows, (tuple(Bd.shape), self.num_rows)
-        Xd = torch.zeros((nrhs, n), dtype=torch.float64, device=self.device) if X is None else _as_block(X, self.device).clone(
-            memory_format=torch.contiguous_format)
-        assert Xd.shape == Bd.shape, (tuple(Xd.shape), tuple(Bd.shape))
-        return Bd, Xd, nrhs, n
+        from .linear_operators import _rhs_blocks
+        Bd, Xd = _rhs_blocks(B, X, self.device, self.num_rows)
+        return (Bd, Xd)+tuple(Bd.shape)
 
     def _cycle_block(self, B, X=None):
         import torch

@@ -32,17 +32,13 @@ def cg(A, b, x0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
     if getattr(b, 'ndim', None) == 2 or (not hasattr(b, 'ndim') and np.ndim(b) == 2):
         return cg_multi(A, b, x0, tol, maxiter, preconditioner)
     import torch
-    device = getattr(A, 'device', None)
-    if device is None:
-        device = A.A.device if hasattr(A, 'A') else torch.device('cuda', torch.cuda.current_device())
+    device = _device_of(A)
     bd = _dev_vector(b, device)
     x = torch.zeros_like(bd) if x0 is None else _dev_vector(x0, device).clone()
     dinv = None
     B = None
     if preconditioner == 'jacobi':
-        d = A.diagonal
-        d = d() if callable(d) else d
-        dinv = 1./_dev_vector(d, device)
+        dinv = _jacobi_dinv(A, device)
     elif callable(preconditioner):
         # r -> B r on device vectors, e.g. multigrid.asPreconditioner() (multigridPreconditioner, multigrid_{SCALAR}.pxi:470-497)
         B = preconditioner
@@ -90,112 +86,224 @@ def cg(A, b, x0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
     return x.cpu().numpy(), its, residuals
 
 
-def _cg_group(A, ctx, dinv, B, X, have_x0, tol, maxiter, its, res):
-    """the loop of pnl_cg_jacobi_block (csrc/pnl_cg_block.hip) for at most 16 rows of B, with ``A.matvec_multi`` as the product and the
-    library's step calls on device blocks; X [nv, n] contiguous holds the guesses and the results, its / res are filled"""
-    import torch
-    from ._lib import PNL_CGB_STATE
-    nv, n = B.shape
-    dev = B.device
-    R, P, Z = (torch.empty((nv, n), dtype=torch.float64, device=dev) for _ in range(3))
-    state = torch.zeros(nv*PNL_CGB_STATE, dtype=torch.float64, device=dev)
-    dp = dinv.data_ptr() if dinv is not None else 0
-    ldb = max(int(B.stride(0)), n)
+class _Group:
+    """At most 16 rows of a block solve over the library's step calls: the device blocks, ``A.matvec_multi`` as the product, the fences
+    between the context's stream and torch's, the read-back of the state and the record of the rows.  A recurrence supplies
+    ``start(AX_ptr)`` and ``one_pass(it)`` (``run``).  B [nv, n] with a unit inner stride; X [nv, n] contiguous holds the guesses and
+    the results."""
 
-    def product(V):
-        ctx.synchronize()
-        W = A.matvec_multi(V)
-        torch.cuda.current_stream(dev).synchronize()
+    def __init__(self, A, ctx, B, X):
+        self.A, self.ctx, self.B, self.X = A, ctx, B, X
+        (self.nv, self.n), self.dev = B.shape, B.device
+        self.ldb = max(int(B.stride(0)), self.n)
+
+    def blocks(self, k):
+        import torch
+        return tuple(torch.empty((self.nv, self.n), dtype=torch.float64, device=self.dev) for _ in range(k))
+
+    def new_state(self, width):
+        import torch
+        self.width = width
+        self.state = torch.zeros(self.nv*width, dtype=torch.float64, device=self.dev)
+        return self.state.data_ptr()
+
+    def fence(self):
+        import torch
+        torch.cuda.current_stream(self.dev).synchronize()
+
+    def product(self, V):
+        self.ctx.synchronize()
+        W = self.A.matvec_multi(V)
+        self.fence()
         return W
 
-    def read_state():
-        ctx.synchronize()
-        return state.cpu().numpy().reshape(nv, PNL_CGB_STATE)
-
-    AX = product(X) if have_x0 else None
-    torch.cuda.current_stream(dev).synchronize()
-    ctx.cgb_init(n, nv, dp, B.data_ptr(), ldb, AX.data_ptr() if AX is not None else 0, n, R.data_ptr(), n, P.data_ptr(), n, tol, state.data_ptr())
-    st = read_state()
-    res[:] = st[:, 3]
-    its[:] = 0
-    active = st[:, 4] != 0.
-    k = 0
-    for it in range(maxiter):
-        if not active.any():
-            break
-        AP = product(P)
-        ctx.cgb_update(n, nv, dp, P.data_ptr(), n, AP.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, Z.data_ptr(), n, state.data_ptr())
-        if k == 50:
-            AX = product(X)                             # recalculate the residual to avoid rounding errors
-            ctx.cgb_refresh(n, nv, dp, B.data_ptr(), ldb, AX.data_ptr(), n, R.data_ptr(), n, Z.data_ptr(), n, state.data_ptr())
-            k = 0
-        ctx.cgb_direction(n, nv, Z.data_ptr(), n, P.data_ptr(), n, tol, state.data_ptr())
-        st = read_state()
-        res[active] = st[active, 3]
-        done = active & (st[:, 4] == 0.)
-        its[done] = it
-        active &= ~done
-        k += 1
-    its[active] = maxiter
-
-
-def _cg_group_mg(A, ctx, cycle, B, X, have_x0, tol, maxiter, its, res):
-    """the loop of pnl_mg_cg_block (csrc/pnl_mg_block.hip) for at most 16 rows of B, with ``A.matvec_multi`` as the product, ``cycle``
-    (R [nv, n] -> Z, one V cycle from a zero guess for every row: multigrid.cycle on a block) as the preconditioner and the library's
-    external-preconditioner steps on device blocks; X [nv, n] contiguous holds the guesses and the results, its / res are filled"""
-    import torch
-    from ._lib import PNL_CGB_STATE
-    nv, n = B.shape
-    dev = B.device
-    R, P = (torch.empty((nv, n), dtype=torch.float64, device=dev) for _ in range(2))
-    state = torch.zeros(nv*PNL_CGB_STATE, dtype=torch.float64, device=dev)
-    ldb = max(int(B.stride(0)), n)
-
-    def product(V):
-        ctx.synchronize()
-        W = A.matvec_multi(V)
-        torch.cuda.current_stream(dev).synchronize()
-        return W
-
-    def precondition():
-        ctx.synchronize()
-        Z = cycle(R).contiguous()
-        torch.cuda.current_stream(dev).synchronize()
+    def apply(self, cycle, V, out=None):
+        """cycle(V) (a block [nv, n] -> M^-1 of every row: multigrid.cycle), contiguous or copied into ``out``"""
+        self.ctx.synchronize()
+        Z = cycle(V)
+        Z = Z.contiguous() if out is None else out.copy_(Z)
+        self.fence()
         return Z
 
-    def read_state():
-        ctx.synchronize()
-        return state.cpu().numpy().reshape(nv, PNL_CGB_STATE)
+    def read_state(self):
+        self.ctx.synchronize()
+        return self.state.cpu().numpy().reshape(self.nv, self.width)
 
-    AX = product(X) if have_x0 else None
-    torch.cuda.current_stream(dev).synchronize()
-    ctx.cgb_residual(n, nv, B.data_ptr(), ldb, AX.data_ptr() if AX is not None else 0, n, R.data_ptr(), n, 0)
-    Z = precondition()
-    ctx.cgb_start(n, nv, R.data_ptr(), n, Z.data_ptr(), n, P.data_ptr(), n, tol, state.data_ptr())
-    st = read_state()
-    res[:] = st[:, 3]
-    its[:] = 0
-    active = st[:, 4] != 0.
-    k = 0
-    for it in range(maxiter):
-        if not active.any():
-            break
-        AP = product(P)
-        ctx.cgb_step(n, nv, P.data_ptr(), n, AP.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, state.data_ptr())
-        if k == 50:
-            AX = product(X)                             # recalculate the residual to avoid rounding errors
-            ctx.cgb_residual(n, nv, B.data_ptr(), ldb, AX.data_ptr(), n, R.data_ptr(), n, state.data_ptr())
-            k = 0
-        Z = precondition()
-        ctx.cgb_beta(n, nv, R.data_ptr(), n, Z.data_ptr(), n, state.data_ptr())
-        ctx.cgb_direction(n, nv, Z.data_ptr(), n, P.data_ptr(), n, tol, state.data_ptr())
-        st = read_state()
-        res[active] = st[active, 3]
-        done = active & (st[:, 4] == 0.)
-        its[done] = it
-        active &= ~done
-        k += 1
-    its[active] = maxiter
+    def run(self, start, one_pass, have_x0, maxiter, its, res):
+        """its / res are filled: the rows that are active here and no longer on the device have ended in that pass (state slot 3 is the
+        residual, slot 4 the active flag, for every solver)"""
+        AX = self.product(self.X) if have_x0 else None
+        self.fence()
+        start(AX.data_ptr() if AX is not None else 0)
+        st = self.read_state()
+        res[:] = st[:, 3]
+        its[:] = 0
+        active = st[:, 4] != 0.
+        for it in range(maxiter):
+            if not active.any():
+                break
+            one_pass(it)
+            st = self.read_state()
+            res[active] = st[active, 3]
+            done = active & (st[:, 4] == 0.)
+            its[done] = it
+            active &= ~done
+        its[active] = maxiter
+
+
+def _cg_recurrence(g, dinv, tol):
+    """the loop of pnl_cg_jacobi_block (csrc/pnl_cg_block.hip) over its fused steps; ``dinv`` None: the unit diagonal"""
+    from ._lib import PNL_CGB_STATE
+    ctx, n, nv, B, X, sp = g.ctx, g.n, g.nv, g.B, g.X, g.new_state(PNL_CGB_STATE)
+    R, P, Z = g.blocks(3)
+    dp = dinv.data_ptr() if dinv is not None else 0
+
+    def start(AX):
+        ctx.cgb_init(n, nv, dp, B.data_ptr(), g.ldb, AX, n, R.data_ptr(), n, P.data_ptr(), n, tol, sp)
+
+    def one_pass(it):
+        AP = g.product(P)
+        ctx.cgb_update(n, nv, dp, P.data_ptr(), n, AP.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, Z.data_ptr(), n, sp)
+        if it > 0 and it % 50 == 0:
+            AX = g.product(X)                           # recalculate the residual to avoid rounding errors
+            ctx.cgb_refresh(n, nv, dp, B.data_ptr(), g.ldb, AX.data_ptr(), n, R.data_ptr(), n, Z.data_ptr(), n, sp)
+        ctx.cgb_direction(n, nv, Z.data_ptr(), n, P.data_ptr(), n, tol, sp)
+    return start, one_pass
+
+
+def _cg_mg_recurrence(g, cycle, tol):
+    """the loop of pnl_mg_cg_block (csrc/pnl_mg_block.hip) over the external-preconditioner steps, ``cycle`` (one V cycle from a zero
+    guess for every row) applied between them"""
+    from ._lib import PNL_CGB_STATE
+    ctx, n, nv, B, X, sp = g.ctx, g.n, g.nv, g.B, g.X, g.new_state(PNL_CGB_STATE)
+    R, P = g.blocks(2)
+
+    def start(AX):
+        ctx.cgb_residual(n, nv, B.data_ptr(), g.ldb, AX, n, R.data_ptr(), n, 0)
+        Z = g.apply(cycle, R)
+        ctx.cgb_start(n, nv, R.data_ptr(), n, Z.data_ptr(), n, P.data_ptr(), n, tol, sp)
+
+    def one_pass(it):
+        AP = g.product(P)
+        ctx.cgb_step(n, nv, P.data_ptr(), n, AP.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, sp)
+        if it > 0 and it % 50 == 0:
+            AX = g.product(X)                           # recalculate the residual to avoid rounding errors
+            ctx.cgb_residual(n, nv, B.data_ptr(), g.ldb, AX.data_ptr(), n, R.data_ptr(), n, sp)
+        Z = g.apply(cycle, R)
+        ctx.cgb_beta(n, nv, R.data_ptr(), n, Z.data_ptr(), n, sp)
+        ctx.cgb_direction(n, nv, Z.data_ptr(), n, P.data_ptr(), n, tol, sp)
+    return start, one_pass
+
+
+def _bicgstab_recurrence(g, pre, tol):
+    """the loop of pnl_bicgstab_block (csrc/pnl_bicgstab_block.hip) over its steps.  ``pre`` a callable: the external mode, ``pre`` (a
+    block cycle) applied here between the steps; else ``pre`` is dinv (None: the unit diagonal), applied by the steps"""
+    from ._lib import PNL_BCGB_STATE
+    ctx, n, nv, B, X, sp = g.ctx, g.n, g.nv, g.B, g.X, g.new_state(PNL_BCGB_STATE)
+    ext = callable(pre)
+    cycle = pre
+    R, P, R0, P2, S2 = g.blocks(5)
+    dp = pre.data_ptr() if pre is not None and not ext else 0
+
+    def start(AX):
+        ctx.bcgb_init(n, nv, ext, dp, B.data_ptr(), g.ldb, AX, n, R.data_ptr(), n, P.data_ptr(), n, R0.data_ptr(), n, P2.data_ptr(), n, sp)
+        if ext:
+            g.apply(cycle, R, R0)
+            P2.copy_(R0)                                # P = R at the start
+            g.fence()
+            ctx.bcgb_start(n, nv, R.data_ptr(), n, R0.data_ptr(), n, sp)
+
+    def one_pass(it):
+        T = g.product(P2)
+        ctx.bcgb_alpha(n, nv, ext, dp, T.data_ptr(), n, R0.data_ptr(), n, R.data_ptr(), n, S2.data_ptr(), n, sp)
+        if ext:
+            g.apply(cycle, R, S2)                       # S lives in R between the two steps
+        T2 = g.product(S2)
+        ctx.bcgb_omega(n, nv, P2.data_ptr(), n, S2.data_ptr(), n, T2.data_ptr(), n, R0.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, tol, sp)
+        ctx.bcgb_direction(n, nv, ext, dp, R.data_ptr(), n, T.data_ptr(), n, P.data_ptr(), n, P2.data_ptr(), n, sp)
+        if ext:
+            g.apply(cycle, P, P2)
+    return start, one_pass
+
+
+def _device_of(A, constructed=False):
+    """the device of the vectors of an operator.  One that shows neither ``device`` nor a dense block is asked (``_device()``) only
+    once it is ``constructed``, as the block front end has seen to; else the current device stands in"""
+    import torch
+    device = getattr(A, 'device', None)
+    if device is None:
+        device = A.A.device if hasattr(A, 'A') else (A._device() if constructed else torch.device('cuda', torch.cuda.current_device()))
+    return device
+
+
+def _jacobi_dinv(A, device):
+    d = A.diagonal
+    d = d() if callable(d) else d
+    return 1./_dev_vector(d, device)
+
+
+def _block_preconditioner(name, A, preconditioner):
+    """what ``name`` (cg_multi, bicgstab_multi) takes: the multigrid behind ``preconditioner`` (None for 'jacobi' and None) if A and it
+    are fit for a block of right-hand sides, NotImplementedError if not"""
+    from .multigrid import multigrid as _multigrid
+    from .linear_operators import DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator
+    from .distributed_h2 import DistributedH2Matrix_localData
+    # a multigrid object, or the callable of its asPreconditioner(): the block cycle of that hierarchy
+    mg = preconditioner if isinstance(preconditioner, _multigrid) else getattr(preconditioner, 'multigrid', None)
+    if mg is None and callable(preconditioner):
+        raise NotImplementedError('{}: a plain callable as preconditioner for a block of right-hand sides is not built '
+                                  '(pass a multigrid object or its asPreconditioner())'.format(name))
+    if mg is None and preconditioner not in ('jacobi', None):
+        raise NotImplementedError(preconditioner)
+    if isinstance(A, (DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator,
+                      DistributedH2Matrix_localData)):
+        raise NotImplementedError('{}: the block products of the distributed operators loop their matvec; solve row by row with {}'.format(
+            name, name[:-len('_multi')]))
+    if not hasattr(A, 'matvec_multi'):
+        raise NotImplementedError('{} needs an operator with matvec_multi; got {!r}'.format(name, A))
+    if mg is not None:
+        mg._require_block()                                 # NotImplementedError for a Chebyshev smoother, H2 / sparse levels
+    return mg
+
+
+def _block_steps(name, A, B, X0, tol, maxiter, preconditioner, library=None):
+    """``name`` (cg_multi, bicgstab_multi): the checks, then ``library(mg)`` -- the solver's fast paths into the library, which returns
+    None where none applies -- and else the loop over the library's step calls, groups of 16 rows"""
+    from ._lib import PNL_CGB_MAXVEC
+    from .linear_operators import _rhs_blocks, _block_out
+    mg = _block_preconditioner(name, A, preconditioner)
+    out = library(mg) if library is not None else None
+    if out is not None:
+        return out
+    if hasattr(A, 'assure_constructed'):
+        A.assure_constructed()
+    ctx = A.ctx if hasattr(A, 'ctx') else A.ops[0].ctx
+    device = _device_of(A, constructed=True)
+    assert A.num_rows == A.num_columns, A.shape
+    Bd, X = _rhs_blocks(B, X0, device, A.num_rows)
+    # the preconditioner of the recurrence: the block cycle, or dinv (None: the unit diagonal)
+    if mg is not None:
+        pre = preconditioner if callable(preconditioner) else mg.cycle
+    else:
+        pre = _jacobi_dinv(A, device) if preconditioner == 'jacobi' else None
+    recurrence = _bicgstab_recurrence if name == 'bicgstab_multi' else (_cg_recurrence if mg is None else _cg_mg_recurrence)
+    nrhs = Bd.shape[0]
+    its, res = np.zeros(nrhs, dtype=np.int32), np.zeros(nrhs)
+    for v0 in range(0, nrhs, PNL_CGB_MAXVEC):
+        v1 = min(nrhs, v0+PNL_CGB_MAXVEC)
+        g = _Group(A, ctx, Bd[v0:v1], X[v0:v1])
+        g.run(*recurrence(g, pre, tol), X0 is not None, maxiter, its[v0:v1], res[v0:v1])
+    return _block_out(B, X), its, res
+
+
+def _cg_steps(A, B, X0, tol, maxiter, preconditioner):
+    """cg_multi without its library fast paths (tests compare the two)"""
+    return _block_steps('cg_multi', A, B, X0, tol, maxiter, preconditioner)
+
+
+def _bicgstab_steps(A, B, X0, tol, maxiter, preconditioner):
+    """bicgstab_multi without its library fast path (tests compare the two)"""
+    return _block_steps('bicgstab_multi', A, B, X0, tol, maxiter, preconditioner)
 
 
 def cg_multi(A, B, X0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
@@ -210,59 +318,15 @@ def cg_multi(A, B, X0=None, tol=1e-8, maxiter=1000, preconditioner='jacobi'):
     ``multigrid.cycle`` on the block.
     Returns (X, iterations[nrhs], residuals[nrhs]): the final sqrt(r.Br) of every row; X is a torch tensor on the operator's device if
     B is one, else a numpy array."""
-    import torch
-    from ._lib import PNL_CGB_MAXVEC
-    from .linear_operators import Dense_LinearOperator, _as_block
-    from .multigrid import multigrid as _multigrid
-    # a multigrid object, or the callable of its asPreconditioner(): the block cycle of that hierarchy
-    mg = preconditioner if isinstance(preconditioner, _multigrid) else getattr(preconditioner, 'multigrid', None)
-    if mg is None and callable(preconditioner):
-        raise NotImplementedError('cg_multi: a plain callable as preconditioner for a block of right-hand sides is not built '
-                                  '(pass a multigrid object or its asPreconditioner())')
-    if mg is None and preconditioner not in ('jacobi', None):
-        raise NotImplementedError(preconditioner)
-    from .linear_operators import DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator
-    from .distributed_h2 import DistributedH2Matrix_localData
-    if isinstance(A, (DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator,
-                      DistributedH2Matrix_localData)):
-        raise NotImplementedError('cg_multi: the block products of the distributed operators loop their matvec; solve row by row with cg')
-    if not hasattr(A, 'matvec_multi'):
-        raise NotImplementedError('cg_multi needs an operator with matvec_multi; got {!r}'.format(A))
-    if mg is not None:
-        mg._require_block()                                 # NotImplementedError for a Chebyshev smoother, H2 / sparse levels
-        cycles = getattr(preconditioner, 'maxIter', 1)
-        if isinstance(A, Dense_LinearOperator) and A.num_rows == A.num_columns == mg.num_rows and cycles == 1:
-            return mg._cg_block(B, X0, tol, maxiter, None if A is mg.A else A)          # one library call (pnl_mg_cg_block)
-    elif isinstance(A, Dense_LinearOperator) and A.symmetric and preconditioner == 'jacobi':
-        return A.solve_cg_jacobi_block(B, X0, tol, maxiter)
-    if hasattr(A, 'assure_constructed'):
-        A.assure_constructed()
-    ctx = A.ctx if hasattr(A, 'ctx') else A.ops[0].ctx
-    device = getattr(A, 'device', None)
-    if device is None:
-        device = A.A.device if hasattr(A, 'A') else A._device()
-    Bd = _as_block(B, device)
-    nrhs, n = Bd.shape
-    assert nrhs >= 1 and n == A.num_rows == A.num_columns, (tuple(Bd.shape), A.shape)
-    X = torch.zeros((nrhs, n), dtype=torch.float64, device=device) if X0 is None else _as_block(X0, device).clone(
-        memory_format=torch.contiguous_format)
-    assert X.shape == Bd.shape, (tuple(X.shape), tuple(Bd.shape))
-    dinv = None
-    if preconditioner == 'jacobi':
-        d = A.diagonal
-        d = d() if callable(d) else d
-        dinv = 1./_dev_vector(d, device)
-    its, res = np.zeros(nrhs, dtype=np.int32), np.zeros(nrhs)
-    for v0 in range(0, nrhs, PNL_CGB_MAXVEC):
-        v1 = min(nrhs, v0+PNL_CGB_MAXVEC)
+    from .linear_operators import Dense_LinearOperator
+
+    def library(mg):
         if mg is not None:
-            _cg_group_mg(A, ctx, preconditioner if callable(preconditioner) else mg.cycle, Bd[v0:v1], X[v0:v1], X0 is not None, tol, maxiter,
-                         its[v0:v1], res[v0:v1])
-        else:
-            _cg_group(A, ctx, dinv, Bd[v0:v1], X[v0:v1], X0 is not None, tol, maxiter, its[v0:v1], res[v0:v1])
-    if isinstance(B, torch.Tensor):
-        return X, its, res
-    return X.cpu().numpy(), its, res
+            if isinstance(A, Dense_LinearOperator) and A.num_rows == A.num_columns == mg.num_rows and getattr(preconditioner, 'maxIter', 1) == 1:
+                return mg._cg_block(B, X0, tol, maxiter, None if A is mg.A else A)          # one library call (pnl_mg_cg_block)
+        elif isinstance(A, Dense_LinearOperator) and A.symmetric and preconditioner == 'jacobi':
+            return A.solve_cg_jacobi_block(B, X0, tol, maxiter)
+    return _block_steps('cg_multi', A, B, X0, tol, maxiter, preconditioner, library)
 
 
 def gmres(A, b, x0=None, tol=1e-8, maxiter=50, restarts=1, preconditioner=None, left=True):
@@ -270,16 +334,12 @@ def gmres(A, b, x0=None, tol=1e-8, maxiter=50, restarts=1, preconditioner=None, 
     (multigrid.asPreconditioner()).  Returns (x, iterations, residuals): the residuals are the norms of the (left-
     preconditioned) residual, the first one computed, the others from the rotated right-hand side like the reference."""
     import torch
-    device = getattr(A, 'device', None)
-    if device is None:
-        device = A.A.device if hasattr(A, 'A') else torch.device('cuda', torch.cuda.current_device())
+    device = _device_of(A)
     bd = _dev_vector(b, device)
     x = torch.zeros_like(bd) if x0 is None else _dev_vector(x0, device).clone()
     B = None
     if preconditioner == 'jacobi':
-        d = A.diagonal
-        d = d() if callable(d) else d
-        dinv = 1./_dev_vector(d, device)
+        dinv = _jacobi_dinv(A, device)
         B = lambda r: dinv*r                                   # noqa: E731
     elif callable(preconditioner):
         B = preconditioner
@@ -350,70 +410,6 @@ def gmres(A, b, x0=None, tol=1e-8, maxiter=50, restarts=1, preconditioner=None, 
     return x.cpu().numpy(), allIter, residuals
 
 
-def _bicgstab_group(A, ctx, dinv, cycle, B, X, have_x0, tol, maxiter, its, res):
-    """the loop of pnl_bicgstab_block (csrc/pnl_bicgstab_block.hip) for at most 16 rows of B, with ``A.matvec_multi`` as the product and
-    the library's step calls on device blocks.  ``cycle`` None: the preconditioner is ``dinv`` (None: the unit diagonal), applied by the
-    steps; else the external mode, ``cycle`` (a block [nv, n] -> M^-1 of every row: multigrid.cycle) applied here between the steps.
-    X [nv, n] contiguous holds the guesses and the results, its / res are filled"""
-    import torch
-    from ._lib import PNL_BCGB_STATE
-    nv, n = B.shape
-    dev = B.device
-    ext = cycle is not None
-    R, P, R0, P2, S2 = (torch.empty((nv, n), dtype=torch.float64, device=dev) for _ in range(5))
-    state = torch.zeros(nv*PNL_BCGB_STATE, dtype=torch.float64, device=dev)
-    dp = dinv.data_ptr() if dinv is not None else 0
-    ldb = max(int(B.stride(0)), n)
-
-    def product(V):
-        ctx.synchronize()
-        W = A.matvec_multi(V)
-        torch.cuda.current_stream(dev).synchronize()
-        return W
-
-    def precondition(V, out):
-        ctx.synchronize()
-        out.copy_(cycle(V))
-        torch.cuda.current_stream(dev).synchronize()
-
-    def read_state():
-        ctx.synchronize()
-        return state.cpu().numpy().reshape(nv, PNL_BCGB_STATE)
-
-    AX = product(X) if have_x0 else None
-    torch.cuda.current_stream(dev).synchronize()
-    ctx.bcgb_init(n, nv, ext, dp, B.data_ptr(), ldb, AX.data_ptr() if AX is not None else 0, n, R.data_ptr(), n, P.data_ptr(), n, R0.data_ptr(), n,
-                  P2.data_ptr(), n, state.data_ptr())
-    if ext:
-        precondition(R, R0)
-        P2.copy_(R0)                                    # P = R at the start
-        torch.cuda.current_stream(dev).synchronize()
-        ctx.bcgb_start(n, nv, R.data_ptr(), n, R0.data_ptr(), n, state.data_ptr())
-    st = read_state()
-    res[:] = st[:, 3]
-    its[:] = 0
-    active = st[:, 4] != 0.
-    for it in range(maxiter):
-        if not active.any():
-            break
-        T = product(P2)
-        ctx.bcgb_alpha(n, nv, ext, dp, T.data_ptr(), n, R0.data_ptr(), n, R.data_ptr(), n, S2.data_ptr(), n, state.data_ptr())
-        if ext:
-            precondition(R, S2)                         # S lives in R between the two steps
-        T2 = product(S2)
-        ctx.bcgb_omega(n, nv, P2.data_ptr(), n, S2.data_ptr(), n, T2.data_ptr(), n, R0.data_ptr(), n, X.data_ptr(), n, R.data_ptr(), n, tol,
-                       state.data_ptr())
-        ctx.bcgb_direction(n, nv, ext, dp, R.data_ptr(), n, T.data_ptr(), n, P.data_ptr(), n, P2.data_ptr(), n, state.data_ptr())
-        if ext:
-            precondition(P, P2)
-        st = read_state()
-        res[active] = st[active, 3]
-        done = active & (st[:, 4] == 0.)
-        its[done] = it
-        active &= ~done
-    its[active] = maxiter
-
-
 def bicgstab_multi(A, B, X0=None, tol=1e-8, maxiter=50, preconditioner=None):
     """Solve A X[v] = B[v] for the rows of a 2-D B [nrhs, n], A a general (non-symmetric) operator.  Every row runs the recurrence of
     ``bicgstab`` on its own (own alpha, omega, beta, own convergence test ||r||_2 < tol, frozen once it has converged) and the rows
@@ -429,62 +425,11 @@ def bicgstab_multi(A, B, X0=None, tol=1e-8, maxiter=50, preconditioner=None):
     Returns (X, iterations[nrhs], residuals[nrhs]): the final ||r||_2 of every row (for maxiter = 0 the start value sqrt(|r.M^-1 r|)); X
     is a torch tensor on the operator's device if B is one, else a numpy array."""
     from .linear_operators import Dense_LinearOperator
-    from .multigrid import multigrid as _multigrid
-    mg = preconditioner if isinstance(preconditioner, _multigrid) else getattr(preconditioner, 'multigrid', None)
-    if mg is None and callable(preconditioner):
-        raise NotImplementedError('bicgstab_multi: a plain callable as preconditioner for a block of right-hand sides is not built '
-                                  '(pass a multigrid object or its asPreconditioner())')
-    if mg is None and preconditioner not in ('jacobi', None):
-        raise NotImplementedError(preconditioner)
-    from .linear_operators import DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator
-    from .distributed_h2 import DistributedH2Matrix_localData
-    if isinstance(A, (DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator,
-                      DistributedH2Matrix_localData)):
-        raise NotImplementedError('bicgstab_multi: the block products of the distributed operators loop their matvec; solve row by row '
-                                  'with bicgstab')
-    if not hasattr(A, 'matvec_multi'):
-        raise NotImplementedError('bicgstab_multi needs an operator with matvec_multi; got {!r}'.format(A))
-    if mg is not None:
-        mg._require_block()                                 # NotImplementedError for a Chebyshev smoother, H2 / sparse levels
-    elif isinstance(A, Dense_LinearOperator) and A.num_rows == A.num_columns:
-        return A.solve_bicgstab_block(B, X0, tol, maxiter, preconditioner)          # one library call (pnl_bicgstab_block)
-    return _bicgstab_steps(A, B, X0, tol, maxiter, preconditioner)
 
-
-def _bicgstab_steps(A, B, X0, tol, maxiter, preconditioner):
-    """bicgstab_multi over the library's step calls, groups of 16 rows; the arguments have been checked"""
-    import torch
-    from ._lib import PNL_CGB_MAXVEC
-    from .linear_operators import _as_block
-    from .multigrid import multigrid as _multigrid
-    mg = preconditioner if isinstance(preconditioner, _multigrid) else getattr(preconditioner, 'multigrid', None)
-    if hasattr(A, 'assure_constructed'):
-        A.assure_constructed()
-    ctx = A.ctx if hasattr(A, 'ctx') else A.ops[0].ctx
-    device = getattr(A, 'device', None)
-    if device is None:
-        device = A.A.device if hasattr(A, 'A') else A._device()
-    Bd = _as_block(B, device)
-    nrhs, n = Bd.shape
-    assert nrhs >= 1 and n == A.num_rows == A.num_columns, (tuple(Bd.shape), A.shape)
-    X = torch.zeros((nrhs, n), dtype=torch.float64, device=device) if X0 is None else _as_block(X0, device).clone(
-        memory_format=torch.contiguous_format)
-    assert X.shape == Bd.shape, (tuple(X.shape), tuple(Bd.shape))
-    dinv = None
-    if preconditioner == 'jacobi':
-        d = A.diagonal
-        d = d() if callable(d) else d
-        dinv = 1./_dev_vector(d, device)
-    cycle = None
-    if mg is not None:
-        cycle = preconditioner if callable(preconditioner) else mg.cycle
-    its, res = np.zeros(nrhs, dtype=np.int32), np.zeros(nrhs)
-    for v0 in range(0, nrhs, PNL_CGB_MAXVEC):
-        v1 = min(nrhs, v0+PNL_CGB_MAXVEC)
-        _bicgstab_group(A, ctx, dinv, cycle, Bd[v0:v1], X[v0:v1], X0 is not None, tol, maxiter, its[v0:v1], res[v0:v1])
-    if isinstance(B, torch.Tensor):
-        return X, its, res
-    return X.cpu().numpy(), its, res
+    def library(mg):
+        if mg is None and isinstance(A, Dense_LinearOperator) and A.num_rows == A.num_columns:
+            return A.solve_bicgstab_block(B, X0, tol, maxiter, preconditioner)          # one library call (pnl_bicgstab_block)
+    return _block_steps('bicgstab_multi', A, B, X0, tol, maxiter, preconditioner, library)
 
 
 def bicgstab(A, b, x0=None, tol=1e-8, maxiter=50, preconditioner=None):
@@ -493,16 +438,12 @@ def bicgstab(A, b, x0=None, tol=1e-8, maxiter=50, preconditioner=None):
     if getattr(b, 'ndim', None) == 2 or (not hasattr(b, 'ndim') and np.ndim(b) == 2):
         return bicgstab_multi(A, b, x0, tol, maxiter, preconditioner)
     import torch
-    device = getattr(A, 'device', None)
-    if device is None:
-        device = A.A.device if hasattr(A, 'A') else torch.device('cuda', torch.cuda.current_device())
+    device = _device_of(A)
     bd = _dev_vector(b, device)
     x = torch.zeros_like(bd) if x0 is None else _dev_vector(x0, device).clone()
     B = None
     if preconditioner == 'jacobi':
-        d = A.diagonal
-        d = d() if callable(d) else d
-        dinv = 1./_dev_vector(d, device)
+        dinv = _jacobi_dinv(A, device)
         B = lambda r: dinv*r                                   # noqa: E731
     elif callable(preconditioner):
         B = preconditioner

@@ -589,6 +589,27 @@ def test_dense_operator_and_cg_multi_on_synthetic_matrices():
         cctx.close()
 
 
+@gpu
+@pytest.mark.parametrize('name,n,maxiter', (('dom', 257, 1000), ('lap', 65, 200)))
+def test_step_loop_on_the_dense_operator_has_the_bits_of_the_library_call(name, n, maxiter):
+    """solvers._cg_steps (the Python loop over pnl_cgb_init / _update / _refresh / _direction, A.matvec_multi as the product) on the
+    dense operator returns the bits of solve_cg_jacobi_block (pnl_cg_jacobi_block), from a zero guess and from a seeded X0: b - 0 is b
+    in every bit, both loops use pnl_gemv_block, whose bits do not depend on the leading dimensions, and the same steps.  n = 257: two
+    workgroups and a tail; 17 rows: a full group and a remainder of one; lap(65) passes 50 iterations and takes the refresh"""
+    from pynucleus_amd import solvers
+    A = dom(n) if name == 'dom' else lap(n)
+    B = rhs_block(n, 17)
+    ctx = _context()
+    op = _dense_operator(ctx, A)
+    X, its, res = op.solve_cg_jacobi_block(B, tol=TOL, maxiter=maxiter)
+    assert name != 'lap' or its.max() > 50
+    _assert_same(solvers._cg_steps(op, B, None, TOL, maxiter, 'jacobi'), (X, its, res), 'library call against the step loop')
+    X0 = np.random.default_rng(9300+n).standard_normal((17, n))
+    _assert_same(solvers._cg_steps(op, B, X0, TOL, maxiter, 'jacobi'), op.solve_cg_jacobi_block(B, X0, tol=TOL, maxiter=maxiter),
+                 'library call against the step loop, from a guess')
+    ctx.close()
+
+
 _OPERATORS = {}
 
 
