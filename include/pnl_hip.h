@@ -914,6 +914,39 @@ int pnl_mg_cycle_block(pnl_mg *mg, int nvec, const double *B_dev, int64_t ldb, d
 int pnl_mg_cg_block(pnl_mg *mg, const double *A_dev, int64_t ldA, int nrhs, const double *B_dev, int64_t ldb, double *X_dev, int64_t ldx,
                     double tol, int maxiter, int x_is_zero, int *iters, double *residuals);
 
+/* ---- the vector side of a block eigensolver (csrc/pnl_eig_block.hip): the three contractions of LOBPCG for the smallest eigenpairs of
+ *      A x = lambda M x on blocks of vectors (solvers.lobpcg runs the loop; the small Rayleigh-Ritz problem stays on the host). ----------
+ * Blocks are row-major [k][ld] with ld >= n, one vector per row as in pnl_gemv_block; padding columns are neither read into a sum nor
+ * written.  Asynchronous on the context's stream.  No floating-point atomics: every sum has a shape that depends on n only (the grid
+ * rule of the pnl_cgb_* steps: element i belongs to workgroup (i / 256) mod min(256, ceil(n / 256))), so the same input gives the
+ * same bits.  PNL_ERR_INVALID, before any launch, for a null pointer (but dinv_dev and W_dev of pnl_eigb_residual), a size out of
+ * range, a leading dimension below its row length, a written block that is also an input of the call.
+ *
+ * pnl_eigb_gram: G[a*ldg + b] = sum_i U[a][i] V[b][i], 1 <= ku, kv <= PNL_EIGB_MAXBASIS (three groups of 16 rows), ldg >= kv: the
+ * Gram matrix of the Rayleigh-Ritz step.  v_mfma_f64_16x16x4_f64 with 16 rows of U as the A operand, 16 rows of V as the B operand
+ * and the n direction as MFMA's k; rows that do not exist are zero operands whose results are not stored.  A workgroup writes its
+ * 16 x 16 partial tiles to a scratch buffer of the context, a second launch adds them in ascending workgroup order.  The bits of
+ * G[a][b] depend on U[a], V[b] and n only -- not on ku, kv, the positions a and b or the other rows; with U_dev == V_dev and
+ * ldu == ldv G is bitwise symmetric.
+ *
+ * pnl_eigb_combine: Y[a][i] = sum_{b < kin} C[a*ldc + b] S[b][i], kin <= PNL_EIGB_MAXBASIS, kout <= 16, ldc >= kin, C in device
+ * memory: the basis rotation X <- C^T [X; W; P].  Per element t = C[a][0] S[0][i], then t = fma(C[a][b], S[b][i], t) in ascending b;
+ * every S[b][i] is loaded once per call.  Y must be neither S nor C.
+ *
+ * pnl_eigb_residual: for the columns v < nv <= 16 whose bit is set in mask (mask != 0, no bit at or above nv):
+ * R_v = fma(-theta_v, MX_v, AX_v); W_v = dinv R_v where W_dev is given (dinv_dev NULL: the unit diagonal, W_v = R_v);
+ * sums_dev[2 v] = R_v . R_v, sums_dev[2 v + 1] = MX_v . MX_v.  theta_dev: nv doubles, sums_dev: 2 nv doubles, both on the device.
+ * Columns outside mask are neither read nor written (their sums neither).  AX_dev and MX_dev may be any two blocks that are only
+ * read (MX_dev is the X block when M = I); R_dev and W_dev must differ from each other and from both. */
+#define PNL_EIGB_MAXBASIS 48
+int pnl_eigb_gram(pnl_context *ctx, int n, int ku, const double *U_dev, int64_t ldu, int kv, const double *V_dev, int64_t ldv, double *G_dev,
+                  int64_t ldg);
+int pnl_eigb_combine(pnl_context *ctx, int n, int kin, const double *S_dev, int64_t lds, int kout, const double *C_dev, int64_t ldc,
+                     double *Y_dev, int64_t ldy);
+int pnl_eigb_residual(pnl_context *ctx, int n, int nv, unsigned mask, const double *AX_dev, int64_t ldax, const double *MX_dev, int64_t ldmx,
+                      const double *theta_dev, const double *dinv_dev, double *R_dev, int64_t ldr, double *W_dev, int64_t ldw,
+                      double *sums_dev);
+
 #ifdef __cplusplus
 }
 #endif

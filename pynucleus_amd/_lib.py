@@ -38,7 +38,8 @@ EXPORTS = ['pnl_create', 'pnl_destroy', 'pnl_error_string', 'pnl_version', 'pnl_
            'pnl_h2_matvec_block', 'pnl_h2_upward_block', 'pnl_h2_interact_block', 'pnl_h2_downward_block',
            'pnl_cg_jacobi_block', 'pnl_cgb_init', 'pnl_cgb_update', 'pnl_cgb_refresh', 'pnl_cgb_direction',
            'pnl_cgb_residual', 'pnl_cgb_start', 'pnl_cgb_step', 'pnl_cgb_beta', 'pnl_mg_cycle_block', 'pnl_mg_cg_block',
-           'pnl_bicgstab_block', 'pnl_bcgb_init', 'pnl_bcgb_start', 'pnl_bcgb_alpha', 'pnl_bcgb_omega', 'pnl_bcgb_direction']
+           'pnl_bicgstab_block', 'pnl_bcgb_init', 'pnl_bcgb_start', 'pnl_bcgb_alpha', 'pnl_bcgb_omega', 'pnl_bcgb_direction',
+           'pnl_eigb_gram', 'pnl_eigb_combine', 'pnl_eigb_residual']
 
 PNL_FUN_BRUSSELATOR, PNL_FUN_CUBIC = 0, 1
 PNL_IMEX_CG_MG, PNL_IMEX_CHOL = 0, 1
@@ -48,6 +49,8 @@ PNL_CGB_MAXVEC, PNL_CGB_STATE = 16, 8
 # pnl_bcgb_*: doubles per column of the state; the breakdown codes of slot [6]
 PNL_BCGB_STATE = 12
 PNL_BCGB_OK, PNL_BCGB_TR0, PNL_BCGB_OMEGA, PNL_BCGB_KAPPA, PNL_BCGB_NONFINITE = 0, 1, 2, 3, 4
+# pnl_eigb_*: rows of a Rayleigh-Ritz basis at most (three groups of 16)
+PNL_EIGB_MAXBASIS = 48
 
 
 def source_sha16():
@@ -236,6 +239,9 @@ def load():
     L.pnl_bcgb_alpha.argtypes = [vp, i32, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.pnl_bcgb_omega.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, dbl, vp]
     L.pnl_bcgb_direction.argtypes = [vp, i32, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.pnl_eigb_gram.argtypes = [vp, i32, i32, vp, i64, i32, vp, i64, vp, i64]
+    L.pnl_eigb_combine.argtypes = [vp, i32, i32, vp, i64, i32, vp, i64, vp, i64]
+    L.pnl_eigb_residual.argtypes = [vp, i32, i32, C.c_uint, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp]
     L.pnl_mg_cycle_block.argtypes = [vp, i32, vp, i64, vp, i64, i32]
     L.pnl_mg_cg_block.argtypes = [vp, vp, i64, i32, vp, i64, vp, i64, dbl, i32, i32, vp, vp]
     L.pnl_upload_sparsity.argtypes = [vp, i32, vp, vp]
@@ -806,6 +812,19 @@ class Context:
         """active columns: P = R + beta (P - omega T); not external: P2 = dinv P"""
         self.check(self.L.pnl_bcgb_direction(self.h, int(n), int(nvec), int(bool(external)), _vp(dinv_ptr), _vp(R_ptr), int(ldr), _vp(T_ptr), int(ldt),
                                              _vp(P_ptr), int(ldp), _vp(P2_ptr), int(ldp2), _vp(state_ptr)))
+
+    def eigb_gram(self, n, ku, U_ptr, ldu, kv, V_ptr, ldv, G_ptr, ldg):
+        """G[a, b] = U[a] . V[b] for ku x kv <= 48 x 48 rows (fp64 MFMA, fixed-shape sums; include/pnl_hip.h)"""
+        self.check(self.L.pnl_eigb_gram(self.h, int(n), int(ku), _vp(U_ptr), int(ldu), int(kv), _vp(V_ptr), int(ldv), _vp(G_ptr), int(ldg)))
+
+    def eigb_combine(self, n, kin, S_ptr, lds, kout, C_ptr, ldc, Y_ptr, ldy):
+        """Y[a] = sum_b C[a, b] S[b] for kin <= 48 rows of S and kout <= 16 rows of Y; C [kout, ldc] on the device"""
+        self.check(self.L.pnl_eigb_combine(self.h, int(n), int(kin), _vp(S_ptr), int(lds), int(kout), _vp(C_ptr), int(ldc), _vp(Y_ptr), int(ldy)))
+
+    def eigb_residual(self, n, nv, mask, AX_ptr, ldax, MX_ptr, ldmx, theta_ptr, dinv_ptr, R_ptr, ldr, W_ptr, ldw, sums_ptr):
+        """columns of mask: R = AX - theta MX, W = dinv R (W_ptr 0: no W; dinv_ptr 0: the unit diagonal), sums[2v] = R.R, sums[2v+1] = MX.MX"""
+        self.check(self.L.pnl_eigb_residual(self.h, int(n), int(nv), int(mask), _vp(AX_ptr), int(ldax), _vp(MX_ptr), int(ldmx), _vp(theta_ptr),
+                                            _vp(dinv_ptr), _vp(R_ptr), int(ldr), _vp(W_ptr), int(ldw), _vp(sums_ptr)))
 
     def h2_matvec_block(self, nvec, X_ptr, ldx, Y_ptr, ldy):
         """Y[v] += far field of X[v] for the H2 operator set up in the context, without float atomics (pnl_h2_block.hip)"""

@@ -147,6 +147,7 @@ struct pnl_context {
     DevBuf b_blk_part, b_blk_xt;      // pnl_block.hip: partial sums of the column chunks [chunk][16][nrows]; the transposed group of vectors [n][NV]
     DevBuf b_kb_part;                 // pnl_krylov_block.h: partial sums of the dot products of the block Krylov steps [5][256][16]
     DevBuf b_cgb_work, b_bcgb_work;   // pnl_cg_jacobi_block: dinv, R, P, AP, Z and the state; pnl_bicgstab_block: dinv, seven blocks and the state
+    DevBuf b_eigb_part;               // pnl_eig_block.hip: the partial tiles of pnl_eigb_gram [workgroup][9 tile pairs][16 x 16]
     std::vector<int32_t> slab_rowdofs, slab_coldofs;
     int slab_rows = 0, slab_cols = 0;
     std::vector<DevKernel> kcls_host;

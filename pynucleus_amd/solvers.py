@@ -111,9 +111,10 @@ class _Group:
         import torch
         torch.cuda.current_stream(self.dev).synchronize()
 
-    def product(self, V):
+    def product(self, V, op=None):
+        """A V, or ``op`` V for another operator of the same size (the mass matrix of lobpcg)"""
         self.ctx.synchronize()
-        W = self.A.matvec_multi(V)
+        W = (self.A if op is None else op).matvec_multi(V)
         self.fence()
         return W
 
@@ -243,7 +244,7 @@ def _jacobi_dinv(A, device):
 
 
 def _block_preconditioner(name, A, preconditioner):
-    """what ``name`` (cg_multi, bicgstab_multi) takes: the multigrid behind ``preconditioner`` (None for 'jacobi' and None) if A and it
+    """what ``name`` (cg_multi, bicgstab_multi, lobpcg) takes: the multigrid behind ``preconditioner`` (None for 'jacobi' and None) if A and it
     are fit for a block of right-hand sides, NotImplementedError if not"""
     from .multigrid import multigrid as _multigrid
     from .linear_operators import DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator
@@ -257,13 +258,20 @@ def _block_preconditioner(name, A, preconditioner):
         raise NotImplementedError(preconditioner)
     if isinstance(A, (DistributedDense_LinearOperator, DistributedSlab_LinearOperator, DistributedSparse_LinearOperator,
                       DistributedH2Matrix_localData)):
-        raise NotImplementedError('{}: the block products of the distributed operators loop their matvec; solve row by row with {}'.format(
-            name, name[:-len('_multi')]))
+        raise NotImplementedError('{}: the block products of the distributed operators loop their matvec; {}'.format(
+            name, 'eigenpairs of distributed operators are not built' if name == 'lobpcg' else 'solve row by row with '+name[:-len('_multi')]))
     if not hasattr(A, 'matvec_multi'):
         raise NotImplementedError('{} needs an operator with matvec_multi; got {!r}'.format(name, A))
     if mg is not None:
         mg._require_block()                                 # NotImplementedError for a Chebyshev smoother, H2 / sparse levels
     return mg
+
+
+def _block_context(A):
+    """(context, device) of the operator behind a block solve, constructed if it is assembled lazily"""
+    if hasattr(A, 'assure_constructed'):
+        A.assure_constructed()
+    return (A.ctx if hasattr(A, 'ctx') else A.ops[0].ctx), _device_of(A, constructed=True)
 
 
 def _block_steps(name, A, B, X0, tol, maxiter, preconditioner, library=None):
@@ -275,10 +283,7 @@ def _block_steps(name, A, B, X0, tol, maxiter, preconditioner, library=None):
     out = library(mg) if library is not None else None
     if out is not None:
         return out
-    if hasattr(A, 'assure_constructed'):
-        A.assure_constructed()
-    ctx = A.ctx if hasattr(A, 'ctx') else A.ops[0].ctx
-    device = _device_of(A, constructed=True)
+    ctx, device = _block_context(A)
     assert A.num_rows == A.num_columns, A.shape
     Bd, X = _rhs_blocks(B, X0, device, A.num_rows)
     # the preconditioner of the recurrence: the block cycle, or dinv (None: the unit diagonal)
@@ -476,6 +481,233 @@ def bicgstab(A, b, x0=None, tol=1e-8, maxiter=50, preconditioner=None):
     if isinstance(b, torch.Tensor):
         return x, its, residuals
     return x.cpu().numpy(), its, residuals
+
+
+_RITZ_RANK_TOL = 1e-10
+
+
+def _ritz(GA, GM, idx, m):
+    """The Rayleigh-Ritz problem of lobpcg on the rows ``idx`` of the Gram matrices S A S^T and S M S^T of a basis S: the ``m`` smallest
+    Ritz values and C [len(idx), m] with (C^T S) M (C^T S)^T = I.  The basis may be numerically rank deficient (P against W late in the
+    iteration): it is scaled to a unit diagonal of G_M, and the directions of the scaled G_M below _RITZ_RANK_TOL times its largest
+    eigenvalue -- the level of a Gram matrix's own rounding is n u -- are dropped through its eigendecomposition."""
+    idx = np.asarray(idx, dtype=np.int64)
+    dg = np.diagonal(GM)[idx]
+    idx = idx[np.isfinite(dg) & (dg > 0.)]
+    GA, GM = GA[np.ix_(idx, idx)], GM[np.ix_(idx, idx)]
+    GA, GM = .5*(GA+GA.T), .5*(GM+GM.T)
+    d = 1./np.sqrt(np.diagonal(GM))
+    GA, GM = d[:, None]*GA*d[None, :], d[:, None]*GM*d[None, :]
+    lam, V = np.linalg.eigh(GM)
+    keep = lam > _RITZ_RANK_TOL*lam[-1]
+    if int(keep.sum()) < m:
+        raise np.linalg.LinAlgError('lobpcg: the basis has rank {} < {} (linearly dependent start vectors?)'.format(int(keep.sum()), m))
+    B = V[:, keep]/np.sqrt(lam[keep])
+    theta, Z = np.linalg.eigh(B.T@GA@B)
+    return theta[:m], idx, d[:, None]*(B@Z[:, :m])
+
+
+def _mass_operator(M, ctx, device, n):
+    """``M`` of lobpcg as an operator with matvec_multi: None stays None, a scipy.sparse matrix becomes a CSR_LinearOperator in ``ctx``
+    (which must know the n DoFs, as every context that a builder has used does)"""
+    import torch
+    if M is None or hasattr(M, 'matvec_multi'):
+        return M
+    import scipy.sparse as sp
+    from .linear_operators import CSR_LinearOperator
+    if not sp.issparse(M):
+        raise NotImplementedError('lobpcg: M is None, a scipy.sparse matrix or an operator with matvec_multi; got {!r}'.format(type(M)))
+    Mc = sp.csr_matrix(M, dtype=np.float64)
+    Mc.sum_duplicates()
+    Mc.sort_indices()
+    assert Mc.shape == (n, n), (Mc.shape, n)
+    op = CSR_LinearOperator(Mc.indptr, Mc.indices, n, ctx, device)
+    op.data_dev[:Mc.nnz] = torch.from_numpy(np.ascontiguousarray(Mc.data)).to(device)
+    return op
+
+
+def lobpcg(A, k=1, M=None, X0=None, tol=1e-8, maxiter=200, preconditioner='jacobi', blockSize=None):
+    """The ``k`` smallest eigenvalues theta[0] <= ... <= theta[k-1] of A x = theta M x and their eigenvectors X [k, n] by LOBPCG
+    (Knyazev 2001) with soft locking.  ``A``: symmetric positive definite, any operator with ``matvec_multi`` (dense, CSR, SSS, H2 in
+    either far-field mode, interpolated).  ``M``: None (the identity), a scipy.sparse matrix (wrapped into a CSR_LinearOperator in A's
+    context) or an operator with ``matvec_multi``; symmetric positive definite.  A block of m = ``blockSize`` (default
+    min(16, n, k + max(2, k // 2)); k <= m <= 16) vectors is iterated: the rows beyond k are guard vectors, which speed up convergence
+    and are never required to converge.  ``X0`` [m or k, n] is the start; without it, and for the rows it lacks, the rows of a
+    standard-normal block drawn on the CPU with seed 0, so that a run repeats.  ``preconditioner``: 'jacobi', None, or a ``multigrid``
+    object / its ``asPreconditioner()`` (dense levels, Jacobi smoother: the block V cycle on the residuals of the active columns).
+
+    One pass: R = AX - theta MX, W = T R and the residual sums (pnl_eigb_residual; T the preconditioner); W made M-orthogonal to X and
+    scaled (pnl_eigb_gram, pnl_eigb_combine); one ``A.matvec_multi(W)`` and, with M, one ``M.matvec_multi(W)``; the Gram matrices of
+    the basis [X; W; P] against [AX; AW; AP] and [MX; MW; MP] (pnl_eigb_gram, at most 48 x 48), read back once; the small generalised
+    eigenproblem on the host (``_ritz``); X, AX, MX and P, AP, MP as combinations of the basis (pnl_eigb_combine).
+
+    residuals[v] = ||A x_v - theta_v M x_v||_2 / (|theta_v| ||M x_v||_2).  The AX and MX that the passes carry drift like a recursive
+    CG residual, so a column counts as converged only on recomputed data: when the carried residuals of the first k columns are all
+    <= tol, or maxiter is reached, AX = A X and MX = M X are formed afresh, theta become the Rayleigh quotients and the residuals are
+    recomputed; then the solver returns, or goes on from these blocks if passes remain.  The returned residuals are always of that
+    kind.  ``passes < maxiter`` with all residuals <= tol is success; else passes == maxiter and the residuals say how far each
+    column got.  maxiter = 0 returns the Rayleigh-Ritz values of X0 and their residuals.  The rows of X are scaled to x^T M x = 1.
+    Returns (theta [k], X [k, n], passes, residuals [k]); X is a torch tensor on the operator's device if X0 is one, else numpy."""
+    import torch
+    from ._lib import PNL_CGB_MAXVEC, PNL_EIGB_MAXBASIS
+    from .linear_operators import _as_block
+    mg = _block_preconditioner('lobpcg', A, preconditioner)
+    k = int(k)
+    if k > PNL_CGB_MAXVEC or (blockSize is not None and blockSize > PNL_CGB_MAXVEC):
+        raise NotImplementedError('lobpcg: more than {} vectors are not built (k = {}, blockSize = {})'.format(PNL_CGB_MAXVEC, k, blockSize))
+    ctx, device = _block_context(A)
+    n = A.num_rows
+    assert A.num_rows == A.num_columns, A.shape
+    m = int(blockSize) if blockSize is not None else min(PNL_CGB_MAXVEC, n, k+max(2, k//2))
+    if not 1 <= k <= m <= n:
+        raise ValueError('lobpcg: 1 <= k <= blockSize <= n is needed (k = {}, blockSize = {}, n = {})'.format(k, m, n))
+    if maxiter < 0:
+        raise ValueError('lobpcg: maxiter < 0')
+    Mop = _mass_operator(M, ctx, device, n)
+    if mg is not None:
+        cycle = preconditioner if callable(preconditioner) else mg.cycle
+        dinv = None
+    else:
+        cycle = None
+        dinv = _jacobi_dinv(A, device).contiguous() if preconditioner == 'jacobi' else None
+    f64 = dict(dtype=torch.float64, device=device)
+    LDG = PNL_EIGB_MAXBASIS
+
+    # two sets of blocks [4 m, n], rows [raw W; X; W; P]: the basis [X; W; P] and [raw W; X] are contiguous, a combination is
+    # written to the other set
+    S = [torch.zeros((4*m, n), **f64) for _ in range(2)]
+    AS = [torch.zeros((4*m, n), **f64) for _ in range(2)]
+    MS = [torch.zeros((4*m, n), **f64) for _ in range(2)] if Mop is not None else S
+    Rb = torch.zeros((m, n), **f64)
+    Gd = torch.zeros((2, LDG, LDG), **f64)
+    Cd = torch.zeros((2, PNL_CGB_MAXVEC, LDG), **f64)
+    theta_d, sums_d = torch.zeros(m, **f64), torch.zeros(2*m, **f64)
+    start = torch.randn((m, n), generator=torch.Generator().manual_seed(0), dtype=torch.float64).to(device)
+    if X0 is not None:
+        X0d = _as_block(X0, device)
+        if X0d.shape[1] != n or X0d.shape[0] not in (k, m):
+            raise ValueError('lobpcg: X0 of shape {} for k = {}, blockSize = {}, n = {}'.format(tuple(X0d.shape), k, m, n))
+        start[:X0d.shape[0]] = X0d
+    cur = 0
+    S[cur][m:2*m] = start
+    rows = lambda T, b: T[b*m:(b+1)*m]                       # noqa: E731  block b of a set: 0 raw W, 1 X, 2 W, 3 P
+    g = _Group(A, ctx, Rb, Rb)                              # the fences and the products of the block solvers
+    fence = g.fence
+
+    def product(op, V, out):
+        out.copy_(g.product(V, None if op is A else op))
+        fence()
+    ptr = lambda T, b: T.data_ptr()+8*b*m*n                 # noqa: E731
+
+    def grams(ka, kb, b):
+        """(S A S^T, S M S^T) of the rows [b m, b m + ka) of the current set against the same rows of AS and MS, on the host"""
+        ctx.eigb_gram(n, ka, ptr(S[cur], b), n, kb, ptr(AS[cur], b), n, Gd[0].data_ptr(), LDG)
+        ctx.eigb_gram(n, ka, ptr(S[cur], b), n, kb, ptr(MS[cur], b), n, Gd[1].data_ptr(), LDG)
+        ctx.synchronize()
+        G = Gd.cpu().numpy()
+        return G[0, :ka, :kb], G[1, :ka, :kb]
+
+    def upload(theta, Cx=None, Cp=None):
+        """theta and the coefficients of X (and P), as [m, kin] row-major blocks, to the device"""
+        Ch = np.zeros((2, PNL_CGB_MAXVEC, LDG))
+        if Cx is not None:
+            Ch[0, :Cx.shape[1], :Cx.shape[0]] = Cx.T
+        if Cp is not None:
+            Ch[1, :Cp.shape[1], :Cp.shape[0]] = Cp.T
+        Cd.copy_(torch.from_numpy(Ch))
+        theta_d.copy_(torch.from_numpy(np.ascontiguousarray(theta)))
+        fence()
+
+    def rotate(kin, withP):
+        """X, AX, MX (and P, AP, MP) of the other set from kin rows of the basis of the current one"""
+        nonlocal cur
+        for T in (S, AS)+((MS,) if Mop is not None else ()):
+            ctx.eigb_combine(n, kin, ptr(T[cur], 1), n, m, Cd[0].data_ptr(), LDG, ptr(T[cur ^ 1], 1), n)
+            if withP:
+                ctx.eigb_combine(n, kin, ptr(T[cur], 1), n, m, Cd[1].data_ptr(), LDG, ptr(T[cur ^ 1], 3), n)
+        cur ^= 1
+
+    def residual(active, res, W):
+        """R (and, with W, the raw W = dinv R) of the active columns; their carried or explicit residuals into res"""
+        mask = int(sum(1 << v for v in range(m) if active[v]))
+        ctx.eigb_residual(n, m, mask, ptr(AS[cur], 1), n, ptr(MS[cur], 1), n, theta_d.data_ptr(), dinv.data_ptr() if dinv is not None else 0,
+                          Rb.data_ptr(), n, ptr(S[cur], 0) if W else 0, n, sums_d.data_ptr())
+        ctx.synchronize()
+        s = sums_d.cpu().numpy()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            r = np.sqrt(s[0::2])/(np.abs(theta)*np.sqrt(s[1::2]))
+        res[active] = np.where(np.isfinite(r), r, np.inf)[active]
+
+    fence()
+    product(A, rows(S[cur], 1), rows(AS[cur], 1))
+    if Mop is not None:
+        product(Mop, rows(S[cur], 1), rows(MS[cur], 1))
+    GA, GM = grams(m, m, 1)
+    theta, idx, C = _ritz(GA, GM, np.arange(m), m)
+    upload(theta, C)
+    rotate(m, False)
+    haveP = False
+    everyone = np.ones(m, dtype=bool)
+    active = everyone.copy()
+    res = np.full(m, np.inf)
+    passes = 0
+    ownW = cycle is None
+    while True:
+        residual(active, res, ownW)
+        active &= res > tol
+        if (res[:k] <= tol).all() or passes == maxiter:
+            # the carried AX, MX say so: recompute them, theta as Rayleigh quotients and the residuals of every column
+            product(A, rows(S[cur], 1), rows(AS[cur], 1))
+            if Mop is not None:
+                product(Mop, rows(S[cur], 1), rows(MS[cur], 1))
+            GA, GM = grams(m, m, 1)
+            theta, xmx = np.diagonal(GA)/np.diagonal(GM), np.diagonal(GM).copy()
+            upload(theta)
+            residual(everyone, res, ownW)
+            if (res[:k] <= tol).all() or passes == maxiter:
+                break
+            active = res > tol
+        if not ownW:
+            # the block V cycle on the active residuals only; the raw W of the other rows stays what it was (they get weight 0)
+            rows_on = torch.from_numpy(np.nonzero(active)[0]).to(device)
+            rows(S[cur], 0).index_copy_(0, rows_on, g.apply(cycle, Rb.index_select(0, rows_on)))
+            fence()
+        # W <- D (W - (W MX^T) X), D = 1 / ||W||_2 for the active rows and 0 for the others: the coefficients stay on the device
+        ctx.eigb_gram(n, m, ptr(S[cur], 0), n, m, ptr(MS[cur], 1), n, Gd[0].data_ptr(), LDG)
+        ctx.eigb_gram(n, m, ptr(S[cur], 0), n, m, ptr(S[cur], 0), n, Gd[1].data_ptr(), LDG)
+        ctx.synchronize()
+        on = torch.from_numpy(active).to(device)
+        nrm2 = torch.diagonal(Gd[1])[:m]
+        sc = torch.where(on & (nrm2 > 0.), torch.rsqrt(torch.where(nrm2 > 0., nrm2, torch.ones_like(nrm2))), torch.zeros_like(nrm2))
+        Cd[0].zero_()
+        Cd[0, :m, :m] = torch.diag(sc)
+        Cd[0, :m, m:2*m] = -sc[:, None]*torch.where(on[:, None], Gd[0, :m, :m], torch.zeros_like(Gd[0, :m, :m]))
+        fence()
+        ctx.eigb_combine(n, 2*m, ptr(S[cur], 0), n, m, Cd[0].data_ptr(), LDG, ptr(S[cur], 2), n)
+        product(A, rows(S[cur], 2), rows(AS[cur], 2))
+        if Mop is not None:
+            product(Mop, rows(S[cur], 2), rows(MS[cur], 2))
+        GA, GM = grams(3*m, 3*m, 1)
+        act = np.nonzero(active)[0]
+        theta, idx, C = _ritz(GA, GM, np.concatenate([np.arange(m), m+act, 2*m+act if haveP else act[:0]]), m)
+        Cx = np.zeros((3*m, m))
+        Cx[idx] = C
+        Cp = Cx.copy()
+        Cp[:m] = 0.
+        upload(theta, Cx, Cp)
+        rotate(3*m, True)
+        haveP = True
+        passes += 1
+    # the rows that are returned: x^T M x = 1, and ascending theta (Rayleigh quotients of a cluster may have left the order of the
+    # Ritz values by a rounding)
+    order = np.argsort(theta[:k], kind='stable')
+    Cn = np.zeros((k, k))
+    Cn[order, np.arange(k)] = 1./np.sqrt(xmx[order])
+    upload(theta, Cn)
+    X = torch.empty((k, n), **f64)
+    ctx.eigb_combine(n, k, ptr(S[cur], 1), n, k, Cd[0].data_ptr(), LDG, X.data_ptr(), n)
+    ctx.synchronize()
+    return theta[order], (X if isinstance(X0, torch.Tensor) else X.cpu().numpy()), passes, res[order]
 
 
 class _DenseFactor:
